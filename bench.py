@@ -2,6 +2,10 @@
 """Benchmark of the hot path: disparity Mpix/s on synthetic 1920x1080 pairs, D=128 (BASELINE.json).
 
     python bench.py --gpus N --steps K --warmup W [--workload bilateral|guided2|guided|geodesic|wmedian]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps, writes its outputs if --dump-outputs is given and prints the line.  The
+secondary legs (the batch API, the PCIe-inclusive one-call rate, the CPU baseline) run only under --full.
 
 A "step" is one pass of the hot path over one batch of `--frames` stereo pairs that are already
 resident in HBM (uploaded before the timed region).  One process per GPU; frames are independent,
@@ -12,8 +16,14 @@ N > 1: under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus
 rank (RANK / LOCAL_RANK / WORLD_SIZE from the environment); a bare `python bench.py --gpus N` starts the N
 ranks itself as child processes (launch_ranks: the parent never touches the GPU).  Either way WORLD_SIZE
 must equal --gpus and every rank must find its own GPU, or the run fails loudly.  After the timed region the
-ranks leave the process group; rank 0 alone then drives all N devices from one process through the library's
-own batch API (`asw_stereo_match_batch`, 64 frames, host buffers in and out) and reports it as `batch_api`.
+ranks leave the process group; under --full rank 0 alone then drives all N devices from one process through the
+library's own batch API (`asw_stereo_match_batch`, 64 frames, host buffers in and out) and reports it as `batch_api`.
+
+--dump-outputs DIR: after the timed region every rank writes what the last timed step left for a caller of the resident
+path, as float32 .npy files: `disparity` (every frame's disparity map, frames x H x W) and `cost_volume_last_frame` (the
+kept cost volume of the last frame, planes x H x W).  An array larger than its share of DUMP_BYTES is replaced by a fixed,
+seeded sample of its flattened values (sorted indices, numpy default_rng(DUMP_SEED)), so that two builds run with the same
+arguments can be compared value for value.  With N > 1 ranks the names carry a `_rank<r>` suffix.
 """
 import argparse
 import json
@@ -29,6 +39,8 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: 8.0 TB/s spec
 F64_PEAK_TFLOPS = 78.6      # vector f64
+DUMP_BYTES = 60 * 10**6     # --dump-outputs: all files of all ranks together (64 MB at most, headers included)
+DUMP_SEED = 20261016        # --dump-outputs: the sample of an array too large to write whole
 
 WORKLOADS = {
     # name: (algorithm enum, candidates(numD), label)
@@ -114,10 +126,15 @@ def parse_args(argv=None):
     ap.add_argument("--disp", type=int, default=128)
     ap.add_argument("--win", type=int, default=15)
     ap.add_argument("--frames", type=int, default=8, help="frames per GPU per step (C5: 64 frames / 8 GPUs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's work, also run the secondary legs: asw_stereo_match_batch (--batch-frames), "
+                         "the PCIe-inclusive one-call rate and the CPU baseline (--no-cpu skips it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32, %d MB at most)" % (DUMP_BYTES // 10**6))
     ap.add_argument("--batch-frames", type=int, default=64,
-                    help="frames of the asw_stereo_match_batch leg over all --gpus devices (C5: 64); 0 skips it")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu", action="store_true")
+                    help="--full: frames of the asw_stereo_match_batch leg over all --gpus devices (C5: 64); 0 skips it")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: CPU time budget of the CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--backend", default="nccl", help="process-group backend for N>1 (nccl = RCCL; gloo for rehearsals: implied by --dry-run and --oversubscribe)")
     ap.add_argument("--oversubscribe", action="store_true",
                     help="rehearsal only: allow more ranks than visible GPUs (ranks wrap over the devices)")
@@ -189,6 +206,9 @@ class DryEngine:
         self.sums[i] = int(np.abs(L.astype(np.int32) - R.astype(np.int32)).sum())
         return {"aggregate_ms": 0.0, "total_ms": 0.0, "aggregate_launches": 0}
 
+    def outputs(self):
+        return {"checksum": np.array([self.sums[i] for i in sorted(self.sums)], np.float64)}
+
     def synchronize(self):
         pass
 
@@ -196,11 +216,29 @@ class DryEngine:
         pass
 
 
+def dump_outputs(directory, arrays, budget_bytes, suffix=""):
+    """Write each array as DIR/<name><suffix>.npy; an array over its equal share of budget_bytes becomes a seeded sample."""
+    os.makedirs(directory, exist_ok=True)
+    share = budget_bytes // max(1, len(arrays))
+    for name, a in sorted(arrays.items()):
+        n = share // a.itemsize
+        if a.size > n:
+            what = "a seeded sample of %d of the %d values of shape %s" % (n, a.size, a.shape)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, n, replace=False))]
+        else:
+            what = "shape %s" % (a.shape,)
+        path = os.path.join(directory, name + suffix + ".npy")
+        np.save(path, a)
+        sys.stderr.write("bench.py: wrote %s (%s, %s)\n" % (path, a.dtype, what))
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     args = parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args, argv))  # parent: spawn the ranks, touch nothing else
 
@@ -252,6 +290,12 @@ def main(argv=None):
             def match(self, i):
                 ctx.match_resident(i, asw.DISPARITY_LEFT, alg, args.win, 0, D, keep_volume=True)
                 return ctx.timing()
+
+            def outputs(self):
+                last = args.frames - 1
+                planes = ctx._lib.asw_volume_planes(alg, D)
+                return {"disparity": np.stack([ctx.download_disparity(i, (H, W)) for i in range(args.frames)]),
+                        "cost_volume_last_frame": ctx.download_volume(last, (planes, H, W))}
 
             def synchronize(self):
                 torch.cuda.synchronize()
@@ -369,13 +413,15 @@ def main(argv=None):
     # together.  Ranks other than 0 are finished and free their device; rank 0 goes on alone with the legs that are not part of
     # `value` -- no collective is pending, so nothing of RCCL can spin on a device meanwhile.
     group.close()
+    if args.dump_outputs:  # every rank, before any secondary leg touches the context
+        dump_outputs(args.dump_outputs, eng.outputs(), DUMP_BYTES // world, "_rank%d" % rank if world > 1 else "")
     if rank != 0:
         eng.close()
         return
 
-    # ---- second leg, rank 0 only, after the timed region: the product's own multi-GPU API.  asw_stereo_match_batch shards
-    # --batch-frames frames (host buffers in and out) over ALL --gpus devices from ONE process.
-    if not args.dry_run and args.batch_frames > 0:
+    # ---- second leg (--full), rank 0 only, after the timed region: the product's own multi-GPU API.  asw_stereo_match_batch
+    # shards --batch-frames frames (host buffers in and out) over ALL --gpus devices from ONE process.
+    if args.full and not args.dry_run and args.batch_frames > 0:
         if rank == 0:
             import aswstereomatch_amd as asw
 
@@ -401,7 +447,7 @@ def main(argv=None):
                 out["batch_api"] = {"api": "asw_stereo_match_batch", "error": "%s: %s" % (type(e).__name__, e)}
 
     if rank == 0 and not args.dry_run:
-        if world == 1:
+        if args.full and world == 1:
             # the same method through the one-call host-buffer entry point (asw_stereo_match: H2D of both images, kernels,
             # D2H of the disparity) -- the PCIe-inclusive rate of sequential calls; never the headline value
             L, R = frames[0]

@@ -6,6 +6,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 SMALL = ["--dry-run", "--backend", "gloo", "--width", "96", "--height", "64", "--disp", "8", "--frames", "3", "--steps", "2",
@@ -85,11 +88,66 @@ def test_a_failing_rank_aborts_the_job():
 
 
 def test_without_a_gpu_the_real_bench_refuses():
-    # the product path has no CPU fallback: on this GPU-less host the non-dry run must exit with a message, not a number
-    import torch
-
-    if torch.cuda.is_available():
+    # the product path has no CPU fallback: on this GPU-less host the non-dry run must exit with a message, not a number.
+    # Asked in a child process: torch brings its own copy of the HIP runtime, and once the library's copy is loaded here
+    # (tests/test_abi_cpu.py), starting a second one in this process leaves the library without a device for the GPU tests.
+    probe = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.is_available())"], env=_clean_env(),
+                           capture_output=True, text=True, timeout=300)
+    assert probe.returncode == 0, probe.stderr[-2000:]
+    if probe.stdout.strip().splitlines()[-1] == "True":
         return
     r = subprocess.run([sys.executable, BENCH, "--steps", "1", "--warmup", "0"], env=_clean_env(), capture_output=True, text=True,
                        timeout=300)
     assert r.returncode != 0 and "needs a GPU" in r.stderr and "{" not in r.stdout
+
+
+def test_dump_outputs_are_the_same_from_run_to_run(tmp_path):
+    sums = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, BENCH, "--dump-outputs", str(tmp_path / d)] + SMALL, env=_clean_env(), capture_output=True,
+                           text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        _json_line(r.stdout)
+        assert sorted(os.listdir(tmp_path / d)) == ["checksum.npy"]
+        sums.append(np.load(tmp_path / d / "checksum.npy"))
+    assert sums[0].dtype == np.float64 and sums[0].shape == (3,) and np.array_equal(sums[0], sums[1])
+
+
+def test_dump_outputs_samples_an_array_over_its_share(tmp_path):
+    import bench
+
+    big = np.arange(1000, dtype=np.float32)
+    small = np.ones((2, 3), np.float64)
+    bench.dump_outputs(str(tmp_path), {"big": big, "small": small}, 2000, "_rank1")
+    got = np.load(tmp_path / "big_rank1.npy")
+    assert got.dtype == np.float32 and got.size == 1000 // 4 and np.all(np.diff(got) > 0)  # 1000 bytes: a sorted seeded sample
+    assert np.array_equal(got, big[got.astype(np.int64)])
+    bench.dump_outputs(str(tmp_path / "again"), {"big": big}, 1000)
+    assert np.array_equal(np.load(tmp_path / "again" / "big.npy"), got)
+    assert np.array_equal(np.load(tmp_path / "small_rank1.npy"), small)
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_what_the_resident_path_computed(tmp_path):
+    import aswstereomatch_amd as asw
+    from aswstereomatch_amd.synth import make_pair
+
+    args = ["--width", "96", "--height", "64", "--disp", "8", "--frames", "2", "--steps", "2", "--warmup", "1"]
+    r = subprocess.run([sys.executable, BENCH, "--dump-outputs", str(tmp_path)] + args, env=_clean_env(), capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = _json_line(r.stdout)
+    assert out["steps"] == 2 and out["ms_per_step"] > 0 and "cpu_baseline" not in out and "batch_api" not in out
+    disp = np.load(tmp_path / "disparity.npy")
+    vol = np.load(tmp_path / "cost_volume_last_frame.npy")
+    assert disp.dtype == vol.dtype == np.float32 and disp.shape == (2, 64, 96) and vol.shape == (9, 64, 96)
+    ctx = asw.Context(0)
+    try:
+        for i in range(2):
+            L, R, _ = make_pair(64, 96, 8, seed=1234 + i)
+            want, wvol = ctx.stereoMatching(L, R, asw.DISPARITY_LEFT, asw.StereoMatchingAlgorithms.ADAPTIVE_WEIGHT, 15, 0, 8,
+                                            return_cost_volume=True)
+            assert np.array_equal(disp[i], want)
+        assert np.array_equal(vol, wvol, equal_nan=True)
+    finally:
+        ctx.close()

@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp
 
 bench() {  # name, extra args...
     local name=$1; shift
-    python3 "$ROOT/bench.py" "$@" > "$OUT/final_bench_$name.json" 2> "$OUT/final_bench_$name.err"
+    python3 "$ROOT/bench.py" --full "$@" > "$OUT/final_bench_$name.json" 2> "$OUT/final_bench_$name.err"
     echo "bench $name: $(cut -c1-160 "$OUT/final_bench_$name.json")"
 }
 stats() {  # name, program args...
@@ -42,7 +42,7 @@ bench ncc --workload ncc --frames 4 --steps 3
 bench bilgrid --workload bilgrid --frames 2 --steps 2
 
 # the rocprofv3 summary of the SAME command as the headline bench line (CPU baseline skipped: it is host-only work)
-stats bilateral_bench "$ROOT/bench.py" --no-cpu
+stats bilateral_bench "$ROOT/bench.py" --full --no-cpu
 stats alg8 "$ROOT/tools/run_one.py" --alg 8 --reps 3
 stats alg7 "$ROOT/tools/run_one.py" --alg 7 --reps 3
 stats alg4 "$ROOT/tools/run_one.py" --alg 4 $KITTI --reps 3

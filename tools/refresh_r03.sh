@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 hostname > "$OUT/box.txt" 2>/dev/null || true
 KITTI="--width 1242 --height 375 --disp 192"
-bench() { local name=$1; shift; python3 "$ROOT/bench.py" "$@" > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err"; echo "bench $name: $(cut -c1-150 "$OUT/bench_$name.json")"; }
+bench() { local name=$1; shift; python3 "$ROOT/bench.py" --full "$@" > "$OUT/bench_$name.json" 2> "$OUT/bench_$name.err"; echo "bench $name: $(cut -c1-150 "$OUT/bench_$name.json")"; }
 stats() { local name=$1; shift; rocprofv3 --kernel-trace --stats -d "/tmp/st_$name" -o p --output-format csv -- python3 "$@" > "$OUT/prof_$name.log" 2>&1; cp "/tmp/st_$name/p_kernel_stats.csv" "$OUT/${name}_kernel_stats.csv"; echo "stats $name done"; }
 pmc() { local name=$1; local ctr=$2; shift 2; rocprofv3 --kernel-trace --pmc $ctr -d "/tmp/pm_$name" -o p --output-format csv -- python3 "$@" > "$OUT/pmc_$name.log" 2>&1; cp "/tmp/pm_$name/p_counter_collection.csv" "$OUT/pmc_$name.csv"; echo "pmc $name done"; }
 SQ="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_ACTIVE_INST_LDS SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT"
@@ -24,7 +24,7 @@ bench)
   bench wmedian --workload wmedian $KITTI --frames 4 --steps 3
   ;;
 stats)
-  stats bilateral_bench "$ROOT/bench.py" --no-cpu --batch-frames 0
+  stats bilateral_bench "$ROOT/bench.py" --full --no-cpu --batch-frames 0
   stats alg8 "$ROOT/tools/run_one.py" --alg 8 --reps 3
   stats alg7 "$ROOT/tools/run_one.py" --alg 7 --reps 3
   stats alg4 "$ROOT/tools/run_one.py" --alg 4 $KITTI --reps 4
