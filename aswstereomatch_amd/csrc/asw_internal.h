@@ -54,6 +54,8 @@ struct BilateralTables {  // cached per (kind, win, gamma_c, gamma_g, mirror)
     DevBuf taps;  // int4 per tap
     DevBuf lut;   // float [ncls][256]
     DevBuf cells; // kind 0, win 15, not mirrored: int4 per window cell (kx = -3..17, ky = 0..14) for k_asw_bilateral_xq
+    DevBuf lut_xq;        // kind 0, win 15: the LUT x 2^60 -- k_asw_bilateral_xq accumulates in its scaled domain
+    bool xq_lut_ok = false;  // the LUT admits that domain (bilateral_xq_lut_ok); else the one-kernel form runs
 };
 
 // Measurement / test switches, read from the environment ONCE when a context is created (asw_create): a call never looks at
@@ -128,6 +130,10 @@ struct BilateralLaunch {
 // problem with at least that many candidates; writes the running minimum to bestE / bestD for the tail launch, or -- when
 // there is no tail (disp != nullptr) -- the disparity itself
 int bilateral_xq_candidates(int nwave);  // nwave = 8 / 4 wavefronts per workgroup: 128 / 64 candidates
+// The xq kernel takes the LUT scaled by 2^XQ_LUT_SCALE_LOG2; its sums are bit-identical to the reference's only when every
+// nonzero weight product is >= 2^-68 and the scaled products stay finite: checked on the (unscaled) LUT.
+constexpr int XQ_LUT_SCALE_LOG2 = 60;
+bool bilateral_xq_lut_ok(const float* lut, size_t n);
 int launch_bilateral_xq(hipStream_t s, hipStream_t s_border, int nwave, const uint8_t* gL, const uint8_t* gR, int H, int W, int minD,
                         const int4* cells, const float* lut, float* vol, double* bestE, float* bestD, float* disp, bool right = false);
 int launch_bilateral(hipStream_t s, const BilateralLaunch& a);

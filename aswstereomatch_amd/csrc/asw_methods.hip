@@ -94,9 +94,18 @@ static int ensure_bilateral_tables(asw_ctx* ctx, int kind, int win, double gamma
     if (!taps.empty())  // win = 1 has no taps at all (every E is 0/0)
         ASW_HIP_TRY(hipMemcpyAsync(t.taps.p, taps.data(), taps.size() * sizeof(int4), hipMemcpyHostToDevice, ctx->stream));
     ASW_HIP_TRY(hipMemcpyAsync(t.lut.p, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    std::vector<float> lut_xq;
+    t.xq_lut_ok = false;
     if (!cells.empty()) {
         ASW_TRY(t.cells.ensure(cells.size() * sizeof(int4)));
         ASW_HIP_TRY(hipMemcpyAsync(t.cells.p, cells.data(), cells.size() * sizeof(int4), hipMemcpyHostToDevice, ctx->stream));
+        t.xq_lut_ok = bilateral_xq_lut_ok(lut.data(), lut.size());
+        if (t.xq_lut_ok) {  // a power-of-two scale: exact for every entry (none overflows, none is lost)
+            lut_xq.resize(lut.size());
+            for (size_t i = 0; i < lut.size(); i++) lut_xq[i] = ldexpf(lut[i], XQ_LUT_SCALE_LOG2);
+            ASW_TRY(t.lut_xq.ensure(lut_xq.size() * sizeof(float)));
+            ASW_HIP_TRY(hipMemcpyAsync(t.lut_xq.p, lut_xq.data(), lut_xq.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        }
     }
     ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));  // host vectors die at return
     t.kind = kind; t.win = win; t.gamma_c = gamma_c; t.gamma_g = gamma_g; t.mirror = mirror; t.ntaps = nt_pad;
@@ -147,11 +156,13 @@ static int run_bilateral(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool kee
     // kernel for the first 128 (8 wavefronts per workgroup) or 64 (4 wavefronts: the reference's own call site passes
     // numDisparity 64 -> 65 candidates, aswStereoMatch.cpp:94) and this kernel for the tail.  The tile of the outermost workgroup must still hold the eight image
     // columns next to the border its positions clamp to: LEFT minD <= 48 (columns 0..7 in the first tile), RIGHT
-    // x0_last + minD <= W - 1 (columns W-8..W-1 in the last).  ASW_BILATERAL_XQ=0 forces the one-kernel path (A/B, tests).
+    // x0_last + minD <= W - 1 (columns W-8..W-1 in the last).  The xq form sums in a scaled domain that is exact only for LUTs
+    // whose nonzero weight products are >= 2^-68 (bilateral_xq_lut_ok: every gamma_c above about 10); other gammas take the
+    // one-kernel form.  ASW_BILATERAL_XQ=0 forces the one-kernel path (A/B, tests).
     const bool xq_fits = flip ? (W - 1) / 64 * 64 + mp.minD <= W - 1 : mp.minD <= 48;
     const int xq_waves = nD >= bilateral_xq_candidates(8) ? 8 : 4;
     const bool use_xq = !direct8 && mp.win == 15 && nD >= bilateral_xq_candidates(xq_waves) && mp.minD >= 0 && xq_fits && W >= 64 &&
-                        ctx->tune.bilateral_xq != 0;
+                        ctx->bil.xq_lut_ok && ctx->tune.bilateral_xq != 0;
     if (use_xq) {
         DevBuf& pe = ctx->buf("bil_partE");
         DevBuf& pd = ctx->buf("bil_partD");
@@ -166,7 +177,7 @@ static int run_bilateral(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool kee
         // per-slice winners); on side streams they overlap it instead of adding two latency-bound 0.5 ms launches to the frame
         ASW_HIP_TRY(hipEventRecord(ctx->aux_ev[0], ctx->stream));
         ASW_HIP_TRY(hipStreamWaitEvent(ctx->aux[0], ctx->aux_ev[0], 0));
-        ASW_TRY(launch_bilateral_xq(ctx->stream, ctx->aux[0], xq_waves, a.gL, a.gR, H, W, mp.minD, ctx->bil.cells.as<int4>(), a.lut, a.vol,
+        ASW_TRY(launch_bilateral_xq(ctx->stream, ctx->aux[0], xq_waves, a.gL, a.gR, H, W, mp.minD, ctx->bil.cells.as<int4>(), ctx->bil.lut_xq.as<float>(), a.vol,
                                     a.partE, a.partD, tail ? nullptr : a.disp, flip != 0));
         ASW_HIP_TRY(hipEventRecord(ctx->aux_ev[1], ctx->aux[0]));
         if (tail) {

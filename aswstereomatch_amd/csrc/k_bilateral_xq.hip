@@ -12,9 +12,20 @@
 //       (x+1, q+1) -- same d, next pixel -- needs one tap column earlier.
 // A thread owns pixels X..X+3 and positions Q..Q+3 (16 units, d = X+a - (Q+b)); unit (a,b) runs b tap columns behind the
 // thread's step counter K (kx = K - b), so all units on a diagonal a-b (one d, up to four pixels) consume ONE cost value per
-// step: 7 f64 subtractions per 16 units, and nothing is converted from bytes in the inner loop.  Every unit still adds its own
-// taps in ascending i, in f64, with the exact product -- E is bit-identical to the reference order (fma(ab,c,num) == num + ab*c
-// because ab*c is exact: 24-bit x 8-bit significands).
+// step: 7 integer instructions per 16 units.  Every unit still adds its own taps in ascending i, in f64, with the exact
+// product -- E is bit-identical to the reference order (fma(ab,c,num) == num + ab*c because ab*c is exact: 24-bit x 8-bit
+// significands).
+//
+// Scaled domain.  The cost sample |gL - gR| in 0..255 is produced by one v_sad into the low word of a register pair whose
+// high word is zero: as an f64 that pair is the denormal c * 2^-1074 (the kernel preserves f64 denormals), so no f64
+// subtraction or conversion is needed.  The weights are staged from a LUT scaled by 2^60 (exact in f32), so that the f32
+// product is ab' = ab * 2^120 and
+//     den' = sum ab'                      = den * 2^120                 exactly,
+//     num' = sum fma(ab', c * 2^-1074)     = num * 2^-954                exactly,
+// E = ldexp(num', 954) / ldexp(den', -120) is then the same IEEE quotient num / den as in the reference.  This holds when every
+// nonzero product ab >= 2^-68: the f32 products stay normal in both domains, every nonzero ab * c * 2^-954 is >= 2^-1022, so
+// every partial sum of num' is normal (or zero) and rounds as num does, only 954 binades lower.  The host checks the bound on the
+// LUT (bilateral_xq_lut_ok) and takes the one-kernel form where it does not hold.
 //
 // Workgroup = one image row x 64 pixels x 32 position blocks (d = minD + 4j + a - b, j < 32): 8 wavefronts, lane -> (pixel
 // group g, position block 4*wave + ((lane >> 3) & 3)); the lane -> g map is chosen for the LDS banks, see the kernel.  All 512
@@ -23,7 +34,7 @@
 //     right: wR(q, tap column K-b)  for the 188 positions    -> b = (q - Q) mod 4 is a property of the position, so the buffer of
 //            step K holds, per position, exactly the tap column that position's units consume at step K (double buffered)
 // i.e. 7.5 weight evaluations per thread and step instead of 33 with wave-private staging, one workgroup barrier per step
-// (18 steps of 15 rows), no cost tile, gray tiles as f64 in LDS.
+// (18 steps of 15 rows), no cost tile, gray tiles as u32 in LDS.
 // Block j = 0 holds six units with d < minD (a < b) and a block j = 32 would hold exactly six units with c = d - minD < 128
 // in the same slots (c = 128 + a - b): the j = 0 threads run those instead ("wrapped" units: second position base qrel2,
 // second right gray), so the 512 threads finish candidates [0, 128) with no idle unit.  The tail [128, nD) -- one candidate
@@ -38,7 +49,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
-#include <type_traits>
+#include <cmath>
 
 #include "asw_internal.h"
 
@@ -52,6 +63,7 @@ constexpr int NSTEP = KS + 3;             // 18 steps: unit row b runs b tap col
 constexpr int RING = 5;                   // tap columns of left weights kept (4 in use + the one being staged)
 constexpr int NCELLCOL = NSTEP + 3;       // cell-table columns kx = -3 .. 17
 constexpr int LW8 = 80;                   // u8 row stride of the left tile (multiple of 4)
+constexpr int LWP = 80;                   // u32 row stride of the left gray tile (multiple of 4 >= LWC)
 
 // Everything that depends on the number of wavefronts NW of a workgroup (8: 128 candidates per pass -- the reference's
 // configuration at 1080p; 4: 64 candidates -- its own call site, aswStereoMatch.cpp:94, numDisparity 64 -> 65 candidates):
@@ -59,10 +71,12 @@ constexpr int LW8 = 80;                   // u8 row stride of the left tile (mul
 //   NPOS  right-image positions a workgroup touches: [posmin, posmin + NPOS - 1]
 //   RWC   right tile columns [posmin - 7, posmin + NPOS + 6]
 //   NFIN  candidates [0, NFIN) are finished by the kernel
-// LDS layout (bytes): double [KS][LWC] left gray | double [KS][RWC] right gray | float [RING][KS][PXW] left weights |
-// float [2][KS][NPOS] right weights | u8 [KS][LW8] | u8 [KS][RW8] | u16 [NCELLCOL * KS] packed cell table.
+// LDS layout (bytes): left block [KS] x {float [RING][PXW] left weights, u32 [LWP] left gray} | right block [KS] x {float [2][NPOS]
+// right weights, u32 [RWP] right gray} | u8 [KS][LW8] | u8 [KS][RW8] | u16 [NCELLCOL * KS] packed cell table.  Weights and
+// grays of a window row share one row stride per side, so that every LDS address of the row loop is one of two per-lane bases
+// (three in wave 0) plus an immediate offset: two address increments per row instead of six.
 // Epilogue (over the dead tiles): double [NFIN][PXW] E | per-part WTA partials double E[NW][PXW], float d[NW][PXW].
-// NW = 8: 81 280 B, two workgroups = 16 wavefronts per CU; NW = 4: 52 KB (f32 gray tiles), three workgroups = 12 wavefronts per CU.
+// NW = 8: 70 KB (the epilogue's), two workgroups = 16 wavefronts per CU; NW = 4: 52 KB, three workgroups = 12 wavefronts per CU.
 template <int NW>
 struct XqCfg {
     static constexpr int NWAVE = NW;
@@ -73,39 +87,48 @@ struct XqCfg {
     static constexpr int NFIN = 4 * NJ;
     static constexpr int RW8 = (RWC + 3) / 4 * 4;
     static constexpr int NROWS = (KS + NW - 1) / NW;  // window rows a wavefront stages
-    // Gray tiles for the cost samples: f64 (NW = 8: nothing is converted in the row loop), f32 for NW = 4 -- 13 KB less, 52 KB in
-    // all, so that THREE workgroups (12 wavefronts) fit a CU instead of two, for 7 v_cvt_f64_f32 per row step (the differences of
-    // two gray bytes are exact in f32)
-    static constexpr int GB = NW == 8 ? 8 : 4;
-    static constexpr int OFF_LD = 0;
-    static constexpr int OFF_RD = (OFF_LD + KS * LWC * GB + 15) / 16 * 16;
-    static constexpr int OFF_WL = (OFF_RD + KS * RWC * GB + 15) / 16 * 16;
-    static constexpr int OFF_WR = OFF_WL + RING * KS * PXW * 4;
-    static constexpr int OFF_L8 = OFF_WR + 2 * KS * NPOS * 4;
+    // Gray tiles for the cost samples: u32, the operands of v_sad (the left rows padded to a multiple of four words, so that the
+    // grays of a step are read as 16-byte aligned quads)
+    static constexpr int RWP = (RWC + 3) / 4 * 4;
+    static constexpr int LROW = RING * PXW + LWP;  // words per window row, left block
+    static constexpr int RROW = 2 * NPOS + RWP;    // words per window row, right block
+    static constexpr int LGRAY = RING * PXW;       // left gray, word offset in a row
+    static constexpr int RGRAY = 2 * NPOS;         // right gray, word offset in a row
+    static constexpr int OFF_LB = 0;
+    static constexpr int OFF_RB = OFF_LB + KS * LROW * 4;
+    static constexpr int OFF_L8 = OFF_RB + KS * RROW * 4;
     static constexpr int OFF_R8 = OFF_L8 + KS * LW8;
     static constexpr int OFF_CELL = OFF_R8 + KS * RW8;
-    static constexpr int LDS_TOTAL = (OFF_CELL + NCELLCOL * KS * 2 + 15) / 16 * 16;
     static constexpr int OFF_E64 = 0;
     static constexpr int OFF_PART = NFIN * PXW * 8;
-    typedef typename std::conditional<NW == 8, double, float>::type GrayT;
+    // the epilogue buffers reuse the dead tiles; for NW = 8 they are the larger of the two
+    static constexpr int LDS_TOTAL = std::max((OFF_CELL + NCELLCOL * KS * 2 + 15) / 16 * 16, OFF_PART + NW * PXW * 12);
     static_assert(LDS_TOTAL <= (NW == 8 ? 80 : 53) * 1024, "two (NW = 8) / three (NW = 4) workgroups per CU");
-    static_assert(OFF_PART + NW * PXW * 12 <= LDS_TOTAL, "epilogue buffers fit in the dead tiles");
-    static_assert(OFF_RD % 16 == 0 && OFF_WL % 16 == 0 && OFF_WR % 16 == 0 && (KS * NPOS * 4) % 16 == 0 && (NPOS * 4) % 16 == 0, "b128 alignment");
+    static_assert(OFF_RB % 16 == 0 && (LROW * 4) % 16 == 0 && (RROW * 4) % 16 == 0 && (NPOS * 4) % 16 == 0 && (LGRAY * 4) % 16 == 0, "b128 alignment");
     static_assert(NPOS % 64 == 0, "positions are staged in whole wavefront passes");
 };
 #define XQ_CONSTS(NW)                                                                                                           \
     typedef XqCfg<NW> Cfg;                                                                                                       \
     constexpr int NWAVE = Cfg::NWAVE, NTHR = Cfg::NTHR, NJ = Cfg::NJ, NPOS = Cfg::NPOS, RWC = Cfg::RWC, NFIN = Cfg::NFIN, RW8 = Cfg::RW8,      \
-                  NROWS = Cfg::NROWS, OFF_LD = Cfg::OFF_LD, OFF_RD = Cfg::OFF_RD, OFF_WL = Cfg::OFF_WL, OFF_WR = Cfg::OFF_WR,    \
-                  OFF_L8 = Cfg::OFF_L8, OFF_R8 = Cfg::OFF_R8, OFF_CELL = Cfg::OFF_CELL, LDS_TOTAL = Cfg::LDS_TOTAL,              \
-                  OFF_E64 = Cfg::OFF_E64, OFF_PART = Cfg::OFF_PART;                                                              \
-    (void)NWAVE; (void)NTHR; (void)NJ; (void)NPOS; (void)RWC; (void)NFIN; (void)RW8; (void)NROWS; (void)OFF_LD; (void)OFF_RD; (void)OFF_WL; \
-    (void)OFF_WR; (void)OFF_L8; (void)OFF_R8; (void)OFF_CELL; (void)LDS_TOTAL; (void)OFF_E64; (void)OFF_PART;
+                  NROWS = Cfg::NROWS, LROW = Cfg::LROW, RROW = Cfg::RROW, LGRAY = Cfg::LGRAY, RGRAY = Cfg::RGRAY,               \
+                  OFF_LB = Cfg::OFF_LB, OFF_RB = Cfg::OFF_RB, OFF_L8 = Cfg::OFF_L8, OFF_R8 = Cfg::OFF_R8, OFF_CELL = Cfg::OFF_CELL,  \
+                  LDS_TOTAL = Cfg::LDS_TOTAL, OFF_E64 = Cfg::OFF_E64, OFF_PART = Cfg::OFF_PART;                                  \
+    (void)NWAVE; (void)NTHR; (void)NJ; (void)NPOS; (void)RWC; (void)NFIN; (void)RW8; (void)NROWS; (void)LROW; (void)RROW; (void)LGRAY;  \
+    (void)RGRAY; (void)OFF_LB; (void)OFF_RB; (void)OFF_L8; (void)OFF_R8; (void)OFF_CELL; (void)LDS_TOTAL; (void)OFF_E64; (void)OFF_PART;
 
 struct XqParams {
     int H, W, minD;
     int tile0;  // first 64-pixel tile of this launch (interior tiles and border tiles are separate launches)
 };
+
+// The cost sample of the scaled domain: |gl - gr| (both in 0..255) in the low word of a pair whose high word is zero, i.e. the
+// f64 denormal |gl - gr| * 2^-1074.  The zero high word is an opaque register (hi0, set once per step outside the row loop)
+// so that the compiler keeps it in place instead of rematerialising a v_mov per sample in the loop.
+__device__ __forceinline__ double cost_sample(uint32_t gl, uint32_t gr, uint32_t hi0)
+{
+    const uint32_t c = __builtin_amdgcn_sad_u16(gl, gr, 0u);  // the high halves are zero: |gl - gr|
+    return __builtin_bit_cast(double, (uint64_t)c | ((uint64_t)hi0 << 32));
+}
 
 __device__ __forceinline__ float lut_at(const float* __restrict__ lut, unsigned idx)
 {
@@ -169,15 +192,15 @@ template <int NW>
 __device__ __forceinline__ void stage_commit(int Kn, unsigned char* smem, int wave, int lane, const Staged<NW>& st)
 {
     XQ_CONSTS(NW)
-    float* sWL = reinterpret_cast<float*>(smem + OFF_WL) + (Kn % RING) * (KS * PXW);
-    float* sWR = reinterpret_cast<float*>(smem + OFF_WR) + (Kn & 1) * (KS * NPOS);
+    float* sWL = reinterpret_cast<float*>(smem + OFF_LB) + (Kn % RING) * PXW;
+    float* sWR = reinterpret_cast<float*>(smem + OFF_RB) + (Kn & 1) * NPOS;
 #pragma unroll
     for (int rr = 0; rr < NROWS; rr++) {
         const int ky = wave + NWAVE * rr;
         if (ky >= KS) break;
-        if (Kn < KS) sWL[ky * PXW + lane] = st.v[rr][0];
+        if (Kn < KS) sWL[ky * LROW + lane] = st.v[rr][0];
 #pragma unroll
-        for (int r3 = 0; r3 < NPOS / 64; r3++) sWR[ky * NPOS + lane + 64 * r3] = st.v[rr][1 + r3];
+        for (int r3 = 0; r3 < NPOS / 64; r3++) sWR[ky * RROW + lane + 64 * r3] = st.v[rr][1 + r3];
     }
 }
 
@@ -206,11 +229,8 @@ __device__ __forceinline__ void run_step(unsigned char* smem, int g, int qrel, i
     constexpr int BLO = K > KS - 1 ? K - (KS - 1) : 0;  // kx = K - b <= 14
     constexpr int BHI = K < 3 ? K : 3;                  // kx = K - b >= 0
     constexpr int DLO = 0 - BHI, DHI = 3 - BLO;         // diagonals a - b in use
-    typedef typename Cfg::GrayT GrayT;
-    const GrayT* sLd = reinterpret_cast<const GrayT*>(smem + OFF_LD);
-    const GrayT* sRd = reinterpret_cast<const GrayT*>(smem + OFF_RD);
-    const float* sWL = reinterpret_cast<const float*>(smem + OFF_WL);
-    const float* sWR = reinterpret_cast<const float*>(smem + OFF_WR) + (K & 1) * (KS * NPOS);
+    const uint32_t* sLd = reinterpret_cast<const uint32_t*>(smem + OFF_LB) + LGRAY;  // + ky * LROW
+    const uint32_t* sRd = reinterpret_cast<const uint32_t*>(smem + OFF_RB) + RGRAY;  // + ky * RROW
 
     int iL[7], iR[7];
     if constexpr (EDGE) {
@@ -224,55 +244,74 @@ __device__ __forceinline__ void run_step(unsigned char* smem, int g, int qrel, i
             iR[dl + 3] = min(max(rc - (posmin - HH), 0), RWC - 1);
         }
     }
-    const GrayT* pl = sLd + 4 * g + K;   // + dl: tile column of x + dl + K - 7
-    const GrayT* pr = sRd + qrel + K;    // tile column of Q + K - 7
-    const GrayT* pr2 = sRd + qrel2 + K;
-    const float* pwl = sWL + 4 * g;
-    const float* pwr = sWR + qrel;
-    const float* pwr2 = sWR + qrel2;
+    // the row loop's LDS addresses: three per-lane bases (left block, right block, wrapped right block) that advance by one row
+    // per iteration; everything else is an immediate offset.  The empty asm hides the bases' relation from the loop
+    // optimiser, which otherwise rebuilds them from an SGPR row counter with one more add per row.
+    typedef __attribute__((address_space(3))) const unsigned char lds_u8;
+    lds_u8* bL = (lds_u8*)smem + OFF_LB + 16 * g;
+    lds_u8* bR = (lds_u8*)smem + OFF_RB + 4 * qrel;
+    lds_u8* bR2 = (lds_u8*)smem + OFF_RB + 4 * qrel2;
+    uint32_t hi0[7];
+#pragma unroll
+    for (int i = 0; i < 7; i++) asm volatile("v_mov_b32 %0, 0" : "=v"(hi0[i]));  // seven distinct registers the compiler cannot fold
 #pragma unroll 1
     for (int ky = 0; ky < KS; ky++) {
         if constexpr (COMMIT) {
             if (ky == KS / 2) stage_commit<NW>(K + 1, smem, wave, lane, st);  // the gathers issued before this loop have landed
         }
-        double c[7];
+        double c[7];  // cost samples of the diagonals, scaled domain: |gL - gR| * 2^-1074
         if constexpr (!EDGE) {
-            const GrayT gr = pr[ky * RWC];
-            GrayT gr2 = gr;
-            if constexpr (WRAPW && (RIGHT ? DHI > 0 : DLO < 0)) gr2 = pr2[ky * RWC];
-            // the left grays of the step, read as 16-byte aligned pairs from an even tile column (4g, LWC and E0 are even): a
-            // run that starts on an odd column is split by the compiler into ds_read2_b64, which cost four times the LDS cycles
-            // of ds_read_b128 here (8 instead of 4, and 2-way conflicts: their banks are taken mod 32)
-            constexpr int E0 = (K + DLO) & ~1, NP2 = (K + DHI - E0 + 2) / 2;
-            typedef GrayT gx2 __attribute__((ext_vector_type(2)));
-            const gx2* pl2 = reinterpret_cast<const gx2*>(sLd + 4 * g + E0 + ky * LWC);
-            GrayT glv[2 * NP2];
+            const uint32_t gr = *(const __attribute__((address_space(3))) uint32_t*)(bR + 4 * (RGRAY + K));  // tile column of Q + K - 7
+            uint32_t gr2 = gr;
+            if constexpr (WRAPW && (RIGHT ? DHI > 0 : DLO < 0)) gr2 = *(const __attribute__((address_space(3))) uint32_t*)(bR2 + 4 * (RGRAY + K));
+            // the left grays of the step, read as 16-byte aligned quads from a tile column that is a multiple of four (4g, LWP
+            // and E0 are): a run the compiler cannot prove aligned is split into narrower reads (ds_read2_*), which cost
+            // several times the LDS cycles of ds_read_b128
+            constexpr int E0 = (K + DLO) & ~3, NQ = (K + DHI - E0 + 4) / 4;
+            static_assert(E0 >= 0 && E0 + 4 * NQ + 4 * 15 <= LWP, "the quads stay inside a tile row");
+            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+            const __attribute__((address_space(3))) u32x4* pl4 = (const __attribute__((address_space(3))) u32x4*)(bL + 4 * (LGRAY + E0));
+            uint32_t glv[4 * NQ];
 #pragma unroll
-            for (int i = 0; i < NP2; i++) { const gx2 t = pl2[i]; glv[2 * i] = t.x; glv[2 * i + 1] = t.y; }
+            for (int i = 0; i < NQ; i++) {
+                u32x4 t = pl4[i];
+                asm("" : "+v"(t));  // all four words in use: otherwise the compiler narrows a quad whose first word no diagonal
+                                    // needs into a misaligned 12-byte read and splits that into ds_read2_b32 + ds_read_b32
+                glv[4 * i] = t.x; glv[4 * i + 1] = t.y; glv[4 * i + 2] = t.z; glv[4 * i + 3] = t.w;
+            }
 #pragma unroll
-            for (int dl = DLO; dl <= DHI; dl++) c[dl + 3] = (double)(glv[K + dl - E0] - ((RIGHT ? dl > 0 : dl < 0) ? gr2 : gr));  // exact in f32 too
+            for (int dl = DLO; dl <= DHI; dl++) c[dl + 3] = cost_sample(glv[K + dl - E0], (RIGHT ? dl > 0 : dl < 0) ? gr2 : gr, hi0[dl + 3]);
         } else {
 #pragma unroll
-            for (int dl = DLO; dl <= DHI; dl++) c[dl + 3] = (double)(sLd[ky * LWC + iL[dl + 3]] - sRd[ky * RWC + iR[dl + 3]]);
+            for (int dl = DLO; dl <= DHI; dl++) c[dl + 3] = cost_sample(sLd[ky * LROW + iL[dl + 3]], sRd[ky * RROW + iR[dl + 3]], hi0[dl + 3]);
         }
-        const float4 wr4 = *reinterpret_cast<const float4*>(pwr + ky * NPOS);
+        typedef float f32x4 __attribute__((ext_vector_type(4)));
+        typedef __attribute__((address_space(3))) const f32x4 lds_f32x4;
+        const f32x4 wr4 = *(lds_f32x4*)(bR + 4 * (K & 1) * NPOS);
         const float wr[4] = {wr4.x, wr4.y, wr4.z, wr4.w};
         float wr2[4] = {wr4.x, wr4.y, wr4.z, wr4.w};
         if constexpr ((WRAPW || EDGE) && (RIGHT ? BLO <= 2 : BHI >= 1)) {  // some active unit is a wrapped one
-            const float4 w2 = *reinterpret_cast<const float4*>(pwr2 + ky * NPOS);
+            const f32x4 w2 = *(lds_f32x4*)(bR2 + 4 * (K & 1) * NPOS);
             wr2[0] = w2.x; wr2[1] = w2.y; wr2[2] = w2.z; wr2[3] = w2.w;
         }
 #pragma unroll
         for (int b = BLO; b <= BHI; b++) {
-            const float4 wl4 = *reinterpret_cast<const float4*>(pwl + (((K - b) % RING) * KS + ky) * PXW);
+            const f32x4 wl4 = *(lds_f32x4*)(bL + 4 * ((K - b) % RING) * PXW);
             const float wl[4] = {wl4.x, wl4.y, wl4.z, wl4.w};
 #pragma unroll
             for (int a = 0; a < 4; a++) {
-                const float ab = wl[a] * ((RIGHT ? b < a : a < b) ? wr2[b] : wr[b]);  // f32 product, M.cpp:1104-1105
+                const float ab = wl[a] * ((RIGHT ? b < a : a < b) ? wr2[b] : wr[b]);  // f32 product, M.cpp:1104-1105 (x 2^120)
                 const double abd = (double)ab;
-                num[a][b] = __builtin_fma(abd, __builtin_fabs(c[a - b + 3]), num[a][b]);  // exact product: == num + ab*|c|
-                den[a][b] = den[a][b] + abd;                                      // M.cpp:1107-1108
+                num[a][b] = __builtin_fma(abd, c[a - b + 3], num[a][b]);  // exact product: == num + ab*c (x 2^-954)
+                den[a][b] = den[a][b] + abd;                              // M.cpp:1107-1108 (x 2^120)
             }
+        }
+        bL += 4 * LROW;
+        bR += 4 * RROW;
+        asm("" : "+v"(bL), "+v"(bR));
+        if constexpr (WRAPW || EDGE) {
+            bR2 += 4 * RROW;
+            asm("" : "+v"(bR2));
         }
     }
 }
@@ -316,26 +355,25 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
     const int x0 = (p.tile0 + blockIdx.x) * PXW, y = blockIdx.y;
     const int posmin = RIGHT ? x0 + p.minD : x0 - p.minD - 4 * NJ;  // == Q (mod 4) either way
 
-    // ---- gray tiles, replicate-clamped (M.cpp:1059-1060, 1101-1106), as bytes (weight staging) and as f64 (cost samples)
+    // ---- gray tiles, replicate-clamped (M.cpp:1059-1060, 1101-1106), as bytes (weight staging) and as u32 (cost samples)
     {
         uint8_t* sL8 = smem + OFF_L8;
         uint8_t* sR8 = smem + OFF_R8;
-        typedef typename Cfg::GrayT GrayT;
-        GrayT* sLd = reinterpret_cast<GrayT*>(smem + OFF_LD);
-        GrayT* sRd = reinterpret_cast<GrayT*>(smem + OFF_RD);
+        uint32_t* sLd = reinterpret_cast<uint32_t*>(smem + OFF_LB) + Cfg::LGRAY;
+        uint32_t* sRd = reinterpret_cast<uint32_t*>(smem + OFF_RB) + Cfg::RGRAY;
         for (int i = tid; i < KS * LWC; i += NTHR) {
             const int r = i / LWC, c = i - r * LWC;
             const int yy = min(max(y - HH + r, 0), H - 1), xx = min(max(x0 - HH + c, 0), W - 1);
             const int v = gL[(size_t)yy * W + xx];
             sL8[r * LW8 + c] = (uint8_t)v;
-            sLd[r * LWC + c] = (GrayT)v;
+            sLd[r * Cfg::LROW + c] = (uint32_t)v;
         }
         for (int i = tid; i < KS * RWC; i += NTHR) {
             const int r = i / RWC, c = i - r * RWC;
             const int yy = min(max(y - HH + r, 0), H - 1), xx = min(max(posmin - HH + c, 0), W - 1);
             const int v = gR[(size_t)yy * W + xx];
             sR8[r * RW8 + c] = (uint8_t)v;
-            sRd[r * RWC + c] = (GrayT)v;
+            sRd[r * Cfg::RROW + c] = (uint32_t)v;
         }
         uint16_t* sCell = reinterpret_cast<uint16_t*>(smem + OFF_CELL);
         for (int i = tid; i < NCELLCOL * KS; i += NTHR) {
@@ -347,7 +385,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
 
     // lane -> (pixel group g, position block jl): g's low three bits from the lane's low three bits and its bit 3 from lane bit
     // 5, so that the sixteen lanes one ds_read_b128 services together hold eight distinct g's (the f64 gray reads are 32 B
-    // apart per g: g and g + 8 share a bank; measured: 2.9e9 -> 0.9e9 conflict cycles per frame)
+    // apart per g: g and g + 8 share a bank; measured: 2.9e9 -> 0.9e9 conflict cycles per frame; kept for the u32 gray quads and
+    // the 16-byte weight reads, which are 16 B apart per g)
     const int g = (lane & 7) | ((lane >> 2) & 8);
     const int jl = 4 * wave + ((lane >> 3) & 3);
     // Q - posmin; LEFT: Q = x0 + 4g - minD - 4 jl, RIGHT: Q = x0 + 4g + minD + 4 jl
@@ -380,7 +419,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
                                                     x0, posmin, num, den);
     // (the last step ended with a barrier: the tiles are dead)
 
-    // ---- E = num / den (M.cpp:1111) -> LDS [candidate][pixel]
+    // ---- E = num / den (M.cpp:1111) -> LDS [candidate][pixel]; back from the scaled domain first (both ldexp are exact)
     double* sE = reinterpret_cast<double*>(smem + OFF_E64);
 #pragma unroll
     for (int a = 0; a < 4; a++)
@@ -388,7 +427,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
         for (int b = 0; b < 4; b++) {
             const int c = RIGHT ? (b < a ? dbase2 : dbase) - p.minD + b - a
                                 : (a < b ? dbase2 : dbase) - p.minD + a - b;  // in [0, 128) for every unit
-            sE[c * PXW + 4 * g + a] = num[a][b] / den[a][b];
+            sE[c * PXW + 4 * g + a] = __builtin_ldexp(num[a][b], 954) / __builtin_ldexp(den[a][b], -120);
         }
     __syncthreads();
     // ---- WTA (strict '<' while d ascends) and volume: thread -> (pixel, 16 consecutive candidates)
@@ -428,6 +467,21 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
 }  // namespace
 
 int bilateral_xq_candidates(int nwave) { return 16 * nwave; }
+
+// The scaled domain of the kernel is exact when every nonzero product of two LUT entries is >= 2^-68 (then every f32 product
+// is normal in both domains and every nonzero ab * c * 2^-954 >= 2^-1022) and when the scaled products stay finite:
+// (max * 2^60)^2 < 2^128.  At the reference's gammas (30, 20) the smallest product is about 2^-23.
+bool bilateral_xq_lut_ok(const float* lut, size_t n)
+{
+    double mn = 0, mx = 0;
+    for (size_t i = 0; i < n; i++) {
+        const double v = lut[i];
+        if (!(v >= 0)) return false;  // weights are exp() values: never negative or NaN
+        if (v > 0 && (mn == 0 || v < mn)) mn = v;
+        if (v > mx) mx = v;
+    }
+    return mn * mn >= std::ldexp(1.0, -68) && mx * mx < std::ldexp(1.0, 128 - 2 * XQ_LUT_SCALE_LOG2 - 1);
+}
 
 namespace {
 template <int NW>
@@ -476,7 +530,8 @@ int launch_xq_t(hipStream_t s, hipStream_t s_border, const uint8_t* gL, const ui
 }  // namespace
 
 // nwave: 8 = candidates [0, 128), 4 = candidates [0, 64).
-// cells: int4[21 * 15] {dxw, dyw, class * 256, -} per window cell, kx = -3..17; lut: float[ncls][256] with an all-zero class.
+// cells: int4[21 * 15] {dxw, dyw, class * 256, -} per window cell, kx = -3..17; lut: float[ncls][256] with an all-zero class,
+// scaled by 2^XQ_LUT_SCALE_LOG2, from an unscaled LUT that bilateral_xq_lut_ok accepts.
 // disp != nullptr: the launch covers the whole candidate range: write the disparity; else bestE / bestD.
 // s_border: stream of the border-tile launch (may equal s; a side stream lets the 1/30 of the tiles overlap the main launch)
 // right: DISPARITY_RIGHT -- gL is then the fixed (right) image's gray plane and gR the left image's.

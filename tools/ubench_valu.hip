@@ -120,6 +120,37 @@ KERNEL(k_cvt_add_dep, double a0 = threadIdx.x; double t = 0; float b = 1.0001f;,
                     : "+v"(a0), "+v"(t) : "v"(b));,
        out[blockIdx.x * blockDim.x + threadIdx.x] = (float)a0)
 
+// The integer cost sample of k_asw_bilateral_xq and what it replaces: 4 independent chains per wave as above
+KERNEL(k_sad_u32, unsigned a0 = threadIdx.x; unsigned a1 = a0 + 1; unsigned a2 = a0 + 2; unsigned a3 = a0 + 3; unsigned b = 0x37u;,
+       asm volatile("v_sad_u32 %0, %0, %4, 0\n v_sad_u32 %1, %1, %4, 0\n v_sad_u32 %2, %2, %4, 0\n v_sad_u32 %3, %3, %4, 0\n"
+                    "v_sad_u32 %0, %0, %4, 0\n v_sad_u32 %1, %1, %4, 0\n v_sad_u32 %2, %2, %4, 0\n v_sad_u32 %3, %3, %4, 0\n"
+                    : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "v"(b));,
+       out[blockIdx.x * blockDim.x + threadIdx.x] = (float)(a0 + a1 + a2 + a3))
+KERNEL(k_sad_u16, unsigned a0 = threadIdx.x; unsigned a1 = a0 + 1; unsigned a2 = a0 + 2; unsigned a3 = a0 + 3; unsigned b = 0x37u;,
+       asm volatile("v_sad_u16 %0, %0, %4, 0\n v_sad_u16 %1, %1, %4, 0\n v_sad_u16 %2, %2, %4, 0\n v_sad_u16 %3, %3, %4, 0\n"
+                    "v_sad_u16 %0, %0, %4, 0\n v_sad_u16 %1, %1, %4, 0\n v_sad_u16 %2, %2, %4, 0\n v_sad_u16 %3, %3, %4, 0\n"
+                    : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "v"(b));,
+       out[blockIdx.x * blockDim.x + threadIdx.x] = (float)(a0 + a1 + a2 + a3))
+KERNEL(k_add_u32, unsigned a0 = threadIdx.x; unsigned a1 = a0 + 1; unsigned a2 = a0 + 2; unsigned a3 = a0 + 3; unsigned b = 0x640u;,
+       asm volatile("v_add_u32 %0, %0, %4\n v_add_u32 %1, %1, %4\n v_add_u32 %2, %2, %4\n v_add_u32 %3, %3, %4\n"
+                    "v_add_u32 %0, %0, %4\n v_add_u32 %1, %1, %4\n v_add_u32 %2, %2, %4\n v_add_u32 %3, %3, %4\n"
+                    : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "v"(b));,
+       out[blockIdx.x * blockDim.x + threadIdx.x] = (float)(a0 + a1 + a2 + a3))
+// num' += ab' * c' as in the scaled domain: ab' ~ 2^120 (normal), c' = 37 * 2^-1074 (denormal), accumulators normal
+KERNEL(k_fma_f64_denorm, double a0 = 0x1p-1000 * (threadIdx.x + 1); double a1 = a0 * 2; double a2 = a0 * 3; double a3 = a0 * 4;
+       double w = 0x1.3p120; double c = __builtin_bit_cast(double COMMA (unsigned long long)37);,
+       asm volatile("v_fma_f64 %0, %4, %5, %0\n v_fma_f64 %1, %4, %5, %1\n v_fma_f64 %2, %4, %5, %2\n v_fma_f64 %3, %4, %5, %3\n"
+                    "v_fma_f64 %0, %4, %5, %0\n v_fma_f64 %1, %4, %5, %1\n v_fma_f64 %2, %4, %5, %2\n v_fma_f64 %3, %4, %5, %3\n"
+                    : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "v"(w), "v"(c));,
+       out[blockIdx.x * blockDim.x + threadIdx.x] = (float)((a0 + a1 + a2 + a3) * 0x1p1000))
+// the same with a normal c (37.0): the unscaled form
+KERNEL(k_fma_f64_normal, double a0 = 0x1p-10 * (threadIdx.x + 1); double a1 = a0 * 2; double a2 = a0 * 3; double a3 = a0 * 4;
+       double w = 0x1.3p-20; double c = 37.0;,
+       asm volatile("v_fma_f64 %0, %4, %5, %0\n v_fma_f64 %1, %4, %5, %1\n v_fma_f64 %2, %4, %5, %2\n v_fma_f64 %3, %4, %5, %3\n"
+                    "v_fma_f64 %0, %4, %5, %0\n v_fma_f64 %1, %4, %5, %1\n v_fma_f64 %2, %4, %5, %2\n v_fma_f64 %3, %4, %5, %3\n"
+                    : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "v"(w), "v"(c));,
+       out[blockIdx.x * blockDim.x + threadIdx.x] = (float)(a0 + a1 + a2 + a3))
+
 typedef void (*kern_t)(float*, int);
 
 int main()
@@ -131,7 +162,8 @@ int main()
         {"v_cvt_f32_ubyteN (x1.5)", k_cvt_f32_ubyte}, {"v_cvt_f32_ubyteN", k_cvt_ubyte8}, {"v_and/lshrrev_b32", k_and_shift}, {"v_min/max_u32", k_minmax_u32}, {"v_fma_f64", k_fma_f64}, {"v_add_f64", k_add_f64}, {"v_mul_f64", k_mul_f64},
         {"v_cvt_f64_f32", k_cvt_f64_f32}, {"v_cvt_f64_u32", k_cvt_f64_u32},
         {"v_add_f64 1 chain", k_add_f64_dep}, {"v_add_f64 2 chains", k_add_f64_dep2}, {"v_add_f32 1 chain", k_add_f32_dep},
-        {"cvt_f64_f32+add_f64 chain", k_cvt_add_dep}};
+        {"cvt_f64_f32+add_f64 chain", k_cvt_add_dep}, {"v_sad_u32", k_sad_u32}, {"v_sad_u16", k_sad_u16}, {"v_add_u32", k_add_u32},
+        {"v_fma_f64 denormal c", k_fma_f64_denorm}, {"v_fma_f64 normal c", k_fma_f64_normal}};
     hipEvent_t e0, e1;
     hipEventCreate(&e0);
     hipEventCreate(&e1);
