@@ -396,7 +396,8 @@ extern "C" int asw_guided_filter(asw_ctx* ctx, const asw_image* guide, const flo
     ASW_TRY(psc.ensure(sizeof(float2)));
     ASW_TRY(gsc.ensure(sizeof(float2)));
     ASW_TRY(stats.ensure(guided_stats_floats(C, 1, H, W) * 4));
-    ASW_TRY(ab.ensure(guided_ab_floats(C, 1, H, W, r) * 4));
+    const size_t ab_floats = guided_ab_floats(C, 1, H, W, r);  // two-pass path: a caller's P may hold NaN, the fused walk does not apply
+    ASW_TRY(ab.ensure(ab_floats * 4));
     ASW_TRY(qv.ensure(plane * 4));
     ASW_TRY(pxa.ensure((plane + 4) * 4));  // + slack: the q pass reads the guide words of a lane's two columns as one pair, the last one may start at column W-1
     ASW_TRY(pxb.ensure((plane + 4) * 4));
@@ -412,6 +413,7 @@ extern "C" int asw_guided_filter(asw_ctx* ctx, const asw_image* guide, const flo
     a.gscales = gsc.as<float2>(); a.P = raw.as<float>(); a.pscales = psc.as<float2>();
     a.H = H; a.W = W; a.n = 1; a.r = r; a.minD = 0; a.eps = eps;
     a.stats = stats.as<float>(); a.rep_scratch = nullptr; a.ab = ab.as<float>(); a.q = qv.as<float>();
+    a.ab_floats = ab_floats; a.fused = 0;
     a.tune = &ctx->tune;
     ASW_TRY(launch_guided(ctx->stream, a));
     ASW_HIP_TRY(hipMemcpyAsync(q, qv.p, plane * 4, hipMemcpyDeviceToHost, ctx->stream));

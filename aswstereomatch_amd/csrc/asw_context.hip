@@ -82,6 +82,7 @@ void AswTuning::read_environment()
     ring_ab = num("ASW_RING_AB", ring_ab);
     ring_q = num("ASW_RING_Q", ring_q);
     q_wg_strips = num("ASW_Q_WG_STRIPS", q_wg_strips);
+    guide_share = num("ASW_GUIDE_SHARE", guide_share);
     guided_fused = num("ASW_GUIDED_FUSED", guided_fused);
     q6_pair = num("ASW_Q6_PAIR", q6_pair);
     ab6_pair = num("ASW_AB6_PAIR", ab6_pair);

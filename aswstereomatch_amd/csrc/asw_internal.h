@@ -73,6 +73,8 @@ struct AswTuning {
     int ab6_pair = -1;           // ASW_AB6_PAIR: 0 = the a/b pass of the 6-channel guide through k_box_walk instead of k_ab6_pair
     int q6_pair = -1;            // ASW_Q6_PAIR: 0 = the q pass of the 6-channel guide through k_box_walk (re-fetching form) instead of k_q6_pair
     int q_wg_strips = 1;         // ASW_Q_WG_STRIPS: workgroup of the q pass = 4 neighbouring strips (1) / 4 slices of a strip (0)
+    int guide_share = 1;         // ASW_GUIDE_SHARE: 6-channel guide [fixed image, other image shifted by d] (GuidedF, GuidedF_3 LEFT / RIGHT):
+                                 // 1 = statistics shared across slices (k_guided.hip: StatsSplit), 0 = plain statistics of every slice
     void read_environment();
 };
 
@@ -199,12 +201,16 @@ struct GuidedLaunch {
     float* stats;           // scratch, guided_stats_floats(): {meanI_c, var_c+eps} interleaved per pixel and BGRX word
     int* rep_scratch;       // scratch, n ints (or null): scale-group representative of every slice (6-channel per-slice guides)
     float* ab;              // scratch, guided_ab_floats(): {a_c, b} per pixel (3-channel guide: strip-major float2 tiles, k_guided.hip ABTiles)
+    size_t ab_floats;       // capacity of `ab` in floats: the two-pass path needs guided_ab_floats(), the fused walk none
+    int fused;              // 1: the fused a/b -> q walk (the caller's guided_uses_fused decision); launch_guided does not decide again
     float* q;               // out [n][H][W]
     const AswTuning* tune;  // the context's switches
 };
 size_t guided_stats_floats(int C, int nstat, int H, int W);
 size_t guided_ab_floats(int C, int n, int H, int W, int r);
-// true: launch_guided will run the fused a/b -> q walk for this problem (no a/b scratch is touched)
+// true: the fused a/b -> q walk exists for this problem (3-channel slice-independent guide, finite costs, 15x15, H >= 16)
+bool guided_fused_form_exists(int C, int guide_per_slice, int shifted, int nan_safe, int H, int r);
+// true: run the fused walk (GuidedLaunch::fused) -- the form exists and the switches / frame size ask for it; decided once, by the caller
 bool guided_uses_fused(const AswTuning& t, int C, int guide_per_slice, int shifted, int nan_safe, int H, int W, int n, int r);
 int launch_pack_words(hipStream_t s, const uint8_t* img, int H, int W, int C, int w, uint32_t* out);
 int launch_guided(hipStream_t s, const GuidedLaunch& a);

@@ -336,8 +336,10 @@ static int run_guided(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_v
     ASW_TRY(gsc.ensure((size_t)n * sizeof(float2)));
     ASW_TRY(stats.ensure(guided_stats_floats(C, nstat, H, W) * 4));
     // (GuidedF_2 on large frames runs the fused walk: no a/b volume -- 4.4 GB at 1080p D=128)
+    // the one place that decides fused or two-pass; launch_guided follows GuidedLaunch::fused
     const bool fused = guided_uses_fused(ctx->tune, C, plain3 ? 0 : 1, 0, ncc ? 1 : 0, H, W, n, mp.win);
-    ASW_TRY(ab.ensure(fused ? 64 : guided_ab_floats(C, n, H, W, mp.win) * 4));
+    const size_t ab_floats = fused ? 16 : guided_ab_floats(C, n, H, W, mp.win);
+    ASW_TRY(ab.ensure(ab_floats * 4));
     ASW_TRY(pxa.ensure((plane + 4) * 4));  // + slack: the q pass reads the guide words of a lane's two columns as one pair, the last one may start at column W-1
     ASW_TRY(pxb.ensure((plane + 4) * 4));
     ASW_TRY(f->vol.ensure(plane * n * 4));  // q volume: always needed for the WTA pass
@@ -392,6 +394,7 @@ static int run_guided(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_v
     DevBuf& repb = ctx->buf("g_rep");
     ASW_TRY(repb.ensure((size_t)n * sizeof(int)));
     a.stats = stats.as<float>(); a.rep_scratch = repb.as<int>(); a.ab = ab.as<float>(); a.q = f->vol.as<float>();
+    a.ab_floats = ab_floats; a.fused = fused ? 1 : 0;
     a.tune = &ctx->tune;
     ASW_HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
     ASW_TRY(launch_guided(ctx->stream, a));

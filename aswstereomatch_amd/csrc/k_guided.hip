@@ -1137,7 +1137,8 @@ int launch_walk(hipStream_t s, const Src& src, const Dst& dst, int H, int W, int
 // path): there it runs as fast as the two passes within the spread of the boxes (kernel 3.65-3.83 against 3.42-3.60 ms, whole
 // aggregation by the library's events 3.63 / 3.64 against 3.59 / 3.73 ms on two boxes); on small frames the two passes win.  A
 // first form with both stages in ONE wavefront (both rings: 284-470 registers, one wavefront per SIMD) took 4.18-5.70 ms; the
-// form below splits the stages over a PAIR of wavefronts.  Results are bit-identical to the two-pass path.
+// form below splits the stages over a PAIR of wavefronts.  Results are the two-pass path's real sums in another f64 order: bit-identical
+// where those sums are exact, otherwise within 1 f32 ulp (tests/test_gpu_guided_forms.py).
 struct FusedArgs {
     GuideAccT<false> g;
     const float* P;          // raw cost volume [n][H][W]
@@ -2002,8 +2003,8 @@ int launch_guided3(hipStream_t s, const GuidedLaunch& a, const GuideAccT<SHIFT>&
         if (rc != ASW_OK) return rc;
     }
     if constexpr (!SHIFT) {
-        // one fused a/b -> q walk, no a/b volume (k_guided_pair3)
-        if (guided_uses_fused(t, 3, nstat > 1, 0, a.nan_safe, a.H, a.W, a.n, a.r)) return launch_guided_fused3(s, a, g, sp, t.band_q);
+        // one fused a/b -> q walk, no a/b volume (k_guided_pair3); launch_guided checked that the form exists
+        if (a.fused) return launch_guided_fused3(s, a, g, sp, t.band_q);
     }
     const ABTiles at = ab_tiles(a.H, a.W, a.r);
     ABDstP dst{sp, nstat > 1 ? 1 : 0, reinterpret_cast<float2*>(a.ab), at, a.W};
@@ -2066,6 +2067,13 @@ int launch_guided(hipStream_t s, const GuidedLaunch& a)
     sp.rep = nullptr; sp.per_slice = a.guide_per_slice ? 1 : 0; sp.shifted = -1; sp.sgn = 0;
     sp.lo = a.r / 2; sp.hi = a.r - 1 - a.r / 2; sp.W = a.W; sp.minD = a.minD;
     int rc;
+    // the caller decided fused or two-pass (and sized the a/b scratch for it): a form that does not exist, or a two-pass path
+    // that would write past the a/b capacity, is refused rather than run
+    if (a.fused) {
+        if (!guided_fused_form_exists(a.C, a.guide_per_slice, shifted, a.nan_safe, a.H, a.r)) return ASW_ERR_BAD_ARGUMENT;
+    } else if (a.ab_floats < guided_ab_floats(a.C, a.n, a.H, a.W, a.r)) {
+        return ASW_ERR_BAD_ARGUMENT;
+    }
     if (a.C == 3 && !shifted) {
         // GuidedF_2 / 3-channel getGuidedFilter: the guide does not depend on the slice.
         // 1. guide statistics, once   2. a, b   3. q
@@ -2075,7 +2083,7 @@ int launch_guided(hipStream_t s, const GuidedLaunch& a)
     GuideAccT<true> g{a.guideA, a.guideB, a.gscales, a.guide_per_slice ? 1 : 0, a.W, a.shiftA, a.shiftB, a.minD};
     if (a.C == 3) return launch_guided3<true>(s, a, g, nstat);
     // 6-channel guide
-    const bool share = a.guide_per_slice && a.rep_scratch && ((a.shiftA != 0) != (a.shiftB != 0));
+    const bool share = a.tune->guide_share != 0 && a.guide_per_slice && a.rep_scratch && ((a.shiftA != 0) != (a.shiftB != 0));
     StatsSrc<6, 0, true> s0{g};
     StatsSrc<6, 1, true> s1{g};
     if (!share) {  // public getGuidedFilter (one slice) or both / no words shifted: plain per-slot statistics
@@ -2161,9 +2169,14 @@ size_t guided_stats_floats(int C, int nstat, int H, int W)
 // The fused walk pays 28 warm-up rows per band and 28 halo columns per strip: it matches the two passes when the frame gives
 // it ~10 rounds of tall bands (1080p D=128: 3.64 against 3.73 ms, 4K D=64: 6.97 / 7.03, 720p D=96: 1.49 / 1.49) and loses on small
 // ones (640x360 D=64: 0.33 / 0.27 ms, 1242x375 D=192: 1.63 / 1.37, 1080p D=32: 1.15 / 1.08) -- tools/time_fused_shapes.py.
+bool guided_fused_form_exists(int C, int guide_per_slice, int shifted, int nan_safe, int H, int r)
+{
+    return C == 3 && !guide_per_slice && !shifted && !nan_safe && r == 15 && H >= 16;
+}
+
 bool guided_uses_fused(const AswTuning& t, int C, int guide_per_slice, int shifted, int nan_safe, int H, int W, int n, int r)
 {
-    if (C != 3 || guide_per_slice || shifted || nan_safe || r != 15 || H < 16 || t.guided_fused == 0) return false;
+    if (!guided_fused_form_exists(C, guide_per_slice, shifted, nan_safe, H, r) || t.guided_fused == 0) return false;
     if (t.guided_fused > 0) return true;
     const long long strips = (W + 99) / 100;
     return strips * n * H >= 2000000LL;

@@ -380,7 +380,7 @@ def test_guided2_fused_walk_equals_two_pass_path(oracle):
             L, R, _ = make_pair(H, W, D, seed=seed)
             d0, v0 = base.computeAdaptiveWeight_GuidedF_2(L, R, LEFT, 1e-6, 15, 0, D, return_cost_volume=True)
             d1, v1 = fused.computeAdaptiveWeight_GuidedF_2(L, R, LEFT, 1e-6, 15, 0, D, return_cost_volume=True)
-            assert np.array_equal(d0, d1) and np.allclose(v0, v1, rtol=1e-6, atol=0)
+            assert np.array_equal(d0, d1) and np.array_equal(v0, v1)
             rc, dw, vw = oracle.asw_guided2(L, R, 0, 1e-6, 15, 0, D, want_vol=True)
             assert rc == 0 and np.allclose(v1, vw, rtol=1e-4, atol=1e-6) and np.array_equal(d1, dw)
     finally:
