@@ -26,7 +26,7 @@ __all__ = [
     "computeAdaptiveWeight_geodesic", "getGeodesicDist", "getGuidedFilter", "computeAdaptiveWeight_GuidedF",
     "computeAdaptiveWeight_GuidedF_2", "computeAdaptiveWeight_WeightedMedian", "winnerTakeAll", "last_status",
     "stereoMatchingBatch", "computeAdaptiveWeight_BLO1", "computeAdaptiveWeight_direct8", "computeNCC", "computeNCC_costs",
-    "computeAdaptiveWeight_GuidedF_3",
+    "computeAdaptiveWeight_GuidedF_3", "getDisparity_SGBM", "sgbm", "filterSpeckles",
     "AswError",
 ]
 
@@ -56,6 +56,7 @@ DISPARITY_RIGHT = DisparityType.DISPARITY_RIGHT
 
 OK, ERR_SIZE_MISMATCH, ERR_EVEN_WINDOW, ERR_UNSUPPORTED_METHOD, ERR_UNSUPPORTED_LAYOUT = 0, 1, 2, 3, 4
 ERR_HIP, ERR_ALLOC, ERR_BAD_ARGUMENT, ERR_NO_FRAME = 5, 6, 7, 8
+MODE_SGBM_3WAY = 2  # StereoSGBM::MODE_SGBM_3WAY, the one mode asw_sgbm serves
 # statuses for which the reference returns silently / an empty Mat
 _SILENT = (ERR_SIZE_MISMATCH, ERR_EVEN_WINDOW)
 
@@ -70,7 +71,7 @@ def last_status():
 def _image(arr, depth=0):
     """numpy array -> asw_image (keeps `arr` alive through the returned tuple)."""
     a = np.asarray(arr)
-    want = np.uint8 if depth == 0 else np.float32
+    want = {0: np.uint8, 3: np.int16, 5: np.float32}[depth]
     if a.dtype != want:
         raise TypeError("expected %s image, got %s" % (np.dtype(want).name, a.dtype))
     if a.ndim == 2:
@@ -240,6 +241,43 @@ class Context:
         return self._aggregate(self._lib.asw_aggregate_wmedian, "asw_aggregate_wmedian", numDisparity, leftImg, rightImg,
                                (int(dispType), winSize, float(sampleRateS), float(sampleRateR), minDisparity, numDisparity),
                                return_cost_volume)
+
+    # ---- semi-global block matching ----
+    def getDisparity_SGBM(self, srcLeft, srcRight, winSize=15, minDisparity=0, numDisparity=64):
+        """getDisparity_SGBM (M.h:94, aswMethods.cpp:158-194): StereoSGBM with the reference's settings -> uint8 map
+        (convertTo(CV_8U, 1/16)).  Where the reference raises CV_Error (numDisparity % 16 != 0, even winSize) AswError is raised
+        with status ERR_UNSUPPORTED_METHOD."""
+        d = self.stereoMatching(srcLeft, srcRight, DISPARITY_LEFT, StereoMatchingAlgorithms.SGBM, winSize, minDisparity,
+                                numDisparity)
+        return None if d is None else d.astype(np.uint8)
+
+    def sgbm(self, left, right, minDisparity, numDisparities, blockSize, P1=0, P2=0, disp12MaxDiff=0, preFilterCap=0,
+             uniquenessRatio=0, speckleWindowSize=0, speckleRange=0, mode=MODE_SGBM_3WAY, return_cost_volume=False):
+        """StereoSGBM::create(...) + compute(): int16 disparity x 16 (invalid: 16 * (minDisparity - 1)); with return_cost_volume
+        also the aggregated cost S, float32 [numDisparities][H][W] (asw_sgbm)."""
+        li, la = _image(left)
+        ri, ra = _image(right)
+        disp = np.zeros(la.shape[:2], np.int16)
+        di, _ = _image(disp, 3)
+        vol, pv = None, None
+        if return_cost_volume:
+            vol = np.zeros((numDisparities,) + la.shape[:2], np.float32)
+            pv = vol.ctypes.data_as(C.c_void_p)
+        rc = self._lib.asw_sgbm(self._h, C.byref(li), C.byref(ri), C.byref(di), minDisparity, numDisparities, blockSize, P1, P2,
+                                disp12MaxDiff, preFilterCap, uniquenessRatio, speckleWindowSize, speckleRange, int(mode), pv,
+                                0 if vol is None else vol.size)
+        self._strict(rc, "asw_sgbm")
+        return (disp, vol) if return_cost_volume else disp
+
+    def filterSpeckles(self, img, newVal, maxSpeckleSize, maxDiff):
+        """cv::filterSpeckles on an int16 map (asw_filter_speckles): the filtered copy."""
+        a = np.array(img, copy=True)
+        if a.dtype != np.int16 or a.ndim != 2:
+            raise TypeError("filterSpeckles: a 2-D int16 map expected (CV_16SC1), got %s %s" % (a.dtype, a.shape))
+        ii, a = _image(a, 3)
+        self._strict(self._lib.asw_filter_speckles(self._h, C.byref(ii), int(newVal), int(maxSpeckleSize), int(maxDiff)),
+                     "asw_filter_speckles")
+        return a
 
     # ---- cost builders (M.h:101-113): return a list of planes like std::vector<cv::Mat> ----
     def _cost(self, fn, name, leftImg, rightImg, dtype, plane_shape, numDisparity, args):
@@ -484,3 +522,6 @@ computeAdaptiveWeight_GuidedF_2 = _bind("computeAdaptiveWeight_GuidedF_2")
 computeAdaptiveWeight_WeightedMedian = _bind("computeAdaptiveWeight_WeightedMedian")
 computeAdaptiveWeight_BLO1 = _bind("computeAdaptiveWeight_BLO1")
 winnerTakeAll = _bind("winnerTakeAll")
+getDisparity_SGBM = _bind("getDisparity_SGBM")
+sgbm = _bind("sgbm")
+filterSpeckles = _bind("filterSpeckles")

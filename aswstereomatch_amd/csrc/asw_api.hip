@@ -20,6 +20,7 @@ int match_host(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_
     ASW_TRY(check_pair(left, right));
     ASW_TRY(check_disp_out(disp, left->rows, left->cols));
     if (cost_volume_out) {  // the caller states what its buffer holds; a short one is refused before anything is written
+        if (algorithm == ASW_ALG_SGBM) return ASW_ERR_BAD_ARGUMENT;  // the selector's SGBM has no volume (asw_sgbm has S)
         const int planes = asw_volume_planes(algorithm, mp.numD);
         if (planes > 0 && cost_volume_floats < (size_t)planes * left->rows * left->cols) return ASW_ERR_BAD_ARGUMENT;
     }
@@ -484,4 +485,93 @@ extern "C" int asw_aggregate_wmedian(asw_ctx* ctx, const asw_image* left, const 
     mp.disparity_type = disparity_type; mp.win = win_size; mp.minD = min_disparity; mp.numD = num_disparity;
     mp.rate_s = rate_s; mp.rate_r = rate_r;
     return match_host(ctx, left, right, disp, ASW_ALG_ADAPTIVE_WEIGHT_MEDIAN, mp, cost_volume_out, cost_volume_floats);
+}
+
+// ---- semi-global block matching (StereoSGBM::compute, MODE_SGBM_3WAY) and cv::filterSpeckles ----
+static int check_s16_image(const asw_image* im)
+{
+    if (!im || !im->data || im->rows <= 0 || im->cols <= 0) return ASW_ERR_BAD_ARGUMENT;
+    if (im->depth != ASW_16S || im->channels != 1) return ASW_ERR_UNSUPPORTED_LAYOUT;
+    if (im->step < (size_t)im->cols * sizeof(short)) return ASW_ERR_BAD_ARGUMENT;
+    return ASW_OK;
+}
+
+// events around a host-buffer call that does not go through run_method
+static int timed_finish(asw_ctx* ctx)
+{
+    ASW_HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
+    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    float t = 0;
+    ASW_HIP_TRY(hipEventElapsedTime(&t, ctx->ev[0], ctx->ev[1]));
+    ctx->timing.total_ms = t;
+    ASW_HIP_TRY(hipEventElapsedTime(&t, ctx->ev[2], ctx->ev[3]));
+    ctx->timing.aggregate_ms = t;
+    ctx->timing.cost_ms = ctx->timing.total_ms - ctx->timing.aggregate_ms;
+    return ASW_OK;
+}
+
+extern "C" int asw_sgbm(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp16, int min_disparity,
+                        int num_disparities, int block_size, int p1, int p2, int disp12_max_diff, int pre_filter_cap,
+                        int uniqueness_ratio, int speckle_window_size, int speckle_range, int mode, float* cost_volume_out,
+                        size_t cost_volume_floats)
+{
+    if (!ctx) return ASW_ERR_BAD_ARGUMENT;
+    ASW_TRY(check_pair(left, right));
+    ASW_TRY(check_s16_image(disp16));  // the same status as asw_filter_speckles for a map that is not CV_16SC1
+    if (disp16->rows != left->rows || disp16->cols != left->cols || disp16->step < (size_t)left->cols * sizeof(short))
+        return ASW_ERR_BAD_ARGUMENT;
+    const int H = left->rows, W = left->cols;
+    SgbmParams p;
+    p.minD = min_disparity; p.numD = num_disparities; p.block_size = block_size; p.P1 = p1; p.P2 = p2;
+    p.disp12_max_diff = disp12_max_diff; p.pre_filter_cap = pre_filter_cap; p.uniqueness_ratio = uniqueness_ratio;
+    p.speckle_window_size = speckle_window_size; p.speckle_range = speckle_range; p.mode = mode;
+    ASW_HIP_TRY(hipSetDevice(ctx->device));
+    SgbmLaunch a;
+    ASW_TRY(sgbm_prepare(ctx, p, H, W, left->channels, cost_volume_out != nullptr, &a));
+    const size_t plane = (size_t)H * W, vol_floats = plane * (size_t)num_disparities;
+    if (cost_volume_out && cost_volume_floats < vol_floats) return ASW_ERR_BAD_ARGUMENT;
+    Frame* f = &ctx->host_frame;
+    ASW_TRY(upload_pair_into(ctx, f, left, right));
+    f->invalidate_results();
+    DevBuf& vol = ctx->buf("sgbm_volume");
+    if (cost_volume_out) ASW_TRY(vol.ensure(vol_floats * sizeof(float)));
+    a.L = f->L.as<uint8_t>(); a.R = f->R.as<uint8_t>();
+    a.vol = cost_volume_out ? vol.as<float>() : nullptr;
+    a.ev_agg0 = ctx->ev[2]; a.ev_agg1 = ctx->ev[3];
+    ASW_HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
+    ASW_TRY(launch_sgbm(ctx->stream, a));
+    ASW_TRY(timed_finish(ctx));
+    ctx->timing.aggregate_launches = 2;
+    ASW_HIP_TRY(copy_rows(ctx, disp16->data, disp16->step, a.disp16, (size_t)W * sizeof(short), (size_t)W * sizeof(short), H,
+                          hipMemcpyDeviceToHost));
+    if (cost_volume_out)
+        ASW_HIP_TRY(hipMemcpyAsync(cost_volume_out, vol.p, vol_floats * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ASW_OK;
+}
+
+extern "C" int asw_filter_speckles(asw_ctx* ctx, asw_image* img, int new_val, int max_speckle_size, int max_diff)
+{
+    if (!ctx) return ASW_ERR_BAD_ARGUMENT;
+    ASW_TRY(check_s16_image(img));
+    if (new_val < -32768 || new_val > 32767) return ASW_ERR_BAD_ARGUMENT;
+    const int H = img->rows, W = img->cols;
+    const size_t plane = (size_t)H * W;
+    if (plane >= ((size_t)1 << 31)) return ASW_ERR_BAD_ARGUMENT;
+    ASW_HIP_TRY(hipSetDevice(ctx->device));
+    DevBuf& buf = ctx->buf("speckle_img");
+    DevBuf& scratch = ctx->buf("speckle_scratch");
+    ASW_TRY(buf.ensure(plane * sizeof(short)));
+    ASW_TRY(scratch.ensure(plane * 2 * sizeof(int)));
+    const size_t row = (size_t)W * sizeof(short);
+    ASW_HIP_TRY(copy_rows(ctx, buf.p, row, img->data, img->step, row, H, hipMemcpyHostToDevice));
+    ASW_HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
+    ASW_HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
+    ASW_TRY(launch_filter_speckles(ctx->stream, buf.as<short>(), H, W, new_val, max_speckle_size, max_diff, scratch.as<int>()));
+    ASW_HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
+    ASW_TRY(timed_finish(ctx));
+    ctx->timing.aggregate_launches = 4;  // k_spk_init, union, flatten, apply (+ the pointer-jumping rounds between them)
+    ASW_HIP_TRY(copy_rows(ctx, img->data, img->step, buf.p, row, row, H, hipMemcpyDeviceToHost));
+    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ASW_OK;
 }

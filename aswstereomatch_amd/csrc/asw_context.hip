@@ -196,7 +196,7 @@ int check_pair(const asw_image* L, const asw_image* R)
 // milliseconds when the row length is not a multiple of the DMA granule (1242 x 3 bytes per row: 6.7 ms per call for the three
 // copies of a KITTI-shape frame, against 0.9 ms at 1920 x 3), whatever the pitch -- so padded rows are packed / unpacked on the
 // host through a dense staging buffer of the context and travel as a 1-D copy as well.
-static hipError_t copy_rows(asw_ctx* ctx, void* dst, size_t dpitch, const void* src, size_t spitch, size_t rowbytes, size_t rows,
+hipError_t copy_rows(asw_ctx* ctx, void* dst, size_t dpitch, const void* src, size_t spitch, size_t rowbytes, size_t rows,
                             hipMemcpyKind kind)
 {
     hipStream_t s = ctx->stream;

@@ -23,6 +23,9 @@ struct MatchParams {
 int check_u8_image(const asw_image* im);
 int check_pair(const asw_image* L, const asw_image* R);
 int upload_image(asw_ctx* ctx, const asw_image* im, DevBuf& dst);
+// pitched host rows <-> dense device rows on the context's stream (asw_context.hip)
+hipError_t copy_rows(asw_ctx* ctx, void* dst, size_t dpitch, const void* src, size_t spitch, size_t rowbytes, size_t rows,
+                     hipMemcpyKind kind);
 int check_disp_out(const asw_image* d, int rows, int cols);
 Frame* frame_slot(asw_ctx* ctx, int slot, bool create);
 int upload_pair_into(asw_ctx* ctx, Frame* f, const asw_image* left, const asw_image* right);
@@ -34,6 +37,12 @@ int build_similarity_volume(asw_ctx* ctx, const uint8_t* dL, const uint8_t* dR, 
 int run_ncc_cost(asw_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int H, int W, int disparity_type, int win, int minD,
                         int numD, float* vol /* optional, un-normalised */, float* disp /* optional */, int nwta,
                         int channels = 3);
+// StereoSGBM parameters as StereoSGBM::create takes them; sgbm_prepare validates them, derives the effective
+// values of step 0 and sizes the scratch, run_sgbm enqueues the kernels on the context's stream
+struct SgbmParams {
+    int minD, numD, block_size, P1, P2, disp12_max_diff, pre_filter_cap, uniqueness_ratio, speckle_window_size, speckle_range, mode;
+};
+int sgbm_prepare(asw_ctx* ctx, const SgbmParams& p, int H, int W, int cn, bool want_volume, SgbmLaunch* out);
 int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp, bool keep_volume, bool sync = true);
 int match_host(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp, int algorithm,
                       const MatchParams& mp, float* cost_volume_out, size_t cost_volume_floats);

@@ -264,3 +264,22 @@ int asw_internal_stage_slot(asw_ctx* ctx, int slot, int rows, int cols, int chan
 int asw_internal_enqueue_match(asw_ctx* ctx, int slot, int disparity_type, int algorithm, int win_size, int min_disparity,
                                int num_disparity);  // enqueues on ctx->stream, does not wait
 int asw_internal_check_pair(const asw_image* l, const asw_image* r, const asw_image* d);
+
+// ---- semi-global block matching (k_sgbm.hip): StereoSGBM MODE_SGBM_3WAY + filterSpeckles, DESIGN.md section 4.8 ----
+struct SgbmLaunch {
+    const uint8_t* L;  // dense interleaved 8U images, cn channels
+    const uint8_t* R;
+    int H, W, cn;
+    int minD, D;       // D: a multiple of 16, at most 1024
+    int w, ftzero, P1, P2, U, M;  // effective parameters (step 0)
+    int speckle_window, speckle_range;
+    void* scratch;     // sgbm_scratch_bytes()
+    short* disp16;     // out [H][W], scaled by 16
+    float* vol;        // optional S [D][H][W]
+    hipEvent_t ev_agg0 = nullptr, ev_agg1 = nullptr;  // optional: recorded around the path kernels (asw_timing::aggregate_ms)
+};
+size_t sgbm_scratch_bytes(int H, int W, int cn, int minD, int D);
+int launch_sgbm(hipStream_t s, const SgbmLaunch& a);
+int launch_filter_speckles(hipStream_t s, short* img, int H, int W, int new_val, int max_size, int max_diff,
+                           int* scratch /* 2 * H * W ints */);
+int launch_disp16_to_u8f(hipStream_t s, const short* disp16, size_t n, float* out);

@@ -1,5 +1,6 @@
 // Method runners behind the selector stereoMatching (M.cpp:46-88): tables, scratch buffers and launch sequences of every
 // method, with the literals the selector hard-codes and the reference's error behaviour.
+#include <limits.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -690,6 +691,71 @@ static int run_bilgrid(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_
     return ASW_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// semi-global block matching: StereoSGBM MODE_SGBM_3WAY and the selector's getDisparity_SGBM
+// (aswMethods.cpp:158-194)
+// ------------------------------------------------------------------------------------------
+int sgbm_prepare(asw_ctx* ctx, const SgbmParams& p, int H, int W, int cn, bool want_volume, SgbmLaunch* out)
+{
+    if (p.mode != 2) return ASW_ERR_UNSUPPORTED_METHOD;  // MODE_SGBM_3WAY only
+    if (p.minD < 0 || p.numD <= 0 || p.numD % 16 != 0 || p.numD > 1024) return ASW_ERR_BAD_ARGUMENT;
+    if (cn != 1 && cn != 3) return ASW_ERR_UNSUPPORTED_LAYOUT;
+    if (16 * ((long long)p.minD + p.numD) > 32767) return ASW_ERR_BAD_ARGUMENT;  // the scaled map is int16
+    if ((size_t)H * W >= ((size_t)1 << 31)) return ASW_ERR_BAD_ARGUMENT;         // pixel indices of the speckle filter are int
+    SgbmLaunch a{};
+    a.H = H; a.W = W; a.cn = cn; a.minD = p.minD; a.D = p.numD;
+    // step 0: StereoSGBM::compute's effective parameters
+    a.ftzero = std::max(p.pre_filter_cap, 15) | 1;
+    a.P1 = p.P1 > 0 ? p.P1 : 2;
+    a.P2 = std::max(p.P2 > 0 ? p.P2 : 5, a.P1 + 1);
+    a.U = p.uniqueness_ratio < 0 ? 10 : p.uniqueness_ratio;
+    a.M = p.disp12_max_diff <= 0 ? 1 : p.disp12_max_diff;
+    a.w = p.block_size <= 0 ? 5 : p.block_size;
+    a.speckle_window = p.speckle_window_size;
+    a.speckle_range = (int)std::min<long long>(std::max(p.speckle_range, -(1 << 26)), 1 << 26);  // 16 * range stays an int
+    if (a.P1 == INT_MAX) return ASW_ERR_BAD_ARGUMENT;  // P2 >= P1 + 1
+    // every C, L and S is exact in int32: S <= 3 * (C_max + P2); the f32 volume needs the same bound below 2^24
+    const double k = 2 * (a.w / 2) + 1;
+    const double bound = 3.0 * ((double)cn * (2.0 * a.ftzero + 63.0) * k * k + a.P2);
+    if (bound >= 2147483648.0) return ASW_ERR_BAD_ARGUMENT;
+    if (want_volume && bound >= 16777216.0) return ASW_ERR_BAD_ARGUMENT;
+    DevBuf& scratch = ctx->buf("sgbm_scratch");
+    DevBuf& d16 = ctx->buf("sgbm_disp16");
+    ASW_TRY(scratch.ensure(sgbm_scratch_bytes(H, W, cn, a.minD, a.D)));
+    ASW_TRY(d16.ensure((size_t)H * W * sizeof(short)));
+    a.scratch = scratch.p;
+    a.disp16 = d16.as<short>();
+    *out = a;
+    return ASW_OK;
+}
+
+// getDisparity_SGBM: CV_Error for numDisparity % 16 != 0 or an even window (-> ASW_ERR_UNSUPPORTED_METHOD, the status of a method
+// the library does not serve); the images as they are (cn 1 or 3); StereoSGBM::create(minD, numD, w) with the settings below;
+// compute() -> convertTo(CV_8U, 1/16).  disparityType is ignored: both directions give the left-view map.  No volume is kept.
+static int run_sgbm(asw_ctx* ctx, Frame* f, const MatchParams& mp)
+{
+    if (mp.numD % 16 != 0 || mp.win % 2 == 0) return ASW_ERR_UNSUPPORTED_METHOD;
+    const int cn = f->channels, w = mp.win > 0 ? mp.win : 3;
+    if (w > 4096) return ASW_ERR_BAD_ARGUMENT;  // 32 * cn * w * w stays an int (and far beyond the exactness bound anyway)
+    SgbmParams p;
+    p.minD = mp.minD; p.numD = mp.numD; p.block_size = w;
+    p.P1 = 8 * cn * w * w; p.P2 = 32 * cn * w * w;
+    p.disp12_max_diff = 200; p.pre_filter_cap = 10; p.uniqueness_ratio = 10;
+    p.speckle_window_size = 175; p.speckle_range = 32; p.mode = 2;
+    SgbmLaunch a;
+    ASW_TRY(sgbm_prepare(ctx, p, f->rows, f->cols, cn, false, &a));
+    a.L = f->L.as<uint8_t>(); a.R = f->R.as<uint8_t>();
+    a.vol = nullptr;
+    a.ev_agg0 = ctx->ev[2]; a.ev_agg1 = ctx->ev[3];
+    const size_t plane = (size_t)f->rows * f->cols;
+    ASW_TRY(f->disp.ensure(plane * 4));
+    f->vol_floats = 0;
+    ASW_TRY(launch_sgbm(ctx->stream, a));
+    ASW_TRY(launch_disp16_to_u8f(ctx->stream, a.disp16, plane, f->disp.as<float>()));
+    ctx->timing.aggregate_launches = 2;
+    return ASW_OK;
+}
+
 int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp, bool keep_volume, bool sync)
 {
     f->invalidate_results();  // whatever the slot's disparity / volume were, they are not this call's
@@ -708,6 +774,7 @@ int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp, boo
     case ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER_3: rc = run_guided(ctx, f, mp, keep_volume, GUIDED_NCC); break;
     case ASW_ALG_NCC: rc = run_ncc(ctx, f, mp, keep_volume); break;
     case ASW_ALG_ADAPTIVE_WEIGHT_MEDIAN: rc = run_wmedian(ctx, f, mp, keep_volume); break;
+    case ASW_ALG_SGBM: rc = run_sgbm(ctx, f, mp); break;
     default: rc = ASW_ERR_UNSUPPORTED_METHOD; break;
     }
     if (rc != ASW_OK) {

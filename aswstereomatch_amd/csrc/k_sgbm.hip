@@ -1,0 +1,532 @@
+// Semi-global block matching, StereoSGBM MODE_SGBM_3WAY as DESIGN.md section 4.8 states it (OpenCV 4.1.0 stereosgbm.cpp), and
+// cv::filterSpeckles.  Integer arithmetic throughout; every intermediate is exact in 32 bits (the host refuses parameters for which
+// 3 * (C_max + P2) >= 2^31).
+//
+// Layout: the volumes C (block cost), T (L_tb, then L_tb + L_lr, then S) are int32 [H][Wv][D] with d innermost, over the valid
+// columns x = x0 + xi, x0 = minX1 = minD + D, Wv = W - x0.  Candidate index d <-> absolute disparity minD + d.
+//
+//   k_sgbm_prefilter  step 1 + the Birchfield-Tomasi interval: {value, min, max} planes of every prefiltered plane
+//   k_sgbm_hcost      steps 2 + horizontal half of 3: one thread per (y, d) walks the row with a running window sum
+//   k_sgbm_top        vertical half of 3 + the top->bottom path: one wavefront per column, candidates in lanes
+//   k_sgbm_row        left->right and right->left paths, winner, uniqueness, subpixel, disp2 keys: one wavefront per row
+//   k_sgbm_lr         the left-right rule of step 6 -> int16 map
+//   k_median3_s16     step 7;  k_spk_*: step 8 (union-find over the whole frame);  k_disp16_to_u8f: step 9
+#include "asw_internal.h"
+#include "asw_host.h"
+
+namespace {
+
+constexpr int SGBM_BIG = 0x3fffffff;  // "no predecessor": above every L (< 2^31 / 3), and BIG + P1 < 2^31
+
+// {value, min, max} of one prefiltered plane at x of row y; columns 0 and W-1 hold ftzero (OpenCV's border quirk)
+__device__ __forceinline__ int sgbm_pre(const uint8_t* __restrict__ img, int H, int W, int cn, int k, int y, int x, int ftzero)
+{
+    if (x <= 0 || x >= W - 1) return ftzero;
+    if (k >= cn) return img[((size_t)y * W + x) * cn + (k - cn)];
+    const int yn = max(y - 1, 0), ys = min(y + 1, H - 1);
+    const uint8_t* r0 = img + (size_t)y * W * cn + k;
+    const uint8_t* rn = img + (size_t)yn * W * cn + k;
+    const uint8_t* rs = img + (size_t)ys * W * cn + k;
+    const int s = 2 * ((int)r0[(x + 1) * cn] - (int)r0[(x - 1) * cn]) + (int)rn[(x + 1) * cn] - (int)rn[(x - 1) * cn] +
+                  (int)rs[(x + 1) * cn] - (int)rs[(x - 1) * cn];
+    return min(max(s, -ftzero), ftzero) + ftzero;
+}
+
+// out: int3-like planes [img 0|1][k][H][W] of {v, vmin, vmax}
+__global__ __launch_bounds__(256) void k_sgbm_prefilter(const uint8_t* __restrict__ L, const uint8_t* __restrict__ R, int H, int W,
+                                                        int cn, int ftzero, int4* __restrict__ out)
+{
+    const size_t plane = (size_t)H * W;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= plane) return;
+    const int y = (int)(i / W), x = (int)(i % W);
+    for (int img = 0; img < 2; img++) {
+        const uint8_t* src = img ? R : L;
+        for (int k = 0; k < 2 * cn; k++) {
+            const int a = sgbm_pre(src, H, W, cn, k, y, x, ftzero);
+            const int l = x > 0 ? sgbm_pre(src, H, W, cn, k, y, x - 1, ftzero) : a;
+            const int r = x < W - 1 ? sgbm_pre(src, H, W, cn, k, y, x + 1, ftzero) : a;
+            const int hl = (a + l) >> 1, hr = (a + r) >> 1;
+            out[((size_t)img * 2 * cn + k) * plane + i] = make_int4(a, min(a, min(hl, hr)), max(a, max(hl, hr)), 0);
+        }
+    }
+}
+
+// pixel cost of left column x against right column x - off (step 2)
+__device__ __forceinline__ int sgbm_pix(const int4* __restrict__ pf, size_t plane, int cn, size_t rowL, size_t rowR)
+{
+    int tot = 0;
+    for (int k = 0; k < 2 * cn; k++) {
+        const int4 u = pf[(size_t)k * plane + rowL];
+        const int4 v = pf[((size_t)2 * cn + k) * plane + rowR];
+        const int c = min(max(max(0, u.x - v.z), v.y - u.x), max(max(0, v.x - u.z), u.y - v.x));
+        tot += k < cn ? c : (c >> 2);
+    }
+    return tot;
+}
+
+// horizontal window sums of the pixel cost, clamped to the valid columns: hb[y][xi][d]
+__global__ __launch_bounds__(256) void k_sgbm_hcost(const int4* __restrict__ pf, int H, int W, int cn, int minD, int D, int h,
+                                                    int* __restrict__ hb)
+{
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)H * D) return;
+    const int d = (int)(t % D), y = (int)(t / D);
+    const int x0 = minD + D, Wv = W - x0, off = minD + d;
+    const size_t plane = (size_t)H * W, row = (size_t)y * W;
+    auto pix = [&](int xi) {
+        xi = min(max(xi, 0), Wv - 1);
+        const int x = x0 + xi;
+        return sgbm_pix(pf, plane, cn, row + x, row + (x - off));
+    };
+    int sum = 0;
+    for (int i = -h; i <= h; i++) sum += pix(i);
+    int* out = hb + (size_t)y * Wv * D + d;
+    for (int xi = 0; xi < Wv; xi++) {
+        out[(size_t)xi * D] = sum;
+        sum += pix(xi + h + 1) - pix(xi - h);
+    }
+}
+
+__device__ __forceinline__ int wave_min(int v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
+    return v;
+}
+
+// One path step over the candidates of a wavefront (d = k * 64 + lane): Lr holds L(p - r, d) on entry and L(p, d) on exit, m the
+// minimum over d of the predecessor on entry and of the new L on exit.  nb: the LDS row of this step (2 x D ints, parity `par`).
+template <int NPL>
+__device__ __forceinline__ void sgbm_step(int (&Lr)[NPL], const int (&c)[NPL], int& m, int* nb, int D, int P1, int P2)
+{
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < NPL; k++) {
+        const int d = k * 64 + lane;
+        if (d < D) nb[d] = Lr[k];
+    }
+    __syncthreads();
+    int mn = SGBM_BIG;
+#pragma unroll
+    for (int k = 0; k < NPL; k++) {
+        const int d = k * 64 + lane;
+        if (d < D) {
+            int best = min(Lr[k], m + P2);
+            if (d > 0) best = min(best, nb[d - 1] + P1);
+            if (d < D - 1) best = min(best, nb[d + 1] + P1);
+            Lr[k] = c[k] + best - m;
+            mn = min(mn, Lr[k]);
+        }
+    }
+    m = wave_min(mn);
+}
+
+// vertical window sums of hb (C, written out for the row paths) and the top->bottom path (L_tb): one wavefront per column
+template <int NPL>
+__global__ __launch_bounds__(64) void k_sgbm_top(const int* __restrict__ hb, int H, int Wv, int D, int h, int P1, int P2,
+                                                 int* __restrict__ C, int* __restrict__ T)
+{
+    extern __shared__ int lds[];  // [2][D]
+    const int xi = blockIdx.x, lane = threadIdx.x;
+    const size_t rs = (size_t)Wv * D;  // row stride of the volumes
+    const size_t base = (size_t)xi * D;
+    int vs[NPL], Lr[NPL];
+#pragma unroll
+    for (int k = 0; k < NPL; k++) {
+        const int d = k * 64 + lane;
+        vs[k] = 0;
+        Lr[k] = 0;
+        if (d < D)
+            for (int j = -h; j <= h; j++) vs[k] += hb[(size_t)min(max(j, 0), H - 1) * rs + base + d];
+    }
+    int m = 0;
+    for (int y = 0; y < H; y++) {
+        sgbm_step<NPL>(Lr, vs, m, lds + (y & 1) * D, D, P1, P2);
+        const int ya = min(y + h + 1, H - 1), yr = max(y - h, 0);
+#pragma unroll
+        for (int k = 0; k < NPL; k++) {
+            const int d = k * 64 + lane;
+            if (d < D) {
+                const size_t o = (size_t)y * rs + base + d;
+                C[o] = vs[k];
+                T[o] = Lr[k];
+                vs[k] += hb[(size_t)ya * rs + base + d] - hb[(size_t)yr * rs + base + d];
+            }
+        }
+    }
+}
+
+// left->right then right->left along one row; the second pass completes S, picks the winner (smallest d on a tie), applies the
+// uniqueness rule and the subpixel fit, and files (minS, x) under the matching right-image column x2 for the left-right rule.
+// disp_raw[y][x] (x >= x0): the scaled disparity or INVALID; key[y][x2]: min over the pixels that chose x2 of (minS << 32 | x).
+template <int NPL>
+__global__ __launch_bounds__(64) void k_sgbm_row(const int* __restrict__ C, int* __restrict__ T, int H, int W, int minD, int D,
+                                                 int P1, int P2, int U, int keep_S, int* __restrict__ disp_raw,
+                                                 unsigned long long* __restrict__ key)
+{
+    extern __shared__ int lds[];  // [2][D] path neighbours, [2][D] S row
+    const int y = blockIdx.x, lane = threadIdx.x;
+    const int x0 = minD + D, Wv = W - x0;
+    const int INVALID = 16 * (minD - 1);
+    const size_t rowbase = (size_t)y * Wv * D;
+    int Lr[NPL], c[NPL];
+    int m = 0;
+#pragma unroll
+    for (int k = 0; k < NPL; k++) Lr[k] = 0;
+    for (int xi = 0; xi < Wv; xi++) {
+        const size_t o = rowbase + (size_t)xi * D;
+#pragma unroll
+        for (int k = 0; k < NPL; k++) {
+            const int d = k * 64 + lane;
+            c[k] = d < D ? C[o + d] : 0;
+        }
+        sgbm_step<NPL>(Lr, c, m, lds + (xi & 1) * D, D, P1, P2);
+#pragma unroll
+        for (int k = 0; k < NPL; k++) {
+            const int d = k * 64 + lane;
+            if (d < D) T[o + d] += Lr[k];
+        }
+    }
+    m = 0;
+#pragma unroll
+    for (int k = 0; k < NPL; k++) Lr[k] = 0;
+    int* srow = lds + 2 * D;
+    for (int xi = Wv - 1; xi >= 0; xi--) {
+        const size_t o = rowbase + (size_t)xi * D;
+#pragma unroll
+        for (int k = 0; k < NPL; k++) {
+            const int d = k * 64 + lane;
+            c[k] = d < D ? C[o + d] : 0;
+        }
+        const int par = xi & 1;
+        sgbm_step<NPL>(Lr, c, m, lds + par * D, D, P1, P2);
+        int s[NPL];
+        int mn = 0x7fffffff, bd = 0x7fffffff;
+#pragma unroll
+        for (int k = 0; k < NPL; k++) {
+            const int d = k * 64 + lane;
+            s[k] = 0x7fffffff;
+            if (d < D) {
+                s[k] = T[o + d] + Lr[k];
+                if (keep_S) T[o + d] = s[k];  // only the volume reads S back
+                srow[par * D + d] = s[k];
+                if (s[k] < mn) { mn = s[k]; bd = d; }
+            }
+        }
+        // (minS, smallest d) over the wavefront
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const int om = __shfl_xor(mn, off), od = __shfl_xor(bd, off);
+            if (om < mn || (om == mn && od < bd)) { mn = om; bd = od; }
+        }
+        bool bad = false;
+#pragma unroll
+        for (int k = 0; k < NPL; k++) {
+            const int d = k * 64 + lane;
+            if (d < D && abs(d - bd) > 1 && (long long)s[k] * (100 - U) < (long long)mn * 100) bad = true;
+        }
+        bad = __ballot(bad) != 0;
+        __syncthreads();  // srow of this step is complete (the next write to it is two steps away, behind sgbm_step's barrier)
+        if (lane == 0) {
+            const int x = x0 + xi;
+            int v = INVALID;
+            if (!bad) {
+                v = 16 * bd;
+                if (bd > 0 && bd < D - 1) {
+                    const long long sm = srow[par * D + bd - 1], sp = srow[par * D + bd + 1];
+                    const long long den = max(sm + sp - 2ll * mn, 1ll);
+                    v += (int)((16 * (sm - sp) + den) / (2 * den));  // C division: truncation toward zero
+                }
+                v += 16 * minD;
+                const int x2 = x - (bd + minD);  // >= 1: x >= minD + D > bd + minD
+                atomicMin(&key[(size_t)y * W + x2], ((unsigned long long)(unsigned)mn << 32) | (unsigned)x);
+            }
+            disp_raw[(size_t)y * W + x] = v;
+        }
+    }
+}
+
+// step 6: a pixel is invalidated only when both of its neighbouring integer disparities disagree with the right-view winners
+__global__ __launch_bounds__(256) void k_sgbm_lr(const int* __restrict__ disp_raw, const unsigned long long* __restrict__ key, int H,
+                                                 int W, int minD, int D, int M, short* __restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)H * W) return;
+    const int x = (int)(i % W);
+    const size_t row = i - x;
+    const int INVALID = 16 * (minD - 1);
+    if (x < minD + D) {
+        out[i] = (short)INVALID;
+        return;
+    }
+    const int d1 = disp_raw[i];
+    if (d1 == INVALID) {
+        out[i] = (short)INVALID;
+        return;
+    }
+    auto disagrees = [&](int t) {
+        const int xx = x - t;
+        if (xx < 0 || xx >= W) return false;
+        const unsigned long long kv = key[row + xx];
+        const int d2 = kv == ~0ull ? minD - 1 : (int)(unsigned)(kv & 0xffffffffu) - xx;
+        return d2 >= minD && abs(d2 - t) > M;
+    };
+    const int lo = d1 >> 4, hi = (d1 + 15) >> 4;
+    out[i] = (short)(disagrees(lo) && disagrees(hi) ? INVALID : d1);
+}
+
+__global__ __launch_bounds__(256) void k_fill_s16(short* __restrict__ out, size_t n, short v)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = v;
+}
+
+// S volume [D][H][W] f32, 0 outside the valid columns (exact: the host checks the bound against 2^24)
+__global__ __launch_bounds__(256) void k_sgbm_volume(const int* __restrict__ S, int H, int W, int minD, int D, float* __restrict__ vol)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t plane = (size_t)H * W;
+    if (i >= plane * D) return;
+    const int d = (int)(i / plane);
+    const size_t p = i % plane;
+    const int x = (int)(p % W), y = (int)(p / W);
+    const int x0 = minD + D, Wv = W - x0;
+    vol[i] = x < x0 ? 0.0f : (float)S[((size_t)y * Wv + (x - x0)) * D + d];
+}
+
+// medianBlur(3) of an int16 map, replicated borders
+__global__ __launch_bounds__(256) void k_median3_s16(const short* __restrict__ in, int H, int W, short* __restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)H * W) return;
+    const int x = (int)(i % W), y = (int)(i / W);
+    int v[9];
+    int n = 0;
+    for (int dy = -1; dy <= 1; dy++)
+        for (int dx = -1; dx <= 1; dx++)
+            v[n++] = in[(size_t)min(max(y + dy, 0), H - 1) * W + min(max(x + dx, 0), W - 1)];
+#pragma unroll
+    for (int a = 0; a < 5; a++)  // partial selection sort: v[4] ends as the 5th smallest
+#pragma unroll
+        for (int b = a + 1; b < 9; b++) {
+            const int lo = min(v[a], v[b]), hi = max(v[a], v[b]);
+            v[a] = lo;
+            v[b] = hi;
+        }
+    out[i] = (short)v[4];
+}
+
+// ---- filterSpeckles: union-find over the whole frame.  parent[i] <= i always (a root is linked under the smaller root), so every
+// value a parent ever holds is a member of the same set; path halving during the union phase is therefore benign under races.
+__device__ __forceinline__ int spk_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void spk_store(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__device__ int spk_find_halving(int* parent, int x)
+{
+    while (true) {
+        const int p = spk_load(parent + x);
+        if (p == x) return x;
+        const int gp = spk_load(parent + p);
+        if (gp != p) spk_store(parent + x, gp);
+        x = gp;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_spk_init(const short* __restrict__ img, size_t n, int new_val, int* __restrict__ parent,
+                                                  int* __restrict__ size)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    parent[i] = img[i] == new_val ? -1 : (int)i;
+    size[i] = 0;
+}
+
+__device__ void spk_union(int* parent, int a, int b)
+{
+    while (true) {
+        a = spk_find_halving(parent, a);
+        b = spk_find_halving(parent, b);
+        if (a == b) return;
+        if (a < b) { const int t = a; a = b; b = t; }
+        if (atomicCAS(parent + a, a, b) == a) return;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_spk_union(const short* __restrict__ img, int H, int W, int new_val, int max_diff,
+                                                   int* __restrict__ parent)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)H * W) return;
+    const int v = img[i];
+    if (v == new_val) return;
+    const int x = (int)(i % W), y = (int)(i / W);
+    if (x + 1 < W) {
+        const int u = img[i + 1];
+        if (u != new_val && abs(u - v) <= max_diff) spk_union(parent, (int)i, (int)i + 1);
+    }
+    if (y + 1 < H) {
+        const int u = img[i + W];
+        if (u != new_val && abs(u - v) <= max_diff) spk_union(parent, (int)i, (int)(i + W));
+    }
+}
+
+// one round of pointer jumping, parent[i] = parent[parent[i]]: every value a parent takes is an ancestor, so concurrent rounds only
+// shorten the chains faster; ceil(log2(n)) rounds leave every pixel one link below its root whatever chains the union phase left
+// (a 1-pixel path of a component that snakes through the frame can be hundreds of thousands of links deep before)
+__global__ __launch_bounds__(256) void k_spk_jump(size_t n, int* __restrict__ parent)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int p = spk_load(parent + i);
+    if (p < 0) return;
+    const int gp = spk_load(parent + p);
+    if (gp != p) spk_store(parent + i, gp);
+}
+
+// root of every pixel (read-only walk: a concurrent flattening store only ever replaces a parent by its root) + component sizes.
+// One atomicAdd per run of equal roots within a wavefront's 64 consecutive pixels, not per pixel: a large component would
+// otherwise serialise a million atomics on its root's counter (19.7 ms at 1080p measured in the per-pixel form).
+__global__ __launch_bounds__(256) void k_spk_flatten(size_t n, int* __restrict__ parent, int* __restrict__ size)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    int x = i < n ? spk_load(parent + i) : -1;
+    if (x >= 0) {
+        while (true) {
+            const int p = spk_load(parent + x);
+            if (p == x) break;
+            x = p;
+        }
+        spk_store(parent + i, x);
+    }
+    const int prev = __shfl_up(x, 1);
+    const bool head = x >= 0 && (lane == 0 || prev != x);
+    const unsigned long long ends = __ballot(lane == 0 || prev != x);  // every lane that starts a run (valid or not)
+    if (head) {
+        const unsigned long long above = lane == 63 ? 0ull : ends & (~0ull << (lane + 1));
+        const int next = above ? __ffsll((long long)above) - 1 : 64;
+        atomicAdd(size + x, next - lane);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_spk_apply(short* __restrict__ img, size_t n, int new_val, int max_size,
+                                                   const int* __restrict__ parent, const int* __restrict__ size)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int r = parent[i];
+    if (r >= 0 && size[r] <= max_size) img[i] = (short)new_val;
+}
+
+// convertTo(CV_8U, 1/16): round half to even, saturate -- as f32 for the selector's CV_32F result
+__global__ __launch_bounds__(256) void k_disp16_to_u8f(const short* __restrict__ in, size_t n, float* __restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = fminf(fmaxf(rintf((float)in[i] * 0.0625f), 0.0f), 255.0f);
+}
+
+inline unsigned blocks(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
+
+template <int NPL>
+int launch_paths(hipStream_t s, const int* hb, int H, int W, int minD, int D, int h, int P1, int P2, int U, int keep_S, int* C, int* T,
+                 int* disp_raw, unsigned long long* key)
+{
+    const int Wv = W - (minD + D);
+    hipLaunchKernelGGL(k_sgbm_top<NPL>, dim3(Wv), dim3(64), 2 * D * sizeof(int), s, hb, H, Wv, D, h, P1, P2, C, T);
+    ASW_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_sgbm_row<NPL>, dim3(H), dim3(64), 4 * D * sizeof(int), s, C, T, H, W, minD, D, P1, P2, U, keep_S, disp_raw,
+                       key);
+    ASW_HIP_TRY(hipGetLastError());
+    return ASW_OK;
+}
+
+}  // namespace
+
+size_t sgbm_scratch_bytes(int H, int W, int cn, int minD, int D)
+{
+    const size_t Wv = W > minD + D ? (size_t)(W - minD - D) : 0;
+    const size_t plane = (size_t)H * W;
+    // hb, C, T volumes | prefiltered planes | disp2 keys | speckle scratch | raw disparities | left-right checked map
+    return 3 * ((size_t)H * Wv * D * 4) + plane * 64 * cn + plane * 8 + plane * 8 + plane * 4 + (plane * 2 + 15) / 16 * 16;
+}
+
+int launch_sgbm(hipStream_t s, const SgbmLaunch& a)
+{
+    const int H = a.H, W = a.W, D = a.D, minD = a.minD;
+    const size_t plane = (size_t)H * W;
+    const int INVALID = 16 * (minD - 1);
+    if (W <= minD + D) {  // no valid column: every pixel INVALID, nothing to filter
+        hipLaunchKernelGGL(k_fill_s16, dim3(blocks(plane, 256)), dim3(256), 0, s, a.disp16, plane, (short)INVALID);
+        ASW_HIP_TRY(hipGetLastError());
+        if (a.vol) ASW_HIP_TRY(hipMemsetAsync(a.vol, 0, plane * D * sizeof(float), s));
+        if (a.ev_agg0) ASW_HIP_TRY(hipEventRecord(a.ev_agg0, s));
+        if (a.ev_agg1) ASW_HIP_TRY(hipEventRecord(a.ev_agg1, s));
+        return ASW_OK;
+    }
+    const int Wv = W - (minD + D);
+    const size_t vol = (size_t)H * Wv * D;
+    // carve the scratch in sgbm_scratch_bytes' order (every region starts 8-byte aligned)
+    char* p = (char*)a.scratch;
+    int* hb = (int*)p; p += vol * 4;
+    int* C = (int*)p; p += vol * 4;
+    int* T = (int*)p; p += vol * 4;
+    int4* pf = (int4*)p; p += plane * 64 * a.cn;
+    unsigned long long* key = (unsigned long long*)p; p += plane * 8;
+    int* spk = (int*)p; p += plane * 8;
+    int* disp_raw = (int*)p; p += plane * 4;
+    short* lr = (short*)p;
+    hipLaunchKernelGGL(k_sgbm_prefilter, dim3(blocks(plane, 256)), dim3(256), 0, s, a.L, a.R, H, W, a.cn, a.ftzero, pf);
+    ASW_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_sgbm_hcost, dim3(blocks((size_t)H * D, 256)), dim3(256), 0, s, pf, H, W, a.cn, minD, D, a.w / 2, hb);
+    ASW_HIP_TRY(hipGetLastError());
+    ASW_HIP_TRY(hipMemsetAsync(key, 0xff, plane * 8, s));
+    const int npl = (D + 63) / 64;
+    if (a.ev_agg0) ASW_HIP_TRY(hipEventRecord(a.ev_agg0, s));
+    if (npl <= 1) ASW_TRY(launch_paths<1>(s, hb, H, W, minD, D, a.w / 2, a.P1, a.P2, a.U, a.vol != nullptr, C, T, disp_raw, key));
+    else if (npl <= 2) ASW_TRY(launch_paths<2>(s, hb, H, W, minD, D, a.w / 2, a.P1, a.P2, a.U, a.vol != nullptr, C, T, disp_raw, key));
+    else if (npl <= 4) ASW_TRY(launch_paths<4>(s, hb, H, W, minD, D, a.w / 2, a.P1, a.P2, a.U, a.vol != nullptr, C, T, disp_raw, key));
+    else if (npl <= 8) ASW_TRY(launch_paths<8>(s, hb, H, W, minD, D, a.w / 2, a.P1, a.P2, a.U, a.vol != nullptr, C, T, disp_raw, key));
+    else if (npl <= 16) ASW_TRY(launch_paths<16>(s, hb, H, W, minD, D, a.w / 2, a.P1, a.P2, a.U, a.vol != nullptr, C, T, disp_raw, key));
+    else return ASW_ERR_BAD_ARGUMENT;
+    if (a.ev_agg1) ASW_HIP_TRY(hipEventRecord(a.ev_agg1, s));
+    if (a.vol) {
+        hipLaunchKernelGGL(k_sgbm_volume, dim3(blocks(plane * D, 256)), dim3(256), 0, s, T, H, W, minD, D, a.vol);
+        ASW_HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_sgbm_lr, dim3(blocks(plane, 256)), dim3(256), 0, s, disp_raw, key, H, W, minD, D, a.M, lr);
+    ASW_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_median3_s16, dim3(blocks(plane, 256)), dim3(256), 0, s, lr, H, W, a.disp16);
+    ASW_HIP_TRY(hipGetLastError());
+    if (a.speckle_window > 0)
+        ASW_TRY(launch_filter_speckles(s, a.disp16, H, W, INVALID, a.speckle_window, 16 * a.speckle_range, spk));
+    return ASW_OK;
+}
+
+int launch_filter_speckles(hipStream_t s, short* img, int H, int W, int new_val, int max_size, int max_diff, int* scratch)
+{
+    const size_t n = (size_t)H * W;
+    int* parent = scratch;
+    int* size = scratch + n;
+    hipLaunchKernelGGL(k_spk_init, dim3(blocks(n, 256)), dim3(256), 0, s, img, n, new_val, parent, size);
+    ASW_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_spk_union, dim3(blocks(n, 256)), dim3(256), 0, s, img, H, W, new_val, max_diff, parent);
+    ASW_HIP_TRY(hipGetLastError());
+    for (size_t span = 1; span < n; span *= 2) {
+        hipLaunchKernelGGL(k_spk_jump, dim3(blocks(n, 256)), dim3(256), 0, s, n, parent);
+        ASW_HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_spk_flatten, dim3(blocks(n, 256)), dim3(256), 0, s, n, parent, size);
+    ASW_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_spk_apply, dim3(blocks(n, 256)), dim3(256), 0, s, img, n, new_val, max_size, parent, size);
+    ASW_HIP_TRY(hipGetLastError());
+    return ASW_OK;
+}
+
+int launch_disp16_to_u8f(hipStream_t s, const short* disp16, size_t n, float* out)
+{
+    hipLaunchKernelGGL(k_disp16_to_u8f, dim3(blocks(n, 256)), dim3(256), 0, s, disp16, n, out);
+    ASW_HIP_TRY(hipGetLastError());
+    return ASW_OK;
+}

@@ -139,6 +139,20 @@ inline void cost_volume(const MatT& l, const MatT& r, std::vector<MatT>& out, in
     }
 }
 
+// the selector's SGBM result (whole numbers 0..255 in a CV_32F map) as the CV_8U Mat convertTo(CV_8U, 1/16) gives the reference
+inline MatT f32_to_u8(const MatT& f)
+{
+    if (f.empty()) return MatT();
+    MatT u = make(f.rows, f.cols, ASW_8U, 1);
+    asw_image fi = view(f), ui = view(u);
+    for (int y = 0; y < f.rows; y++) {
+        const float* src = (const float*)((const uint8_t*)fi.data + (size_t)y * fi.step);
+        uint8_t* dst = (uint8_t*)ui.data + (size_t)y * ui.step;
+        for (int x = 0; x < f.cols; x++) dst[x] = (uint8_t)src[x];
+    }
+    return u;
+}
+
 }  // namespace detail
 }  // namespace asw
 
@@ -147,10 +161,26 @@ inline void cost_volume(const MatT& l, const MatT& r, std::vector<MatT>& out, in
 // ---------------------------------------------------------------------------------------------------
 typedef asw::detail::MatT AswMat;
 
-// M.h:91-92 / M.cpp:46-88
+// M.h:94 / aswMethods.cpp:158-194: StereoSGBM (MODE_SGBM_3WAY) with the reference's settings, CV_8U result.  The CV_Error cases
+// (numDisparity % 16 != 0, even winSize, an empty image) throw.
+inline void getDisparity_SGBM(AswMat srcLeft, AswMat srcRight, AswMat& disparityMap, int winSize = 15, int minDisparity = 0,
+                              int numDisparity = 64)
+{
+    if (srcLeft.empty() || srcRight.empty()) throw std::runtime_error("getDisparity_SGBM: one of the input images is empty");
+    AswMat d = asw::detail::aggregate(srcLeft, srcRight, [&](asw_ctx* c, asw_image* l, asw_image* r, asw_image* o) {
+        return asw_stereo_match(c, l, r, o, (int)DISPARITY_LEFT, (int)SGBM, winSize, minDisparity, numDisparity, nullptr, 0);
+    }, "getDisparity_SGBM");
+    disparityMap = asw::detail::f32_to_u8(d);
+}
+
+// M.h:91-92 / M.cpp:46-88 (SGBM: the CV_8U map of getDisparity_SGBM, as M.cpp:54-55; every other method CV_32F)
 inline void stereoMatching(AswMat srcLeft, AswMat srcRight, AswMat& disparityMap, DisparityType disparityType,
                            StereoMatchingAlgorithms algorithmType, int winSize = 15, int minDisparity = 0, int numDisparity = 64)
 {
+    if (algorithmType == SGBM) {
+        getDisparity_SGBM(srcLeft, srcRight, disparityMap, winSize, minDisparity, numDisparity);
+        return;
+    }
     AswMat d = asw::detail::aggregate(srcLeft, srcRight, [&](asw_ctx* c, asw_image* l, asw_image* r, asw_image* o) {
         return asw_stereo_match(c, l, r, o, (int)disparityType, (int)algorithmType, winSize, minDisparity, numDisparity, nullptr, 0);
     }, "stereoMatching");

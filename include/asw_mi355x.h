@@ -35,7 +35,7 @@ typedef enum asw_status {
     ASW_OK = 0,
     ASW_ERR_SIZE_MISMATCH = 1,      /* M.cpp:217-220, 313-316, 430-433: silent return          */
     ASW_ERR_EVEN_WINDOW = 2,        /* M.cpp:654-657, 1440-1443, 2458-2462, 3238-3241: Mat()  */
-    ASW_ERR_UNSUPPORTED_METHOD = 3, /* enum values 0 and 1 (BM, SGBM: OpenCV's own matchers) */
+    ASW_ERR_UNSUPPORTED_METHOD = 3, /* enum value 0 (BM); SGBM's CV_Error cases; asw_sgbm modes other than 3WAY */
     ASW_ERR_UNSUPPORTED_LAYOUT = 4, /* where the reference throws cv::Exception (SURVEY B-7)  */
     ASW_ERR_HIP = 5,                /* a HIP runtime call or kernel launch failed             */
     ASW_ERR_ALLOC = 6,
@@ -63,7 +63,7 @@ enum {
 };
 
 /* cv::Mat depth codes */
-enum { ASW_8U = 0, ASW_32F = 5 };
+enum { ASW_8U = 0, ASW_16S = 3, ASW_32F = 5 };
 
 /* The part of a cv::Mat header the path needs (M.h:91: cv::Mat srcLeft, srcRight, disparityMap) */
 typedef struct asw_image {
@@ -71,7 +71,7 @@ typedef struct asw_image {
     int rows;     /* cv::Mat::rows                              */
     int cols;     /* cv::Mat::cols                              */
     int channels; /* cv::Mat::channels()                        */
-    int depth;    /* ASW_8U or ASW_32F                          */
+    int depth;    /* ASW_8U, ASW_16S or ASW_32F                 */
     size_t step;  /* bytes per row (cv::Mat::step), >= cols*channels*elemsize */
 } asw_image;
 
@@ -115,7 +115,8 @@ int asw_stereo_match(asw_ctx* ctx, const asw_image* left, const asw_image* right
                      float* cost_volume_out, size_t cost_volume_floats);
 
 /* Planes of the cost volume `algorithm` produces for num_disparity candidates (what cost_volume_out must hold);
- * 0 for an algorithm the library does not serve. */
+ * 0 for an algorithm without a selector volume: BM (not served) and SGBM (a non-NULL cost_volume_out is refused with
+ * ASW_ERR_BAD_ARGUMENT; asw_sgbm returns its aggregated cost). */
 int asw_volume_planes(int algorithm, int num_disparity);
 
 /* ---- the same, split so that inputs can stay resident in HBM (bench / pipelines) ----
@@ -239,6 +240,27 @@ int asw_lr_check(asw_ctx* ctx, const float* disp_left, const float* disp_right, 
                  float invalid_value, float* out, int* n_invalid);
 /* cvtColor(COLOR_BGR2GRAY) as used at M.cpp:1031-1033 */
 int asw_bgr2gray(asw_ctx* ctx, const asw_image* bgr, uint8_t* gray);
+
+/* ---- semi-global block matching: StereoSGBM (OpenCV 4.1.0 stereosgbm.cpp, MODE_SGBM_3WAY) as DESIGN.md section 4.8 states it ----
+ * The selector's SGBM entry (getDisparity_SGBM, aswMethods.cpp:158-194) runs it with the reference's fixed settings: blockSize w =
+ * win > 0 ? win : 3, preFilterCap 10, P1 = 8*cn*w*w, P2 = 32*cn*w*w, uniquenessRatio 10, speckleWindowSize 175, speckleRange 32,
+ * disp12MaxDiff 200, and returns convertTo(CV_8U, 1/16) of the result as floats; numDisparity % 16 != 0 and an even win (CV_Error in
+ * the reference) give ASW_ERR_UNSUPPORTED_METHOD; disparity_type is ignored (the left-view map); it has no cost volume.
+ * asw_sgbm: StereoSGBM::create(min_disparity, num_disparities, block_size, p1, p2, disp12_max_diff, pre_filter_cap, uniqueness_ratio,
+ * speckle_window_size, speckle_range, mode) + compute().  disp16: ASW_16S, 1 channel (else ASW_ERR_UNSUPPORTED_LAYOUT, as for
+ * asw_filter_speckles), rows x cols: disparity x 16, invalid pixels 16 * (min_disparity - 1).  mode: 2 (MODE_SGBM_3WAY) only, else ASW_ERR_UNSUPPORTED_METHOD.  num_disparities: a positive multiple of
+ * 16, at most 1024; min_disparity >= 0; 16 * (min_disparity + num_disparities) <= 32767; 1 or 3 channels.  Parameters for which a sum
+ * could leave int32 (3 * (C_max + P2) >= 2^31, C_max = cn * (2 * ftzero + 63) * w^2) are refused with ASW_ERR_BAD_ARGUMENT.
+ * cost_volume_out (optional): the aggregated cost S of the three paths, f32 [num_disparities][rows][cols] (plane k <-> disparity
+ * min_disparity + k), 0 in the columns x < min_disparity + num_disparities; refused (ASW_ERR_BAD_ARGUMENT) when S could exceed 2^24
+ * (not exact in f32) or when cost_volume_floats is short. */
+int asw_sgbm(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp16, int min_disparity,
+             int num_disparities, int block_size, int p1, int p2, int disp12_max_diff, int pre_filter_cap,
+             int uniqueness_ratio, int speckle_window_size, int speckle_range, int mode, float* cost_volume_out,
+             size_t cost_volume_floats);
+/* cv::filterSpeckles, in place: 4-connected components of pixels != new_val whose neighbours differ by at most max_diff; every
+ * component of at most max_speckle_size pixels becomes new_val.  img: ASW_16S, 1 channel (ASW_8U: ASW_ERR_UNSUPPORTED_LAYOUT). */
+int asw_filter_speckles(asw_ctx* ctx, asw_image* img, int new_val, int max_speckle_size, int max_diff);
 
 /* ---- batch over frames and devices (frames are independent; no collective) ----
  * Frame i goes to device device_ids[i % n_devices]; one host thread + one context per device. */
