@@ -26,7 +26,8 @@ __all__ = [
     "computeAdaptiveWeight_geodesic", "getGeodesicDist", "getGuidedFilter", "computeAdaptiveWeight_GuidedF",
     "computeAdaptiveWeight_GuidedF_2", "computeAdaptiveWeight_WeightedMedian", "winnerTakeAll", "last_status",
     "stereoMatchingBatch", "computeAdaptiveWeight_BLO1", "computeAdaptiveWeight_direct8", "computeNCC", "computeNCC_costs",
-    "computeAdaptiveWeight_GuidedF_3", "getDisparity_SGBM", "sgbm", "filterSpeckles",
+    "computeAdaptiveWeight_GuidedF_3", "getDisparity_SGBM", "sgbm", "filterSpeckles", "getDisparity_BM", "stereoBM",
+    "PREFILTER_NORMALIZED_RESPONSE", "PREFILTER_XSOBEL",
     "AswError",
 ]
 
@@ -57,6 +58,7 @@ DISPARITY_RIGHT = DisparityType.DISPARITY_RIGHT
 OK, ERR_SIZE_MISMATCH, ERR_EVEN_WINDOW, ERR_UNSUPPORTED_METHOD, ERR_UNSUPPORTED_LAYOUT = 0, 1, 2, 3, 4
 ERR_HIP, ERR_ALLOC, ERR_BAD_ARGUMENT, ERR_NO_FRAME = 5, 6, 7, 8
 MODE_SGBM_3WAY = 2  # StereoSGBM::MODE_SGBM_3WAY, the one mode asw_sgbm serves
+PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL = 0, 1  # StereoBM::PREFILTER_*; asw_stereo_bm serves XSOBEL
 # statuses for which the reference returns silently / an empty Mat
 _SILENT = (ERR_SIZE_MISMATCH, ERR_EVEN_WINDOW)
 
@@ -267,6 +269,40 @@ class Context:
                                 disp12MaxDiff, preFilterCap, uniquenessRatio, speckleWindowSize, speckleRange, int(mode), pv,
                                 0 if vol is None else vol.size)
         self._strict(rc, "asw_sgbm")
+        return (disp, vol) if return_cost_volume else disp
+
+    # ---- block matching ----
+    def getDisparity_BM(self, srcLeft, srcRight, winSize=15, minDisparity=0, numDisparity=64):
+        """getDisparity_BM (M.h:93, aswMethods.cpp:100-146): StereoBM with the reference's settings -> uint8 map
+        (convertTo(CV_8U, 1/16)); 3-channel input is converted to gray first.  Where the reference raises CV_Error
+        (numDisparity % 16 != 0, even winSize, an empty image, a block size outside 5..min(H, W, 255)) AswError is raised with
+        status ERR_UNSUPPORTED_METHOD."""
+        li, la = _image(srcLeft)
+        ri, ra = _image(srcRight)
+        out = np.zeros(la.shape[:2], np.uint8)
+        oi, _ = _image(out)
+        rc = self._lib.asw_get_disparity_bm(self._h, C.byref(li), C.byref(ri), C.byref(oi), winSize, minDisparity, numDisparity)
+        self._strict(rc, "asw_get_disparity_bm")
+        return out
+
+    def stereoBM(self, left, right, minDisparity, numDisparities, blockSize, preFilterType=PREFILTER_XSOBEL, preFilterSize=9,
+                 preFilterCap=31, textureThreshold=10, uniquenessRatio=15, speckleWindowSize=0, speckleRange=0, disp12MaxDiff=-1,
+                 return_cost_volume=False):
+        """StereoBM::create + setters + compute() on 8-bit gray images: int16 disparity x 16 (FILTERED: 16 * (minDisparity - 1));
+        with return_cost_volume also the block SAD, float32 [numDisparities][H][W] (plane k <-> disparity minDisparity + k, NaN
+        where nothing is computed) (asw_stereo_bm)."""
+        li, la = _image(left)
+        ri, ra = _image(right)
+        disp = np.zeros(la.shape[:2], np.int16)
+        di, _ = _image(disp, 3)
+        vol, pv = None, None
+        if return_cost_volume:
+            vol = np.zeros((numDisparities,) + la.shape[:2], np.float32)
+            pv = vol.ctypes.data_as(C.c_void_p)
+        rc = self._lib.asw_stereo_bm(self._h, C.byref(li), C.byref(ri), C.byref(di), minDisparity, numDisparities, blockSize,
+                                     int(preFilterType), preFilterSize, preFilterCap, textureThreshold, uniquenessRatio,
+                                     speckleWindowSize, speckleRange, disp12MaxDiff, pv, 0 if vol is None else vol.size)
+        self._strict(rc, "asw_stereo_bm")
         return (disp, vol) if return_cost_volume else disp
 
     def filterSpeckles(self, img, newVal, maxSpeckleSize, maxDiff):
@@ -525,3 +561,5 @@ winnerTakeAll = _bind("winnerTakeAll")
 getDisparity_SGBM = _bind("getDisparity_SGBM")
 sgbm = _bind("sgbm")
 filterSpeckles = _bind("filterSpeckles")
+getDisparity_BM = _bind("getDisparity_BM")
+stereoBM = _bind("stereoBM")

@@ -21,7 +21,7 @@ ABI_SYMBOLS = [
     "asw_preprocess_pair", "asw_download_pair", "asw_download_disparity_u8",
     "asw_cost_ad", "asw_cost_tad", "asw_cost_sd", "asw_cost_similarity", "asw_cost_sad", "asw_cost_sad_d",
     "asw_guided_filter", "asw_geodesic_dist", "asw_wta", "asw_bgr2gray", "asw_lr_check", "asw_volume_planes",
-    "asw_stereo_match_batch", "asw_sgbm", "asw_filter_speckles",
+    "asw_stereo_match_batch", "asw_sgbm", "asw_filter_speckles", "asw_stereo_bm", "asw_get_disparity_bm",
 ]
 
 
@@ -103,5 +103,7 @@ def lib():
         l.asw_stereo_match_batch.argtypes = [I, IMG, IMG, IMG, I, I, I, I, I, I, C.POINTER(C.c_int)]
         l.asw_sgbm.argtypes = [P, IMG, IMG, IMG, I, I, I, I, I, I, I, I, I, I, I, P, C.c_size_t]
         l.asw_filter_speckles.argtypes = [P, IMG, I, I, I]
+        l.asw_stereo_bm.argtypes = [P, IMG, IMG, IMG, I, I, I, I, I, I, I, I, I, I, I, P, C.c_size_t]
+        l.asw_get_disparity_bm.argtypes = [P, IMG, IMG, IMG, I, I, I]
         _lib = l
     return _lib

@@ -575,3 +575,105 @@ extern "C" int asw_filter_speckles(asw_ctx* ctx, asw_image* img, int new_val, in
     ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ASW_OK;
 }
+
+// ---- block matching (StereoBM::compute with PREFILTER_XSOBEL) and the reference's getDisparity_BM ----
+static int bm_run_host(asw_ctx* ctx, BmLaunch& a, const uint8_t* dL, const uint8_t* dR, float* vol_dev)
+{
+    a.L = dL; a.R = dR;
+    a.vol = vol_dev;
+    a.ev_agg0 = ctx->ev[2]; a.ev_agg1 = ctx->ev[3];
+    ASW_TRY(launch_bm(ctx->stream, a));
+    return ASW_OK;
+}
+
+extern "C" int asw_stereo_bm(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp16, int min_disparity,
+                             int num_disparities, int block_size, int pre_filter_type, int pre_filter_size, int pre_filter_cap,
+                             int texture_threshold, int uniqueness_ratio, int speckle_window_size, int speckle_range,
+                             int disp12_max_diff, float* cost_volume_out, size_t cost_volume_floats)
+{
+    if (!ctx) return ASW_ERR_BAD_ARGUMENT;
+    ASW_TRY(check_pair(left, right));
+    if (left->channels != 1) return ASW_ERR_UNSUPPORTED_LAYOUT;  // StereoBM takes CV_8UC1 only
+    ASW_TRY(check_s16_image(disp16));
+    if (disp16->rows != left->rows || disp16->cols != left->cols) return ASW_ERR_BAD_ARGUMENT;
+    const int H = left->rows, W = left->cols;
+    BmParams p;
+    p.minD = min_disparity; p.numD = num_disparities; p.block_size = block_size; p.pre_filter_type = pre_filter_type;
+    p.pre_filter_size = pre_filter_size; p.pre_filter_cap = pre_filter_cap; p.texture_threshold = texture_threshold;
+    p.uniqueness_ratio = uniqueness_ratio; p.speckle_window_size = speckle_window_size; p.speckle_range = speckle_range;
+    p.disp12_max_diff = disp12_max_diff;
+    ASW_HIP_TRY(hipSetDevice(ctx->device));
+    BmLaunch a;
+    ASW_TRY(bm_prepare(ctx, p, H, W, &a));
+    const size_t plane = (size_t)H * W, vol_floats = plane * (size_t)num_disparities;
+    if (cost_volume_out && cost_volume_floats < vol_floats) return ASW_ERR_BAD_ARGUMENT;
+    Frame* f = &ctx->host_frame;
+    ASW_TRY(upload_pair_into(ctx, f, left, right));
+    f->invalidate_results();
+    DevBuf& vol = ctx->buf("bm_volume");
+    if (cost_volume_out) ASW_TRY(vol.ensure(vol_floats * sizeof(float)));
+    ASW_HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
+    ASW_TRY(bm_run_host(ctx, a, f->L.as<uint8_t>(), f->R.as<uint8_t>(), cost_volume_out ? vol.as<float>() : nullptr));
+    ASW_TRY(timed_finish(ctx));
+    ctx->timing.aggregate_launches = 1;
+    ASW_HIP_TRY(copy_rows(ctx, disp16->data, disp16->step, a.disp16, (size_t)W * sizeof(short), (size_t)W * sizeof(short), H,
+                          hipMemcpyDeviceToHost));
+    if (cost_volume_out)
+        ASW_HIP_TRY(hipMemcpyAsync(cost_volume_out, vol.p, vol_floats * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ASW_OK;
+}
+
+// getDisparity_BM (aswMethods.cpp:100-146): the CV_Error cases (numDisparity % 16 != 0, an even winSize, an empty image, and
+// compute's assertions on numDisparities and blockSize = winSize > 0 ? winSize : 9) give ASW_ERR_UNSUPPORTED_METHOD; a 3-channel
+// image is converted with cvtColor(BGR2GRAY) on the device (asw_set_gray_bits); StereoBM with the wrapper's settings, then
+// convertTo(CV_8U, 1/16).
+extern "C" int asw_get_disparity_bm(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp_u8, int win,
+                                    int min_disparity, int num_disparities)
+{
+    if (!ctx || !left || !right || !disp_u8) return ASW_ERR_BAD_ARGUMENT;
+    if (num_disparities % 16 != 0 || win % 2 == 0) return ASW_ERR_UNSUPPORTED_METHOD;
+    if (!left->data || !right->data || left->rows <= 0 || left->cols <= 0 || right->rows <= 0 || right->cols <= 0)
+        return ASW_ERR_UNSUPPORTED_METHOD;
+    ASW_TRY(check_pair(left, right));
+    const int cn = left->channels;
+    if (cn != 1 && cn != 3) return ASW_ERR_UNSUPPORTED_LAYOUT;
+    const int H = left->rows, W = left->cols;
+    const int w = win > 0 ? win : 9;
+    if (num_disparities <= 0 || w < 5 || w > 255 || w > std::min(H, W)) return ASW_ERR_UNSUPPORTED_METHOD;
+    if (!disp_u8->data || disp_u8->depth != ASW_8U || disp_u8->channels != 1) return ASW_ERR_UNSUPPORTED_LAYOUT;
+    if (disp_u8->rows != H || disp_u8->cols != W || disp_u8->step < (size_t)W) return ASW_ERR_BAD_ARGUMENT;
+    BmParams p;
+    p.minD = min_disparity; p.numD = num_disparities; p.block_size = w; p.pre_filter_type = 1; p.pre_filter_size = 9;
+    p.pre_filter_cap = 31; p.texture_threshold = 10; p.uniqueness_ratio = 15; p.speckle_window_size = 100; p.speckle_range = 32;
+    p.disp12_max_diff = 1;
+    ASW_HIP_TRY(hipSetDevice(ctx->device));
+    BmLaunch a;
+    ASW_TRY(bm_prepare(ctx, p, H, W, &a));
+    const size_t plane = (size_t)H * W;
+    Frame* f = &ctx->host_frame;
+    ASW_TRY(upload_pair_into(ctx, f, left, right));
+    f->invalidate_results();
+    DevBuf& u8 = ctx->buf("bm_u8");
+    ASW_TRY(u8.ensure(plane));
+    const uint8_t* dL = f->L.as<uint8_t>();
+    const uint8_t* dR = f->R.as<uint8_t>();
+    ASW_HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
+    if (cn == 3) {
+        DevBuf& gl = ctx->buf("grayL");
+        DevBuf& gr = ctx->buf("grayR");
+        ASW_TRY(gl.ensure(plane));
+        ASW_TRY(gr.ensure(plane));
+        ASW_TRY(launch_bgr2gray(ctx->stream, dL, H, W, gl.as<uint8_t>(), ctx->gray_bits));
+        ASW_TRY(launch_bgr2gray(ctx->stream, dR, H, W, gr.as<uint8_t>(), ctx->gray_bits));
+        dL = gl.as<uint8_t>();
+        dR = gr.as<uint8_t>();
+    }
+    ASW_TRY(bm_run_host(ctx, a, dL, dR, nullptr));
+    ASW_TRY(launch_disp16_to_u8(ctx->stream, a.disp16, plane, u8.as<uint8_t>()));
+    ASW_TRY(timed_finish(ctx));
+    ctx->timing.aggregate_launches = 1;
+    ASW_HIP_TRY(copy_rows(ctx, disp_u8->data, disp_u8->step, u8.p, (size_t)W, (size_t)W, H, hipMemcpyDeviceToHost));
+    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ASW_OK;
+}

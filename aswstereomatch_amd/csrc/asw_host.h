@@ -43,6 +43,13 @@ struct SgbmParams {
     int minD, numD, block_size, P1, P2, disp12_max_diff, pre_filter_cap, uniqueness_ratio, speckle_window_size, speckle_range, mode;
 };
 int sgbm_prepare(asw_ctx* ctx, const SgbmParams& p, int H, int W, int cn, bool want_volume, SgbmLaunch* out);
+// StereoBM parameters as StereoBM::create + its setters take them; bm_prepare validates them (step 0) and
+// sizes the scratch
+struct BmParams {
+    int minD, numD, block_size, pre_filter_type, pre_filter_size, pre_filter_cap, texture_threshold, uniqueness_ratio,
+        speckle_window_size, speckle_range, disp12_max_diff;
+};
+int bm_prepare(asw_ctx* ctx, const BmParams& p, int H, int W, BmLaunch* out);
 int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp, bool keep_volume, bool sync = true);
 int match_host(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp, int algorithm,
                       const MatchParams& mp, float* cost_volume_out, size_t cost_volume_floats);

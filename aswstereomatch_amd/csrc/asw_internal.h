@@ -283,3 +283,20 @@ int launch_sgbm(hipStream_t s, const SgbmLaunch& a);
 int launch_filter_speckles(hipStream_t s, short* img, int H, int W, int new_val, int max_size, int max_diff,
                            int* scratch /* 2 * H * W ints */);
 int launch_disp16_to_u8f(hipStream_t s, const short* disp16, size_t n, float* out);
+
+// ---- block matching (k_bm.hip): StereoBM PREFILTER_XSOBEL + validateDisparity + filterSpeckles, DESIGN.md section 4.9 ----
+struct BmLaunch {
+    const uint8_t* L;  // dense 8U gray images
+    const uint8_t* R;
+    int H, W;
+    int minD, D;       // D: a multiple of 16, at most 1024
+    int w, cap, texture, U, M;  // blockSize, preFilterCap, textureThreshold, uniquenessRatio, disp12MaxDiff (< 0: no step 6)
+    int speckle_window, speckle_range;  // step 7 runs when range >= 0 and window > 0 (range unscaled)
+    void* scratch;     // bm_scratch_bytes()
+    short* disp16;     // out [H][W], scaled by 16, FILTERED = 16 * (minD - 1)
+    float* vol;        // optional SAD [D][H][W] (plane p <-> disparity minD + p), NaN where nothing is computed
+    hipEvent_t ev_agg0 = nullptr, ev_agg1 = nullptr;  // optional: recorded around k_bm_match (asw_timing::aggregate_ms)
+};
+size_t bm_scratch_bytes(int H, int W);
+int launch_bm(hipStream_t s, const BmLaunch& a);
+int launch_disp16_to_u8(hipStream_t s, const short* disp16, size_t n, uint8_t* out);

@@ -756,6 +756,38 @@ static int run_sgbm(asw_ctx* ctx, Frame* f, const MatchParams& mp)
     return ASW_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// block matching: StereoBM with PREFILTER_XSOBEL, behind asw_stereo_bm and asw_get_disparity_bm.  The
+// selector's BM value (enum 0) is not routed here: it still returns ASW_ERR_UNSUPPORTED_METHOD.
+// ------------------------------------------------------------------------------------------
+int bm_prepare(asw_ctx* ctx, const BmParams& p, int H, int W, BmLaunch* out)
+{
+    if (p.pre_filter_type == 0) return ASW_ERR_UNSUPPORTED_METHOD;  // PREFILTER_NORMALIZED_RESPONSE is not served
+    if (p.pre_filter_type != 1) return ASW_ERR_BAD_ARGUMENT;
+    // StereoBM::compute's assertions (step 0)
+    if (p.pre_filter_size < 5 || p.pre_filter_size > 255 || p.pre_filter_size % 2 == 0) return ASW_ERR_BAD_ARGUMENT;
+    if (p.pre_filter_cap < 1 || p.pre_filter_cap > 63) return ASW_ERR_BAD_ARGUMENT;
+    if (p.block_size < 5 || p.block_size > 255 || p.block_size % 2 == 0 || p.block_size > std::min(H, W)) return ASW_ERR_BAD_ARGUMENT;
+    if (p.numD <= 0 || p.numD % 16 != 0) return ASW_ERR_BAD_ARGUMENT;
+    if (p.texture_threshold < 0 || p.uniqueness_ratio < 0) return ASW_ERR_BAD_ARGUMENT;
+    // what this library serves: minD >= 0, up to 1024 candidates, an int16 map, int pixel indices in the speckle filter
+    if (p.minD < 0 || p.numD > 1024) return ASW_ERR_BAD_ARGUMENT;
+    if (16 * ((long long)p.minD + p.numD) > 32767) return ASW_ERR_BAD_ARGUMENT;
+    if ((size_t)H * W >= ((size_t)1 << 31)) return ASW_ERR_BAD_ARGUMENT;
+    BmLaunch a{};
+    a.H = H; a.W = W; a.minD = p.minD; a.D = p.numD; a.w = p.block_size; a.cap = p.pre_filter_cap;
+    a.texture = p.texture_threshold; a.U = p.uniqueness_ratio; a.M = p.disp12_max_diff;
+    a.speckle_window = p.speckle_window_size; a.speckle_range = p.speckle_range;
+    DevBuf& scratch = ctx->buf("bm_scratch");
+    DevBuf& d16 = ctx->buf("bm_disp16");
+    ASW_TRY(scratch.ensure(bm_scratch_bytes(H, W)));
+    ASW_TRY(d16.ensure((size_t)H * W * sizeof(short)));
+    a.scratch = scratch.p;
+    a.disp16 = d16.as<short>();
+    *out = a;
+    return ASW_OK;
+}
+
 int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp, bool keep_volume, bool sync)
 {
     f->invalidate_results();  // whatever the slot's disparity / volume were, they are not this call's

@@ -173,6 +173,20 @@ inline void getDisparity_SGBM(AswMat srcLeft, AswMat srcRight, AswMat& disparity
     disparityMap = asw::detail::f32_to_u8(d);
 }
 
+// M.h:93 / aswMethods.cpp:100-146: StereoBM (PREFILTER_XSOBEL) with the reference's settings, CV_8U result; a 3-channel image is
+// converted to gray first.  The CV_Error cases (numDisparity % 16 != 0, even winSize, an empty image, a block size outside
+// 5..min(rows, cols, 255)) throw, and so does every other failure.  stereoMatching(..., BM, ...) is not routed here.
+inline void getDisparity_BM(AswMat srcLeft, AswMat srcRight, AswMat& disparityMap, int winSize = 15, int minDisparity = 0,
+                            int numDisparity = 64)
+{
+    if (srcLeft.empty() || srcRight.empty()) throw std::runtime_error("getDisparity_BM: one of the input images is empty");
+    AswMat d = asw::detail::make(srcLeft.rows, srcLeft.cols, ASW_8U, 1);
+    asw_image li = asw::detail::view(srcLeft), ri = asw::detail::view(srcRight), di = asw::detail::view(d);
+    const int rc = asw_get_disparity_bm(asw::detail::context(), &li, &ri, &di, winSize, minDisparity, numDisparity);
+    if (rc != ASW_OK) throw std::runtime_error(std::string("getDisparity_BM: ") + asw_status_string(rc));
+    disparityMap = d;
+}
+
 // M.h:91-92 / M.cpp:46-88 (SGBM: the CV_8U map of getDisparity_SGBM, as M.cpp:54-55; every other method CV_32F)
 inline void stereoMatching(AswMat srcLeft, AswMat srcRight, AswMat& disparityMap, DisparityType disparityType,
                            StereoMatchingAlgorithms algorithmType, int winSize = 15, int minDisparity = 0, int numDisparity = 64)

@@ -35,7 +35,7 @@ typedef enum asw_status {
     ASW_OK = 0,
     ASW_ERR_SIZE_MISMATCH = 1,      /* M.cpp:217-220, 313-316, 430-433: silent return          */
     ASW_ERR_EVEN_WINDOW = 2,        /* M.cpp:654-657, 1440-1443, 2458-2462, 3238-3241: Mat()  */
-    ASW_ERR_UNSUPPORTED_METHOD = 3, /* enum value 0 (BM); SGBM's CV_Error cases; asw_sgbm modes other than 3WAY */
+    ASW_ERR_UNSUPPORTED_METHOD = 3, /* enum value 0 (BM); the CV_Error cases of SGBM / BM; unserved modes / prefilters */
     ASW_ERR_UNSUPPORTED_LAYOUT = 4, /* where the reference throws cv::Exception (SURVEY B-7)  */
     ASW_ERR_HIP = 5,                /* a HIP runtime call or kernel launch failed             */
     ASW_ERR_ALLOC = 6,
@@ -261,6 +261,30 @@ int asw_sgbm(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_im
 /* cv::filterSpeckles, in place: 4-connected components of pixels != new_val whose neighbours differ by at most max_diff; every
  * component of at most max_speckle_size pixels becomes new_val.  img: ASW_16S, 1 channel (ASW_8U: ASW_ERR_UNSUPPORTED_LAYOUT). */
 int asw_filter_speckles(asw_ctx* ctx, asw_image* img, int new_val, int max_speckle_size, int max_diff);
+
+/* ---- block matching: StereoBM (OpenCV 4.1.0 stereobm.cpp, PREFILTER_XSOBEL) as DESIGN.md section 4.9 states it ----
+ * asw_stereo_bm: StereoBM::create + setters + compute().  left / right: ASW_8U, 1 channel (else ASW_ERR_UNSUPPORTED_LAYOUT, as
+ * StereoBM); disp16: ASW_16S, 1 channel, rows x cols: disparity x 16, FILTERED = 16 * (min_disparity - 1).  Every image's step
+ * is honoured.  pre_filter_type: ASW_PREFILTER_XSOBEL only (ASW_PREFILTER_NORMALIZED_RESPONSE: ASW_ERR_UNSUPPORTED_METHOD).
+ * StereoBM::compute's assertions give ASW_ERR_BAD_ARGUMENT: pre_filter_size odd in 5..255, pre_filter_cap in 1..63, block_size odd
+ * in 5..255 and <= min(rows, cols), num_disparities a positive multiple of 16, texture_threshold >= 0, uniqueness_ratio >= 0; so do
+ * what the library does not serve: min_disparity < 0, num_disparities > 1024, 16 * (min_disparity + num_disparities) > 32767.
+ * disp12_max_diff < 0 skips validateDisparity; speckles are filtered when speckle_range >= 0 and speckle_window_size > 0 (range
+ * in whole disparities, unscaled).  cost_volume_out (optional): the block SAD, f32 [num_disparities][rows][cols] (plane k <->
+ * disparity min_disparity + k), with values on the rows [w/2, rows - w/2) at the columns [min_disparity + num_disparities - 1,
+ * cols) and NaN elsewhere; a short buffer is refused (ASW_ERR_BAD_ARGUMENT) before anything is written.
+ * asw_get_disparity_bm: the reference's getDisparity_BM (aswMethods.h:93, aswMethods.cpp:100-146): 1- or 3-channel input (BGR2GRAY
+ * on the device, asw_set_gray_bits), blockSize win > 0 ? win : 9, preFilterCap 31, textureThreshold 10, uniquenessRatio 15,
+ * disp12MaxDiff 1, speckleWindowSize 100, speckleRange 32; disp_u8: ASW_8U, 1 channel, convertTo(CV_8U, 1/16) of the result.
+ * Its CV_Error cases give ASW_ERR_UNSUPPORTED_METHOD: num_disparities % 16 != 0 or <= 0, an even win, an empty image, a blockSize
+ * outside 5..min(rows, cols, 255).  The selector's BM value (ASW_ALG_BM) is not routed here. */
+enum { ASW_PREFILTER_NORMALIZED_RESPONSE = 0, ASW_PREFILTER_XSOBEL = 1 };
+int asw_stereo_bm(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp16, int min_disparity,
+                  int num_disparities, int block_size, int pre_filter_type, int pre_filter_size, int pre_filter_cap,
+                  int texture_threshold, int uniqueness_ratio, int speckle_window_size, int speckle_range, int disp12_max_diff,
+                  float* cost_volume_out, size_t cost_volume_floats);
+int asw_get_disparity_bm(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp_u8, int win,
+                         int min_disparity, int num_disparities);
 
 /* ---- batch over frames and devices (frames are independent; no collective) ----
  * Frame i goes to device device_ids[i % n_devices]; one host thread + one context per device. */
