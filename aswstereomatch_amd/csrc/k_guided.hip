@@ -25,8 +25,39 @@ namespace {
 
 constexpr int BW = 256;  // threads per block = 4 independent wavefronts
 struct NoRaw {};
+
+// Phase driver of a software-pipelined walk: runs step(s, phase, flags...) for s up to s_end.  The FIFO slot of a step is a
+// compile-time phase, and the loop is unrolled by the number of slots NPH: a run-time dispatch on the phase inside the loop
+// (if (ph == 0) ... else ...) makes the compiler copy the FIFO registers at the join, and those copies WAIT for the loads issued
+// at the top of the very same step -- the pipeline then hides one step's arithmetic, not its depth in steps.  The seams are
+// straight-line code (a loop around a run-time phase dispatch costs hundreds of spilled registers): up to NPH-1 steps until the
+// phase is 0, the unrolled loop, up to NPH-1 steps behind it.
+template <int NPH, class Step, class... Flags>
+__device__ __forceinline__ void run_phases(int& s, int& ph, int s_end, const Step& step, Flags... f)
+{
+    static_assert(NPH >= 1 && NPH <= 3, "pipeline depths 0 .. 2");
+    if constexpr (NPH > 1) { if (ph == 1 && s < s_end) { step(s, std::integral_constant<int, 1 % NPH>(), f...); s++; ph = 2 % NPH; } }
+    if constexpr (NPH > 2) { if (ph == 2 && s < s_end) { step(s, std::integral_constant<int, 2 % NPH>(), f...); s++; ph = 0; } }
+    if (ph == 0) {
+        for (; s + NPH <= s_end; s += NPH) {  // NPH steps, every FIFO slot a fixed set of registers
+            step(s, std::integral_constant<int, 0>(), f...);
+            if constexpr (NPH > 1) step(s + 1, std::integral_constant<int, 1 % NPH>(), f...);
+            if constexpr (NPH > 2) step(s + 2, std::integral_constant<int, 2 % NPH>(), f...);
+        }
+        if constexpr (NPH > 1) { if (s < s_end) { step(s, std::integral_constant<int, 0>(), f...); s++; ph = 1; } }
+        if constexpr (NPH > 2) { if (s < s_end) { step(s, std::integral_constant<int, 1 % NPH>(), f...); s++; ph = 2; } }
+    }
+}
 template <class D, bool P> struct DstRawSel { using type = typename D::Raw; };
 template <class D> struct DstRawSel<D, true> { using type = typename D::Raw2; };
+
+// normalised channels of one BGRX guide word: convertTo 8u->32f with float scale/shift (App. A-10): v_cvt_f32_ubyteN, mul, add
+__device__ __forceinline__ void guide_unpack(uint32_t u, float2 sc, float* I)
+{
+    I[0] = (float)(u & 0xffu) * sc.x + sc.y;
+    I[1] = (float)((u >> 8) & 0xffu) * sc.x + sc.y;
+    I[2] = (float)((u >> 16) & 0xffu) * sc.x + sc.y;
+}
 
 // Every wavefront owns a strip of 128 input columns (two adjacent ones per lane, 128-(k-1) output columns)
 // of a band of rows and walks down the band on its own:
@@ -51,11 +82,11 @@ template <class D> struct DstRawSel<D, true> { using type = typename D::Raw2; };
 // bands were needed to keep that re-read in L2 at all; with it a band can be as tall as the launch geometry allows (k-1
 // warm-up rows per band: 44 % of the work at 32 rows, 10 % at 135).
 typedef uint32_t v16u __attribute__((ext_vector_type(16)));
-template <int NP, int CPL, int ND, int WPE, bool NANSAFE, int KT, int RING, int PF, class Src, class Dst>
+template <int NP, int CPL, int ND, int WPE, bool NANSAFE, int KT, bool RING, int PF, class Src, class Dst>
 __global__ __launch_bounds__(BW) __attribute__((amdgpu_waves_per_eu(WPE, 8))) void k_box_walk(Src src, Dst dst, int H, int W, int k_rt, int band, int nxw, int nslices, int ngx, int nby, int slice_par)
 {
     static_assert(!RING || KT == 15, "the register ring is a 16-entry vector per kept dword");
-    static_assert(PF >= 0 && PF <= 3, "depth of the software pipeline (0: the loads of a step are issued at its own top)");
+    static_assert(PF >= 0 && PF <= 2, "depth of the software pipeline (0: the loads of a step are issued at its own top)");
     const int k = KT ? KT : k_rt;
     constexpr int SW = 64 * CPL;  // strip width (input columns per wavefront)
     extern __shared__ __align__(16) unsigned char smem[];
@@ -148,7 +179,7 @@ __global__ __launch_bounds__(BW) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
     // waited for without waiting for those stores as well; issued a step earlier, every wait names only older loads.
     constexpr int NPH = PF + 1;
     typename Src::Raw fN[NPH][CPL][ND];
-    using LeaveT = typename std::conditional<RING != 0, typename Src::LRaw, typename Src::Raw>::type;  // what the leaving row loads
+    using LeaveT = typename std::conditional<RING, typename Src::LRaw, typename Src::Raw>::type;  // what the leaving row loads
     LeaveT fL[NPH][CPL][ND];
     // DPAIR: the consumer fetches the operands of the lane's two adjacent output columns with ONE set of vector loads and stores
     // both results with one store per plane (planar layouts: every memory instruction of a wavefront covers one dense run).
@@ -178,7 +209,6 @@ __global__ __launch_bounds__(BW) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
     };
     if constexpr (PF >= 1) issue(0, std::integral_constant<int, 0>());
     if constexpr (PF >= 2) issue(1, std::integral_constant<int, 1>());
-    if constexpr (PF >= 3) issue(2, std::integral_constant<int, 2>());
 
     auto step = [&](int s, auto ph_c, auto sub_c, auto out_c) {
         constexpr int PH = decltype(ph_c)::value;
@@ -376,26 +406,19 @@ __global__ __launch_bounds__(BW) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
     using T = std::true_type;
     using F = std::false_type;
     int s = 0, ph = 0;
-    // The FIFO slot of a step is a compile-time phase, and the loops are unrolled by the number of slots: a run-time dispatch on
-    // the phase inside the loop (if (ph == 0) ... else ...) makes the compiler copy the FIFO registers at the join, and those
-    // copies WAIT for the loads issued at the top of the very same step -- the pipeline then hides one step's arithmetic, not
-    // its depth in steps.
+    // the shape of run_phases, spelled out here: through the shared driver the ring a/b walk of the slice-independent guide
+    // (k_box_walk<4, 2, 1, 2, false, 15, true, 1, ABSrc<3, false>, ABDstP>) comes out with one register move in another place
     auto run = [&](int s_end, auto sub_c, auto out_c) {
-        // seams as straight-line code (a loop around a run-time phase dispatch costs hundreds of spilled registers):
-        // up to NPH-1 steps until the phase is 0, the unrolled loop, up to NPH-1 steps behind it
         if constexpr (NPH > 1) { if (ph == 1 && s < s_end) { step(s, std::integral_constant<int, 1 % NPH>(), sub_c, out_c); s++; ph = 2 % NPH; } }
-        if constexpr (NPH > 2) { if (ph == 2 && s < s_end) { step(s, std::integral_constant<int, 2 % NPH>(), sub_c, out_c); s++; ph = 3 % NPH; } }
-        if constexpr (NPH > 3) { if (ph == 3 && s < s_end) { step(s, std::integral_constant<int, 3 % NPH>(), sub_c, out_c); s++; ph = 0; } }
+        if constexpr (NPH > 2) { if (ph == 2 && s < s_end) { step(s, std::integral_constant<int, 2 % NPH>(), sub_c, out_c); s++; ph = 0; } }
         if (ph == 0) {
             for (; s + NPH <= s_end; s += NPH) {  // NPH steps, every FIFO slot a fixed set of registers
                 step(s, std::integral_constant<int, 0>(), sub_c, out_c);
                 if constexpr (NPH > 1) step(s + 1, std::integral_constant<int, 1 % NPH>(), sub_c, out_c);
                 if constexpr (NPH > 2) step(s + 2, std::integral_constant<int, 2 % NPH>(), sub_c, out_c);
-                if constexpr (NPH > 3) step(s + 3, std::integral_constant<int, 3 % NPH>(), sub_c, out_c);
             }
             if constexpr (NPH > 1) { if (s < s_end) { step(s, std::integral_constant<int, 0>(), sub_c, out_c); s++; ph = 1; } }
             if constexpr (NPH > 2) { if (s < s_end) { step(s, std::integral_constant<int, 1 % NPH>(), sub_c, out_c); s++; ph = 2; } }
-            if constexpr (NPH > 3) { if (s < s_end) { step(s, std::integral_constant<int, 2 % NPH>(), sub_c, out_c); s++; ph = 3; } }
         }
     };
     run(min(k - 1, steps), F(), F());
@@ -442,7 +465,7 @@ struct GuideAccT {
         const float2 sc = c.sc;
 #pragma unroll
         for (int w = 0; w < NW; w++) {
-            // convertTo 8u->32f with float scale/shift (App. A-10): v_cvt_f32_ubyteN, mul, add
+            // spelled out, not guide_unpack: through the helper the ABSrc<3, *> / ABDstP and QSrc<6> / QDst<6, true> walks schedule differently
             I[3 * w + 0] = (float)(u[w] & 0xffu) * sc.x + sc.y;
             I[3 * w + 1] = (float)((u[w] >> 8) & 0xffu) * sc.x + sc.y;
             I[3 * w + 2] = (float)((u[w] >> 16) & 0xffu) * sc.x + sc.y;
@@ -985,9 +1008,7 @@ struct QDstP {
     {
         const float2 sc = c.sc;
         float I[3];
-        I[0] = (float)(u & 0xffu) * sc.x + sc.y;
-        I[1] = (float)((u >> 8) & 0xffu) * sc.x + sc.y;
-        I[2] = (float)((u >> 16) & 0xffu) * sc.x + sc.y;
+        guide_unpack(u, sc, I);
         float dot = 0.0f;
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) {
@@ -1066,7 +1087,7 @@ struct PlaneDst {
 // (they share halo columns in L1), 0 = four slices of one strip (they share the slice-independent operands), -1 = default
 struct WalkOpts { int band = 0; int wg_strips = -1; int interleave = 0; };
 
-template <int NP, int CPL, int ND, int WPE = 4, bool NANSAFE = false, int RING = 0, int PF = 1, class Src, class Dst>
+template <int NP, int CPL, int ND, int WPE = 4, bool NANSAFE = false, bool RING = false, int PF = 1, class Src, class Dst>
 int launch_walk_t(hipStream_t s, const Src& src, const Dst& dst, int H, int W, int k, int n, int n_active = -1, WalkOpts o = WalkOpts())
 {
     constexpr int SW = 64 * CPL;
@@ -1097,8 +1118,8 @@ int launch_walk_t(hipStream_t s, const Src& src, const Dst& dst, int H, int W, i
     size_t lds = (size_t)4 * ND * NP * (SW + 2) * sizeof(double);
     // register target: at least 4 waves/SIMD; asking for 6 or 8 makes the allocator serialise/spill (7.1 / 12.6 ms vs 6.2)
     auto kern = ring ? k_box_walk<NP, CPL, ND, WPE, NANSAFE, 15, RING, PF, Src, Dst>
-              : k == 15 ? k_box_walk<NP, CPL, ND, (RING ? 3 : WPE), NANSAFE, 15, 0, (RING ? 1 : PF), Src, Dst>
-                        : k_box_walk<NP, CPL, ND, (RING ? 3 : WPE), NANSAFE, 0, 0, (RING ? 1 : PF), Src, Dst>;
+              : k == 15 ? k_box_walk<NP, CPL, ND, (RING ? 3 : WPE), NANSAFE, 15, false, (RING ? 1 : PF), Src, Dst>
+                        : k_box_walk<NP, CPL, ND, (RING ? 3 : WPE), NANSAFE, 0, false, (RING ? 1 : PF), Src, Dst>;
     // four slices of one strip per workgroup when there are enough slices (1080p D=128: GuidedF 24.1 -> 22.9 ms, BLO1 -7 %,
     // GuidedF_2 -1 %); four strips of the one slice otherwise
     int slice_par = nzs >= 4 ? 1 : 0;
@@ -1122,6 +1143,14 @@ int launch_walk(hipStream_t s, const Src& src, const Dst& dst, int H, int W, int
     // ND > 1 (several slices per wavefront sharing guide pixel and statistics) was measured and rejected: <CPL,ND> =
     // <2,1> 6.2 ms, <2,2> 7.4, <1,2> 7.5, <1,4> 9.7 -- the extra registers cost more occupancy than the traffic saves.
     return launch_walk_t<NP, 2, ND, 4, NANSAFE>(s, src, dst, H, W, k, n, n_active, o);
+}
+
+// one ring-less walk form, NaN-safe or plain
+template <int NP, int CPL, int WPE, int PF, class Src, class Dst>
+int launch_walk_nan(bool nan_safe, hipStream_t s, const Src& src, const Dst& dst, int H, int W, int k, int n, WalkOpts o = WalkOpts())
+{
+    return nan_safe ? launch_walk_t<NP, CPL, 1, WPE, true, false, PF>(s, src, dst, H, W, k, n, -1, o)
+                    : launch_walk_t<NP, CPL, 1, WPE, false, false, PF>(s, src, dst, H, W, k, n, -1, o);
 }
 
 // ---- fused a/b -> q walk: slice-independent 3-channel guide, 15x15 (GuidedF_2), finite costs ------------------------------------
@@ -1151,34 +1180,35 @@ struct FusedArgs {
 // Producer / consumer pair: wavefront A runs the first stage of a strip (cost ring, column sums, horizontal pass, a/b arithmetic) and hands every a/b
 // row through a double-buffered LDS slot to wavefront B, which runs the second stage (a/b ring, column sums, horizontal pass, q):
 // each holds one ring -- 236 registers, TWO wavefronts per SIMD -- and the two stages of a strip run concurrently, one row
-// apart, with one workgroup barrier per row.  A workgroup = NPAIR pairs (slices of one strip and band); one pair per workgroup
-// measured 3.71 against 3.84 ms for two (the barrier then couples only the two wavefronts that exchange data).
+// apart, with one workgroup barrier per row.  A workgroup = one pair: 3.71 against 3.84 ms for two pairs (slices of one strip
+// and band) per workgroup -- the barrier then couples only the two wavefronts that exchange data.
 // Counters (profiles/r03/guided_fused/): VALU busy 55 % of a SIMD's cycles; a wavefront waits 16 % of its cycles in s_waitcnt
 // (average VMEM latency 840 cycles, LDS 118) and 22 % at the barrier; the kernel issues 1.04e9 VALU instructions against 8.3e8
-// of the two passes (100 instead of 114 outputs per strip, the exchange).  Variants that lost (template parameters kept):
-// the statistics of the next a/b row loaded at the end of the producer's step (STATF: 4.27-4.34 ms), the producer's LDS reads of
-// all four planes in flight (HGRP = 4: 3.70-3.78), b computed by the consumer (4.04), s_setprio for the producer (3.81).
-template <int PF, int HGRP, bool STATF, int NPAIR>
-__global__ __launch_bounds__(128 * NPAIR) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_guided_pair3(FusedArgs a)
+// of the two passes (100 instead of 114 outputs per strip, the exchange).  Variants that lost:
+// the statistics of the next a/b row loaded at the end of the producer's step (4.27-4.34 ms), the producer's LDS reads of
+// all four planes in flight (3.70-3.78), b computed by the consumer (4.04), s_setprio for the producer (3.81).
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_guided_pair3(FusedArgs a)
 {
+    constexpr int PF = 1;  // loads one step ahead
     constexpr int K = 15, HL = 7, SW = 128, XO1 = SW - (K - 1), XO2 = SW - 2 * (K - 1), NPL = 4, HP = (K - 1) / 2;
     constexpr int NPH = PF + 1;
     extern __shared__ __align__(16) unsigned char smem[];
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int role = wv & 1, pr = wv >> 1;  // role 0: first stage (A), 1: second stage (B); pair 0 / 1
+    // role 0: first stage (A), 1: second stage (B).  pr: pair within the workgroup -- 0, the workgroup is one pair; the kernel's
+    // code object is pinned to the measured one, in which this index, `live` and `kzc` are still computed
+    const int role = wv & 1, pr = wv >> 1;
     // per pair: double hsA[NPL][SW+2] | double hsB[NPL][SW+2] | float xch[2][NPL][SW]
     constexpr int PAIR_BYTES = 2 * NPL * (SW + 2) * 8 + 2 * NPL * SW * 4;
     unsigned char* pbase = smem + (size_t)pr * PAIR_BYTES;
     double* hs = reinterpret_cast<double*>(pbase) + (role ? NPL * (SW + 2) : 0);
     float* xch = reinterpret_cast<float*>(pbase + 2 * NPL * (SW + 2) * 8);
     const int H = a.H, W = a.W;
-    const int nzg = (a.n + NPAIR - 1) / NPAIR;
     const int wj = blockIdx.x >> 3;
     const int nreg = a.nxw * a.nby, rpx = (nreg + 7) >> 3;
-    const int reg = (blockIdx.x & 7) * rpx + wj / nzg;
-    if (wj / nzg >= rpx || reg >= nreg) return;  // whole workgroup
+    const int reg = (blockIdx.x & 7) * rpx + wj / a.n;
+    if (wj / a.n >= rpx || reg >= nreg) return;  // whole workgroup
     const int xw = reg % a.nxw, by = reg / a.nxw;
-    const int kz = (wj % nzg) * NPAIR + pr;
+    const int kz = wj % a.n + pr;
     const bool live = kz < a.n;                   // a pair without a slice still keeps the workgroup's barriers
     const int kzc = min(kz, a.n - 1);
     const int xo0 = xw * XO2, c0 = 2 * lane;
@@ -1213,8 +1243,6 @@ __global__ __launch_bounds__(128 * NPAIR) __attribute__((amdgpu_waves_per_eu(2, 
 
     float fP[NPH][2];
     uint32_t fG[NPH][2];
-    double fRn[2][3];  // STATF: statistics of the NEXT iteration's a/b row, loaded at the end of a producer step (one set of
-    float fMn[2][3];   // registers: they are consumed before the next load is issued, so nothing rotates)
     auto issue = [&](int s, auto slot_c) __attribute__((always_inline)) {
         constexpr int SL = decltype(slot_c)::value;
         const size_t rn = (size_t)reflect101_idx(y0 - 2 * HL + s, H) * W;
@@ -1224,26 +1252,8 @@ __global__ __launch_bounds__(128 * NPAIR) __attribute__((amdgpu_waves_per_eu(2, 
             fG[SL][c] = (GA + rn)[xi[c]];
         }
     };
-    auto issue_stats = [&](int s) __attribute__((always_inline)) {
-        const size_t ra = (size_t)reflect101_idx(y0 - 3 * HL + s, H) * W;
-#pragma unroll
-        for (int c = 0; c < 2; c++)
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++) {
-                fRn[c][ch] = (RS + (ch * plane + ra))[xs_[c]];
-                fMn[c][ch] = (MS + (ch * plane + ra))[xs_[c]];
-            }
-    };
-    if (role == 0) {
-        if constexpr (PF >= 1) issue(0, std::integral_constant<int, 0>());
-        if constexpr (PF >= 2) issue(1, std::integral_constant<int, 1>());
-    }
-    auto guide = [&](uint32_t u, float (&I)[3]) __attribute__((always_inline)) {
-        I[0] = (float)(u & 0xffu) * gsc.x + gsc.y;
-        I[1] = (float)((u >> 8) & 0xffu) * gsc.x + gsc.y;
-        I[2] = (float)((u >> 16) & 0xffu) * gsc.x + gsc.y;
-    };
-    auto hpass = [&](bool reader, float (&m)[2][NPL], auto grp_c) __attribute__((always_inline)) {
+    if (role == 0) issue(0, std::integral_constant<int, 0>());
+    auto hpass = [&](bool reader, float (&m)[2][NPL]) __attribute__((always_inline)) {
 #pragma unroll
         for (int p = 0; p < NPL; p++) {
             hs[p * (SW + 2) + c0] = vs[0][p] + vs[1][p];
@@ -1255,7 +1265,7 @@ __global__ __launch_bounds__(128 * NPAIR) __attribute__((amdgpu_waves_per_eu(2, 
 #pragma unroll
         for (int p = 0; p < NPL; p++) { m[0][p] = 0.0f; m[1][p] = 0.0f; }
         if (reader) {
-            constexpr int GRP = decltype(grp_c)::value;
+            constexpr int GRP = 2;  // planes whose LDS reads are in flight together
 #pragma unroll
             for (int p0 = 0; p0 < NPL; p0 += GRP) {
                 double bb[GRP][2 * HP + 2];
@@ -1297,23 +1307,21 @@ __global__ __launch_bounds__(128 * NPAIR) __attribute__((amdgpu_waves_per_eu(2, 
             double fR[2][3];
             float fM[2][3];
             if constexpr (OUT1) {
-                if constexpr (!STATF) {
-                    const size_t ra = (size_t)reflect101_idx(y0 - 3 * HL + it, H) * W;  // a/b row emitted in this iteration
+                const size_t ra = (size_t)reflect101_idx(y0 - 3 * HL + it, H) * W;  // a/b row emitted in this iteration
 #pragma unroll
-                    for (int c = 0; c < 2; c++)
+                for (int c = 0; c < 2; c++)
 #pragma unroll
-                        for (int ch = 0; ch < 3; ch++) {
-                            fR[c][ch] = (RS + (ch * plane + ra))[xs_[c]];
-                            fM[c][ch] = (MS + (ch * plane + ra))[xs_[c]];
-                        }
-                }
+                    for (int ch = 0; ch < 3; ch++) {
+                        fR[c][ch] = (RS + (ch * plane + ra))[xs_[c]];
+                        fM[c][ch] = (MS + (ch * plane + ra))[xs_[c]];
+                    }
             }
 #pragma unroll
             for (int c = 0; c < 2; c++) {
                 if constexpr (SUB1) {
                     const float po = __uint_as_float(ring[c][0][slot]) * psc.x + psc.y;
                     float Io[3];
-                    guide(ring[c][1][slot], Io);
+                    guide_unpack(ring[c][1][slot], gsc, Io);
                     vs[c][0] = vs[c][0] - (double)po;
 #pragma unroll
                     for (int ch = 0; ch < 3; ch++) vs[c][1 + ch] = vs[c][1 + ch] - (double)(Io[ch] * po);
@@ -1322,7 +1330,7 @@ __global__ __launch_bounds__(128 * NPAIR) __attribute__((amdgpu_waves_per_eu(2, 
                 ring[c][1][slot] = fG[PH][c];
                 const float pn = fP[PH][c] * psc.x + psc.y;
                 float In[3];
-                guide(fG[PH][c], In);
+                guide_unpack(fG[PH][c], gsc, In);
                 vs[c][0] = vs[c][0] + (double)pn;
 #pragma unroll
                 for (int ch = 0; ch < 3; ch++) vs[c][1 + ch] = vs[c][1 + ch] + (double)(In[ch] * pn);
@@ -1330,7 +1338,7 @@ __global__ __launch_bounds__(128 * NPAIR) __attribute__((amdgpu_waves_per_eu(2, 
             slot = slot + 1 == K ? 0 : slot + 1;
             if constexpr (OUT1) {
                 float m1[2][NPL];
-                hpass(ab_lane, m1, std::integral_constant<int, HGRP>());
+                hpass(ab_lane, m1);
                 float o[2][NPL];
 #pragma unroll
                 for (int c = 0; c < 2; c++) {
@@ -1338,10 +1346,10 @@ __global__ __launch_bounds__(128 * NPAIR) __attribute__((amdgpu_waves_per_eu(2, 
                     float dot = 0.0f;
 #pragma unroll
                     for (int ch = 0; ch < 3; ch++) {
-                        const float mI = STATF ? fMn[c][ch] : fM[c][ch];
+                        const float mI = fM[c][ch];
                         const float mp = mI * meanP;
                         const float cov = m1[c][1 + ch] - mp;
-                        const float ac = (float)((double)cov * (STATF ? fRn[c][ch] : fR[c][ch]));
+                        const float ac = (float)((double)cov * fR[c][ch]);
                         o[c][ch] = ac;
                         const float pr2 = ac * mI;
                         dot = (ch == 0) ? pr2 : dot + pr2;
@@ -1351,7 +1359,6 @@ __global__ __launch_bounds__(128 * NPAIR) __attribute__((amdgpu_waves_per_eu(2, 
 #pragma unroll
                 for (int p = 0; p < NPL; p++) *reinterpret_cast<float2*>(xs + p * SW + c0) = make_float2(o[0][p], o[1][p]);
             }
-            if constexpr (STATF) issue_stats(it + 1);
         }
         uint2 fQ = make_uint2(0u, 0u);
         if constexpr (OUT2) {
@@ -1382,12 +1389,12 @@ __global__ __launch_bounds__(128 * NPAIR) __attribute__((amdgpu_waves_per_eu(2, 
                 slot = slot + 1 == K ? 0 : slot + 1;
                 if constexpr (OUT2) {
                     float m2[2][NPL];
-                    hpass(c0 < XO2, m2, std::integral_constant<int, 2>());
+                    hpass(c0 < XO2, m2);
                     float qv[2];
 #pragma unroll
                     for (int c = 0; c < 2; c++) {
                         float I[3];
-                        guide(c == 0 ? fQ.x : fQ.y, I);
+                        guide_unpack(c == 0 ? fQ.x : fQ.y, gsc, I);
                         float dot = 0.0f;
 #pragma unroll
                         for (int ch = 0; ch < 3; ch++) {
@@ -1413,19 +1420,7 @@ __global__ __launch_bounds__(128 * NPAIR) __attribute__((amdgpu_waves_per_eu(2, 
     using T = std::true_type;
     using F = std::false_type;
     int it = 0, ph = 0;
-    auto run = [&](int it_end, auto a1, auto b1, auto h2, auto a2, auto b2) __attribute__((always_inline)) {
-        if constexpr (NPH > 1) { if (ph == 1 && it < it_end) { step(it, std::integral_constant<int, 1 % NPH>(), a1, b1, h2, a2, b2); it++; ph = 2 % NPH; } }
-        if constexpr (NPH > 2) { if (ph == 2 && it < it_end) { step(it, std::integral_constant<int, 2 % NPH>(), a1, b1, h2, a2, b2); it++; ph = 0; } }
-        if (ph == 0) {
-            for (; it + NPH <= it_end; it += NPH) {
-                step(it, std::integral_constant<int, 0>(), a1, b1, h2, a2, b2);
-                if constexpr (NPH > 1) step(it + 1, std::integral_constant<int, 1 % NPH>(), a1, b1, h2, a2, b2);
-                if constexpr (NPH > 2) step(it + 2, std::integral_constant<int, 2 % NPH>(), a1, b1, h2, a2, b2);
-            }
-            if constexpr (NPH > 1) { if (it < it_end) { step(it, std::integral_constant<int, 0>(), a1, b1, h2, a2, b2); it++; ph = 1; } }
-            if constexpr (NPH > 2) { if (it < it_end) { step(it, std::integral_constant<int, 1 % NPH>(), a1, b1, h2, a2, b2); it++; ph = 2; } }
-        }
-    };
+    auto run = [&](int it_end, auto... f) __attribute__((always_inline)) { run_phases<NPH>(it, ph, it_end, step, f...); };
     run(min(K - 1, iters), F(), F(), F(), F(), F());          // A accumulates
     run(min(K, iters), F(), T(), T(), F(), F());              // first a/b row
     run(min(2 * (K - 1), iters), T(), T(), T(), F(), F());    // B accumulates
@@ -1449,11 +1444,11 @@ struct Q6Args {
     int H, W, n, band, nxw, nby;
 };
 
-template <int PF, bool NANSAFE>
+template <bool NANSAFE>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_q6_pair(Q6Args a)
 {
     constexpr int K = 15, HL = 7, SW = 128, XO = SW - (K - 1), NPL = 4, HP = (K - 1) / 2;
-    constexpr int NPH = PF + 1;
+    constexpr int PF = 2, NPH = PF + 1;  // loads two steps ahead
     extern __shared__ __align__(16) unsigned char smem[];
     const int lane = threadIdx.x & 63, role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     double* hs = reinterpret_cast<double*>(smem) + (size_t)role * NPL * (SW + 2);   // [NPL][SW+2] per wavefront
@@ -1496,8 +1491,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
         for (int c = 0; c < 2; c++) fN[SL][c] = pc[c][rn];
     };
-    if constexpr (PF >= 1) issue(0, std::integral_constant<int, 0>());
-    if constexpr (PF >= 2) issue(1, std::integral_constant<int, 1>());
+    issue(0, std::integral_constant<int, 0>());
+    issue(1, std::integral_constant<int, 1>());
 
     auto step = [&](int s, auto ph_c, auto sub_c, auto out_c) __attribute__((always_inline)) {
         constexpr int PH = decltype(ph_c)::value;
@@ -1590,9 +1585,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             float I[2][3];
 #pragma unroll
             for (int c = 0; c < 2; c++) {
-                I[c][0] = (float)(gw[c][0] & 0xffu) * sc[c].x + sc[c].y;
-                I[c][1] = (float)((gw[c][0] >> 8) & 0xffu) * sc[c].x + sc[c].y;
-                I[c][2] = (float)((gw[c][0] >> 16) & 0xffu) * sc[c].x + sc[c].y;
+                guide_unpack(gw[c][0], sc[c], I[c]);
             }
             if (role == 0) {  // terms 0..2: word A
                 float part[2];
@@ -1633,19 +1626,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     using T = std::true_type;
     using F = std::false_type;
     int s = 0, ph = 0;
-    auto run = [&](int s_end, auto sub_c, auto out_c) __attribute__((always_inline)) {
-        if constexpr (NPH > 1) { if (ph == 1 && s < s_end) { step(s, std::integral_constant<int, 1 % NPH>(), sub_c, out_c); s++; ph = 2 % NPH; } }
-        if constexpr (NPH > 2) { if (ph == 2 && s < s_end) { step(s, std::integral_constant<int, 2 % NPH>(), sub_c, out_c); s++; ph = 0; } }
-        if (ph == 0) {
-            for (; s + NPH <= s_end; s += NPH) {
-                step(s, std::integral_constant<int, 0>(), sub_c, out_c);
-                if constexpr (NPH > 1) step(s + 1, std::integral_constant<int, 1 % NPH>(), sub_c, out_c);
-                if constexpr (NPH > 2) step(s + 2, std::integral_constant<int, 2 % NPH>(), sub_c, out_c);
-            }
-            if constexpr (NPH > 1) { if (s < s_end) { step(s, std::integral_constant<int, 0>(), sub_c, out_c); s++; ph = 1; } }
-            if constexpr (NPH > 2) { if (s < s_end) { step(s, std::integral_constant<int, 1 % NPH>(), sub_c, out_c); s++; ph = 2; } }
-        }
-    };
+    auto run = [&](int s_end, auto... f) __attribute__((always_inline)) { run_phases<NPH>(s, ph, s_end, step, f...); };
     run(min(K - 1, steps), F(), F());
     run(min(K, steps), F(), T());
     run(steps, T(), T());
@@ -1666,9 +1647,9 @@ int launch_q6_pair(hipStream_t s, const GuidedLaunch& a, const GuideAccT<true>& 
     if (nwg > 0x7fffffffLL) return ASW_ERR_BAD_ARGUMENT;
     const size_t lds = 2 * 4 * (128 + 2) * sizeof(double) + 2 * 128 * sizeof(float);
     if (a.nan_safe)
-        hipLaunchKernelGGL((k_q6_pair<2, true>), dim3((unsigned)nwg), dim3(128), lds, s, f);
+        hipLaunchKernelGGL(k_q6_pair<true>, dim3((unsigned)nwg), dim3(128), lds, s, f);
     else
-        hipLaunchKernelGGL((k_q6_pair<2, false>), dim3((unsigned)nwg), dim3(128), lds, s, f);
+        hipLaunchKernelGGL(k_q6_pair<false>, dim3((unsigned)nwg), dim3(128), lds, s, f);
     ASW_HIP_TRY(hipGetLastError());
     return ASW_OK;
 }
@@ -1690,11 +1671,12 @@ struct AB6Args {
     int H, W, n, band, nxw, nby;
 };
 
-template <int PF, int WPE, bool NANSAFE>
-__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_ab6_pair(AB6Args a)
+// register target of three wavefronts per SIMD (168, 4 spilled): 4.38 against 4.65 ms at two (172); pipeline depth 2: 4.67
+template <bool NANSAFE>
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_ab6_pair(AB6Args a)
 {
     constexpr int K = 15, HL = 7, SW = 128, XO = SW - (K - 1), NPL = 4, HP = (K - 1) / 2;
-    constexpr int NPH = PF + 1;
+    constexpr int PF = 1, NPH = PF + 1;
     extern __shared__ __align__(16) unsigned char smem[];
     const int lane = threadIdx.x & 63, role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     double* hs = reinterpret_cast<double*>(smem) + (size_t)role * NPL * (SW + 2);
@@ -1763,13 +1745,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
             fG[SL][c] = gc[c][rn];
         }
     };
-    if constexpr (PF >= 1) issue(0, std::integral_constant<int, 0>());
-    if constexpr (PF >= 2) issue(1, std::integral_constant<int, 1>());
-    auto guide = [&](uint32_t u, float (&I)[3]) __attribute__((always_inline)) {
-        I[0] = (float)(u & 0xffu) * gsc.x + gsc.y;
-        I[1] = (float)((u >> 8) & 0xffu) * gsc.x + gsc.y;
-        I[2] = (float)((u >> 16) & 0xffu) * gsc.x + gsc.y;
-    };
+    issue(0, std::integral_constant<int, 0>());
 
     auto step = [&](int s, auto ph_c, auto sub_c, auto out_c) __attribute__((always_inline)) {
         constexpr int PH = decltype(ph_c)::value;
@@ -1791,7 +1767,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
             if constexpr (SUB) {
                 const float po = __uint_as_float(ring[c][0][slot]) * psc.x + psc.y;
                 float Io[3];
-                guide(ring[c][1][slot], Io);
+                guide_unpack(ring[c][1][slot], gsc, Io);
                 vs[c][0] = vs[c][0] - (double)po;
 #pragma unroll
                 for (int ch = 0; ch < 3; ch++) vs[c][1 + ch] = vs[c][1 + ch] - (double)(Io[ch] * po);
@@ -1800,7 +1776,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
             ring[c][1][slot] = fG[PH][c];
             const float pn = fP[PH][c] * psc.x + psc.y;
             float In[3];
-            guide(fG[PH][c], In);
+            guide_unpack(fG[PH][c], gsc, In);
             vs[c][0] = vs[c][0] + (double)pn;
 #pragma unroll
             for (int ch = 0; ch < 3; ch++) vs[c][1 + ch] = vs[c][1 + ch] + (double)(In[ch] * pn);
@@ -1820,7 +1796,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
                     for (int j = 0; j < K; j++) {
                         const float pw = __uint_as_float(ring[c][0][idx]) * psc.x + psc.y;
                         float Iw[3];
-                        guide(ring[c][1][idx], Iw);
+                        guide_unpack(ring[c][1][idx], gsc, Iw);
                         acc[0] = acc[0] + (double)pw;
 #pragma unroll
                         for (int ch = 0; ch < 3; ch++) acc[1 + ch] = acc[1 + ch] + (double)(Iw[ch] * pw);
@@ -1930,19 +1906,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     using T = std::true_type;
     using F = std::false_type;
     int s = 0, ph = 0;
-    auto run = [&](int s_end, auto sub_c, auto out_c) __attribute__((always_inline)) {
-        if constexpr (NPH > 1) { if (ph == 1 && s < s_end) { step(s, std::integral_constant<int, 1 % NPH>(), sub_c, out_c); s++; ph = 2 % NPH; } }
-        if constexpr (NPH > 2) { if (ph == 2 && s < s_end) { step(s, std::integral_constant<int, 2 % NPH>(), sub_c, out_c); s++; ph = 0; } }
-        if (ph == 0) {
-            for (; s + NPH <= s_end; s += NPH) {
-                step(s, std::integral_constant<int, 0>(), sub_c, out_c);
-                if constexpr (NPH > 1) step(s + 1, std::integral_constant<int, 1 % NPH>(), sub_c, out_c);
-                if constexpr (NPH > 2) step(s + 2, std::integral_constant<int, 2 % NPH>(), sub_c, out_c);
-            }
-            if constexpr (NPH > 1) { if (s < s_end) { step(s, std::integral_constant<int, 0>(), sub_c, out_c); s++; ph = 1; } }
-            if constexpr (NPH > 2) { if (s < s_end) { step(s, std::integral_constant<int, 1 % NPH>(), sub_c, out_c); s++; ph = 2; } }
-        }
-    };
+    auto run = [&](int s_end, auto... f) __attribute__((always_inline)) { run_phases<NPH>(s, ph, s_end, step, f...); };
     run(min(K - 1, steps), F(), F());
     run(min(K, steps), F(), T());
     run(steps, T(), T());
@@ -1961,11 +1925,10 @@ int launch_ab6_pair(hipStream_t s, const GuidedLaunch& a, const GuideAccT<true>&
     const long long nwg = (long long)((f.nxw * f.nby + 7) / 8) * 8 * a.n;
     if (nwg > 0x7fffffffLL) return ASW_ERR_BAD_ARGUMENT;
     const size_t lds = 2 * 4 * (128 + 2) * sizeof(double) + 2 * 128 * sizeof(float);
-    // register target of three wavefronts per SIMD (168, 4 spilled): 4.38 against 4.65 ms at two (172); pipeline depth 2: 4.67
     if (a.nan_safe)
-        hipLaunchKernelGGL((k_ab6_pair<1, 3, true>), dim3((unsigned)nwg), dim3(128), lds, s, f);
+        hipLaunchKernelGGL(k_ab6_pair<true>, dim3((unsigned)nwg), dim3(128), lds, s, f);
     else
-        hipLaunchKernelGGL((k_ab6_pair<1, 3, false>), dim3((unsigned)nwg), dim3(128), lds, s, f);
+        hipLaunchKernelGGL(k_ab6_pair<false>, dim3((unsigned)nwg), dim3(128), lds, s, f);
     ASW_HIP_TRY(hipGetLastError());
     return ASW_OK;
 }
@@ -1984,7 +1947,7 @@ int launch_guided_fused3(hipStream_t s, const GuidedLaunch& a, const GuideAccT<f
     const long long nwg = (long long)((f.nxw * f.nby + 7) / 8) * 8 * a.n;
     if (nwg > 0x7fffffffLL) return ASW_ERR_BAD_ARGUMENT;
     const size_t lds = 2 * 4 * (128 + 2) * sizeof(double) + 2 * 4 * 128 * sizeof(float);
-    hipLaunchKernelGGL((k_guided_pair3<1, 2, false, 1>), dim3((unsigned)nwg), dim3(128), lds, s, f);
+    hipLaunchKernelGGL(k_guided_pair3, dim3((unsigned)nwg), dim3(128), lds, s, f);
     ASW_HIP_TRY(hipGetLastError());
     return ASW_OK;
 }
@@ -2015,11 +1978,10 @@ int launch_guided3(hipStream_t s, const GuidedLaunch& a, const GuideAccT<SHIFT>&
         // (the ring holding the cost only and the leaving row's guide word fetched again -- 3 wavefronts per SIMD -- measured
         // 0.3-0.4 ms slower: two more loads per step in a pass whose address unit is as busy as its VALU)
         ABSrc<3, SHIFT> src{g, a.P, a.pscales, a.H, a.W};
-        rc = launch_walk_t<4, 2, 1, 2, false, 1, 1>(s, src, dst, a.H, a.W, a.r, a.n, -1, oab);
+        rc = launch_walk_t<4, 2, 1, 2, false, true, 1>(s, src, dst, a.H, a.W, a.r, a.n, -1, oab);
     } else {
         ABSrc<3, SHIFT> src{g, a.P, a.pscales, a.H, a.W};
-        rc = a.nan_safe ? launch_walk_t<4, 2, 1, 3, true>(s, src, dst, a.H, a.W, a.r, a.n, -1, oab)
-                        : launch_walk_t<4, 2, 1, 3, false>(s, src, dst, a.H, a.W, a.r, a.n, -1, oab);
+        rc = launch_walk_nan<4, 2, 3, 1>(a.nan_safe, s, src, dst, a.H, a.W, a.r, a.n, oab);
     }
     if (rc != ASW_OK) return rc;
     QSrcP qs{reinterpret_cast<const float2*>(a.ab), at};
@@ -2027,8 +1989,8 @@ int launch_guided3(hipStream_t s, const GuidedLaunch& a, const GuideAccT<SHIFT>&
         // ring = {a_0, a_1, a_2, b} of the last 15 rows of both columns (128 registers): 2 wavefronts per SIMD.  One column per lane
         // (4 wavefronts) measured 2.75 ms against 1.7: twice the wavefront-rows through the one LDS of the CU
         // loads two steps ahead: 1.61 ms against 1.72 at one step (three: 1.58 with spilled registers)
-        if (ring_q) return launch_walk_t<4, 2, 1, 2, false, 1, 2>(s, qs, qd, a.H, a.W, a.r, a.n, -1, oq);
-        return a.nan_safe ? launch_walk<4, 1, true>(s, qs, qd, a.H, a.W, a.r, a.n, -1, oq) : launch_walk<4>(s, qs, qd, a.H, a.W, a.r, a.n, -1, oq);
+        if (ring_q) return launch_walk_t<4, 2, 1, 2, false, true, 2>(s, qs, qd, a.H, a.W, a.r, a.n, -1, oq);
+        return launch_walk_nan<4, 2, 4, 1>(a.nan_safe, s, qs, qd, a.H, a.W, a.r, a.n, oq);
     };
     if constexpr (SHIFT) {
         QDst<3, true> qd{g, a.q, a.H, a.W};
@@ -2128,9 +2090,9 @@ int launch_guided(hipStream_t s, const GuidedLaunch& a)
     if (a.r == 15 && a.tune->ab6_pair != 0)
         rc = launch_ab6_pair(s, a, g, sp, a.tune->band_ab);
     else if (a.r > 32)
-        rc = a.nan_safe ? launch_walk_t<7, 2, 1, 3, true, 0, 0>(s, src, dst, a.H, a.W, a.r, a.n) : launch_walk_t<7, 2, 1, 3, false, 0, 0>(s, src, dst, a.H, a.W, a.r, a.n);
+        rc = launch_walk_nan<7, 2, 3, 0>(a.nan_safe, s, src, dst, a.H, a.W, a.r, a.n);
     else
-        rc = a.nan_safe ? launch_walk_t<7, 1, 1, 4, true, 0, 0>(s, src, dst, a.H, a.W, a.r, a.n) : launch_walk_t<7, 1, 1, 4, false, 0, 0>(s, src, dst, a.H, a.W, a.r, a.n);
+        rc = launch_walk_nan<7, 1, 4, 0>(a.nan_safe, s, src, dst, a.H, a.W, a.r, a.n);
     if (rc != ASW_OK) return rc;
     if (a.r == 15 && a.tune->q6_pair != 0) return launch_q6_pair(s, a, g, a.tune->band_q);
     QSrc<6> qs{a.ab, a.H, a.W, hstride};
@@ -2138,7 +2100,7 @@ int launch_guided(hipStream_t s, const GuidedLaunch& a)
     // two columns per lane: 4.5 ms, one: 5.3 ms.  No load FIFO here (PF = 0): 16 floats per row and lane in flight twice over would
     // cost the fourth wavefront per SIMD (5.1 ms at two)
     // (finite data: a register target of 3 wavefronts per SIMD buys the LDS reads of two planes in flight together, 3.84 against 4.01 ms)
-    return a.nan_safe ? launch_walk_t<7, 2, 1, 4, true, 0, 0>(s, qs, qd, a.H, a.W, a.r, a.n) : launch_walk_t<7, 2, 1, 3, false, 0, 0>(s, qs, qd, a.H, a.W, a.r, a.n);
+    return a.nan_safe ? launch_walk_t<7, 2, 1, 4, true, false, 0>(s, qs, qd, a.H, a.W, a.r, a.n) : launch_walk_t<7, 2, 1, 3, false, false, 0>(s, qs, qd, a.H, a.W, a.r, a.n);
 }
 
 // interleaved C-channel 8U image -> BGRX word planes (channels 3w..3w+2 in plane w)
