@@ -27,7 +27,8 @@ __all__ = [
     "computeAdaptiveWeight_GuidedF_2", "computeAdaptiveWeight_WeightedMedian", "winnerTakeAll", "last_status",
     "stereoMatchingBatch", "computeAdaptiveWeight_BLO1", "computeAdaptiveWeight_direct8", "computeNCC", "computeNCC_costs",
     "computeAdaptiveWeight_GuidedF_3", "getDisparity_SGBM", "sgbm", "filterSpeckles", "getDisparity_BM", "stereoBM",
-    "PREFILTER_NORMALIZED_RESPONSE", "PREFILTER_XSOBEL",
+    "PREFILTER_NORMALIZED_RESPONSE", "PREFILTER_XSOBEL", "refineDisparity", "stereoMatchingRefined",
+    "REFINE_GAMMA_C", "REFINE_GAMMA_S",
     "AswError",
 ]
 
@@ -59,6 +60,7 @@ OK, ERR_SIZE_MISMATCH, ERR_EVEN_WINDOW, ERR_UNSUPPORTED_METHOD, ERR_UNSUPPORTED_
 ERR_HIP, ERR_ALLOC, ERR_BAD_ARGUMENT, ERR_NO_FRAME = 5, 6, 7, 8
 MODE_SGBM_3WAY = 2  # StereoSGBM::MODE_SGBM_3WAY, the one mode asw_sgbm serves
 PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL = 0, 1  # StereoBM::PREFILTER_*; asw_stereo_bm serves XSOBEL
+REFINE_GAMMA_C, REFINE_GAMMA_S = 60.0, 9.0  # default colour / distance gammas of the refinement's weighted median (asw_mi355x.h)
 # statuses for which the reference returns silently / an empty Mat
 _SILENT = (ERR_SIZE_MISMATCH, ERR_EVEN_WINDOW)
 
@@ -407,6 +409,42 @@ class Context:
         self._finish(rc, "asw_lr_check")
         return out, n.value
 
+    def refineDisparity(self, guide, dispLeft, dispRight, minDisparity, numValues, maxDiff=1.0, winSize=15,
+                        gamma_c=REFINE_GAMMA_C, gamma_s=REFINE_GAMMA_S, return_mask=False):
+        """asw_refine_disparity: cross-check, scan-line fill of the rejected pixels, weighted median over the filled ones ->
+        (refined map, rejected pixels, unfillable pixels[, mask: 0 valid / 1 filled / 2 unfillable]).  numValues: number of
+        admissible disparities from minDisparity on (asw_volume_planes(algorithm, numDisparity) for a selector method)."""
+        gi, ga = _image(guide)
+        a = np.ascontiguousarray(dispLeft, dtype=np.float32)
+        b = np.ascontiguousarray(dispRight, dtype=np.float32)
+        if a.ndim != 2 or a.shape != b.shape or a.shape != ga.shape[:2]:
+            raise ValueError("refineDisparity: a guide and two float32 maps of equal (H, W) shape expected")
+        out = np.zeros(a.shape, np.float32)
+        mask = np.zeros(a.shape, np.uint8) if return_mask else None
+        nr, nu = C.c_int(0), C.c_int(0)
+        rc = self._lib.asw_refine_disparity(self._h, C.byref(gi), a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p),
+                                            int(minDisparity), int(numValues), float(maxDiff), int(winSize), float(gamma_c),
+                                            float(gamma_s), out.ctypes.data_as(C.c_void_p),
+                                            mask.ctypes.data_as(C.c_void_p) if return_mask else None, C.byref(nr), C.byref(nu))
+        self._strict(rc, "asw_refine_disparity")
+        return (out, nr.value, nu.value, mask) if return_mask else (out, nr.value, nu.value)
+
+    def stereoMatchingRefined(self, srcLeft, srcRight, algorithmType, winSize=15, minDisparity=0, numDisparity=64, maxDiff=1.0,
+                              refineWin=15, gamma_c=REFINE_GAMMA_C, gamma_s=REFINE_GAMMA_S):
+        """asw_stereo_match_refined: both directions of the method + refineDisparity with srcLeft as guide ->
+        (refined left-view map, rejected pixels, unfillable pixels).  Not a reference function, so there is no silent return to
+        mimic: like the resident calls, every non-zero status raises AswError (size mismatch and even window included)."""
+        li, la = _image(srcLeft)
+        ri, ra = _image(srcRight)
+        disp = np.zeros(la.shape[:2], np.float32)
+        di, _ = _image(disp, 5)
+        nr, nu = C.c_int(0), C.c_int(0)
+        rc = self._lib.asw_stereo_match_refined(self._h, C.byref(li), C.byref(ri), C.byref(di), int(algorithmType), winSize,
+                                                minDisparity, numDisparity, float(maxDiff), int(refineWin), float(gamma_c),
+                                                float(gamma_s), C.byref(nr), C.byref(nu))
+        self._strict(rc, "asw_stereo_match_refined")
+        return disp, nr.value, nu.value
+
     def bgr2gray(self, img):
         ii, ia = _image(img)
         out = np.zeros(ia.shape[:2], np.uint8)
@@ -431,6 +469,17 @@ class Context:
         rc = self._lib.asw_match_resident(self._h, slot, int(disparityType), int(algorithmType), winSize, minDisparity,
                                           numDisparity, 1 if keep_volume else 0)
         self._strict(rc, "asw_match_resident")
+
+    def match_refined_resident(self, slot, algorithmType, winSize, minDisparity, numDisparity, maxDiff=1.0, refineWin=15,
+                               gamma_c=REFINE_GAMMA_C, gamma_s=REFINE_GAMMA_S):
+        """asw_match_refined_resident: both directions on the slot's pair, the refined map becomes the slot's disparity ->
+        (rejected pixels, unfillable pixels)."""
+        nr, nu = C.c_int(0), C.c_int(0)
+        rc = self._lib.asw_match_refined_resident(self._h, slot, int(algorithmType), winSize, minDisparity, numDisparity,
+                                                  float(maxDiff), int(refineWin), float(gamma_c), float(gamma_s), C.byref(nr),
+                                                  C.byref(nu))
+        self._strict(rc, "asw_match_refined_resident")
+        return nr.value, nu.value
 
     def download_disparity(self, slot, shape):
         disp = np.zeros(shape, np.float32)
@@ -563,3 +612,5 @@ sgbm = _bind("sgbm")
 filterSpeckles = _bind("filterSpeckles")
 getDisparity_BM = _bind("getDisparity_BM")
 stereoBM = _bind("stereoBM")
+refineDisparity = _bind("refineDisparity")
+stereoMatchingRefined = _bind("stereoMatchingRefined")

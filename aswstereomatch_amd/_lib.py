@@ -22,6 +22,7 @@ ABI_SYMBOLS = [
     "asw_cost_ad", "asw_cost_tad", "asw_cost_sd", "asw_cost_similarity", "asw_cost_sad", "asw_cost_sad_d",
     "asw_guided_filter", "asw_geodesic_dist", "asw_wta", "asw_bgr2gray", "asw_lr_check", "asw_volume_planes",
     "asw_stereo_match_batch", "asw_sgbm", "asw_filter_speckles", "asw_stereo_bm", "asw_get_disparity_bm",
+    "asw_refine_disparity", "asw_match_refined_resident", "asw_stereo_match_refined",
 ]
 
 
@@ -105,5 +106,8 @@ def lib():
         l.asw_filter_speckles.argtypes = [P, IMG, I, I, I]
         l.asw_stereo_bm.argtypes = [P, IMG, IMG, IMG, I, I, I, I, I, I, I, I, I, I, I, P, C.c_size_t]
         l.asw_get_disparity_bm.argtypes = [P, IMG, IMG, IMG, I, I, I]
+        l.asw_refine_disparity.argtypes = [P, IMG, P, P, I, I, C.c_float, I, D, D, P, P, P, P]
+        l.asw_match_refined_resident.argtypes = [P, I, I, I, I, I, C.c_float, I, D, D, P, P]
+        l.asw_stereo_match_refined.argtypes = [P, IMG, IMG, IMG, I, I, I, I, C.c_float, I, D, D, P, P]
         _lib = l
     return _lib

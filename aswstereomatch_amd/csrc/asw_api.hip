@@ -487,6 +487,59 @@ extern "C" int asw_aggregate_wmedian(asw_ctx* ctx, const asw_image* left, const 
     return match_host(ctx, left, right, disp, ASW_ALG_ADAPTIVE_WEIGHT_MEDIAN, mp, cost_volume_out, cost_volume_floats);
 }
 
+// ---- left-right refinement ----
+extern "C" int asw_refine_disparity(asw_ctx* ctx, const asw_image* guide, const float* disp_left, const float* disp_right,
+                                    int min_disparity, int num_values, float max_diff, int win_size, double gamma_c, double gamma_s,
+                                    float* out, uint8_t* mask_out, int* n_rejected, int* n_unfillable)
+{
+    if (!ctx || !disp_left || !disp_right || !out) return ASW_ERR_BAD_ARGUMENT;
+    ASW_TRY(check_u8_image(guide));
+    const int H = guide->rows, W = guide->cols;
+    RefineParams rp;
+    rp.minD = min_disparity; rp.n = num_values; rp.max_diff = max_diff; rp.win = win_size; rp.gamma_c = gamma_c; rp.gamma_s = gamma_s;
+    ASW_TRY(check_refine_params(rp, H, W, guide->channels));
+    ASW_HIP_TRY(hipSetDevice(ctx->device));
+    const size_t plane = (size_t)H * W;
+    DevBuf& dg = ctx->buf("stageL");
+    DevBuf& a = ctx->buf("refine_left");
+    DevBuf& b = ctx->buf("refine_right");
+    DevBuf& o = ctx->buf("refine_out");
+    ASW_TRY(upload_image(ctx, guide, dg));
+    ASW_TRY(a.ensure(plane * 4));
+    ASW_TRY(b.ensure(plane * 4));
+    ASW_TRY(o.ensure(plane * 4));
+    ASW_HIP_TRY(hipMemcpyAsync(a.p, disp_left, plane * 4, hipMemcpyHostToDevice, ctx->stream));
+    ASW_HIP_TRY(hipMemcpyAsync(b.p, disp_right, plane * 4, hipMemcpyHostToDevice, ctx->stream));
+    int rejected = 0, unfillable = 0;
+    ASW_TRY(run_refine(ctx, dg.as<uint8_t>(), guide->channels, a.as<float>(), b.as<float>(), H, W, rp, o.as<float>(), &rejected,
+                       &unfillable));  // a map outside the domain returns here: nothing of the caller's has been written
+    ASW_HIP_TRY(hipMemcpyAsync(out, o.p, plane * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (mask_out) ASW_HIP_TRY(hipMemcpyAsync(mask_out, ctx->buf("refine_mask").p, plane, hipMemcpyDeviceToHost, ctx->stream));
+    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (n_rejected) *n_rejected = rejected;
+    if (n_unfillable) *n_unfillable = unfillable;
+    return ASW_OK;
+}
+
+extern "C" int asw_stereo_match_refined(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp, int algorithm,
+                                        int win_size, int min_disparity, int num_disparity, float max_diff, int refine_win,
+                                        double gamma_c, double gamma_s, int* n_rejected, int* n_unfillable)
+{
+    if (!ctx) return ASW_ERR_BAD_ARGUMENT;
+    ASW_TRY(check_pair(left, right));
+    ASW_TRY(check_disp_out(disp, left->rows, left->cols));
+    ASW_HIP_TRY(hipSetDevice(ctx->device));
+    Frame* f = &ctx->host_frame;
+    ASW_TRY(upload_pair_into(ctx, f, left, right));
+    int rejected = 0, unfillable = 0;
+    ASW_TRY(match_refined(ctx, f, algorithm, win_size, min_disparity, num_disparity, max_diff, refine_win, gamma_c, gamma_s, &rejected,
+                          &unfillable));
+    ASW_TRY(download_disparity_from(ctx, f, disp));
+    if (n_rejected) *n_rejected = rejected;
+    if (n_unfillable) *n_unfillable = unfillable;
+    return ASW_OK;
+}
+
 // ---- semi-global block matching (StereoSGBM::compute, MODE_SGBM_3WAY) and cv::filterSpeckles ----
 static int check_s16_image(const asw_image* im)
 {

@@ -132,6 +132,8 @@ extern "C" void asw_destroy(asw_ctx* ctx)
     ctx->bil.taps.release();
     ctx->bil.lut.release();
     ctx->bil.cells.release();
+    ctx->refine.tc.release();
+    ctx->refine.ts.release();
     ctx->wm_lut2.release();
     ctx->wm_wd.release();
     for (int i = 0; i < 4; i++)

@@ -50,6 +50,21 @@ struct BmParams {
         speckle_window_size, speckle_range, disp12_max_diff;
 };
 int bm_prepare(asw_ctx* ctx, const BmParams& p, int H, int W, BmLaunch* out);
+// Left-right refinement.  check_refine_params: the argument rules of asw_refine_disparity; run_refine: the three
+// kernels on device maps (out must not alias dl / dr), waits, reads the counters back; ASW_ERR_BAD_ARGUMENT when dl leaves its
+// domain.  The mask stays in ctx->buf("refine_mask").  match_refined: both directions of `algorithm` on the frame's pair + run_refine
+// with the frame's left image as guide; the refined map becomes the frame's disparity.
+struct RefineParams {
+    int minD, n;
+    float max_diff;
+    int win;
+    double gamma_c, gamma_s;
+};
+int check_refine_params(const RefineParams& p, int rows, int cols, int channels);
+int run_refine(asw_ctx* ctx, const uint8_t* guide, int channels, const float* dl, const float* dr, int H, int W, const RefineParams& p,
+               float* out, int* n_rejected, int* n_unfillable);
+int match_refined(asw_ctx* ctx, Frame* f, int algorithm, int win_size, int min_disparity, int num_disparity, float max_diff,
+                  int refine_win, double gamma_c, double gamma_s, int* n_rejected, int* n_unfillable);
 int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp, bool keep_volume, bool sync = true);
 int match_host(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp, int algorithm,
                       const MatchParams& mp, float* cost_volume_out, size_t cost_volume_floats);

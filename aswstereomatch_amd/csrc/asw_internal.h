@@ -78,6 +78,14 @@ struct AswTuning {
     void read_environment();
 };
 
+struct RefineTables {  // cached per (win, gamma_c, gamma_s, channels): integer weights of the refinement's median (k_refine.hip)
+    int win = 0, channels = 0;
+    double gamma_c = 0, gamma_s = 0;
+    int ntc = 0;
+    DevBuf tc;  // u32 [255 * channels + 1]: floor(4096 * exp(-c / gamma_c) + 0.5)
+    DevBuf ts;  // u32 [win/2 + 1][win/2 + 1]: floor(256 * exp(-sqrt(i*i + j*j) / gamma_s) + 0.5)
+};
+
 struct asw_ctx {
     int device = 0;
     AswTuning tune;
@@ -89,6 +97,7 @@ struct asw_ctx {
     std::vector<unsigned char> host_pack;  // dense staging for host images whose rows carry padding (asw_context.hip: copy_rows)
     std::map<std::string, DevBuf> scratch;  // named grow-only scratch buffers
     BilateralTables bil;
+    RefineTables refine;
     // weighted-median tables: exp() LUT of the colour weight per rateR, space kernel per (win, rateS)
     DevBuf wm_lut2, wm_wd;
     double wm_rate_r = -1, wm_rate_s = -1;
@@ -252,6 +261,25 @@ int launch_blo1(hipStream_t s, const uint8_t* gl, const uint8_t* gr, const float
 
 int launch_lr_check(hipStream_t s, const float* dl, const float* dr, int H, int W, float max_diff, float invalid, float* out,
                     unsigned* n_invalid);
+
+// ---- left-right refinement (k_refine.hip): cross-check, scan-line fill, weighted median; DESIGN.md section 4.10 ----
+struct RefineLaunch {
+    const uint8_t* guide;  // dense interleaved 8U, C = 1 or 3 channels
+    int C;
+    const float* dl;       // left-view map, absolute disparities
+    const float* dr;       // right-view map
+    int H, W, minD, n;     // admissible values minD .. minD + n - 1
+    float max_diff;
+    int win;               // odd, 1..35
+    const unsigned* tc;    // RefineTables
+    int ntc;
+    const unsigned* ts;
+    uint8_t* mask;         // out [H][W]: 0 valid, 1 filled, 2 unfillable
+    unsigned short* F;     // scratch [H][W]: filled map, disparity - minD (0xFFFF unfillable)
+    float* out;            // out [H][W]; must not alias dl / dr
+    unsigned* counters;    // 3 words: rejected pixels, unfillable pixels, != 0 when dl leaves the domain
+};
+int launch_refine(hipStream_t s, const RefineLaunch& a);
 
 // ---- bilateral-grid ASW, k_bilgrid.hip ----
 // grid extents (last index per axis; both range axes share nz); ASW_ERR_BAD_ARGUMENT for rates <= 0 or a range axis too fine for LDS

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #include "asw_internal.h"
@@ -840,6 +841,117 @@ extern "C" int asw_match_resident(asw_ctx* ctx, int slot, int disparity_type, in
     MatchParams mp;
     mp.disparity_type = disparity_type; mp.win = win_size; mp.minD = min_disparity; mp.numD = num_disparity;
     return run_method(ctx, f, algorithm, mp, keep_volume != 0);
+}
+
+// ------------------------------------------------------------------------------------------
+// left-right refinement: cross-check, scan-line fill, weighted median (not in the reference)
+// ------------------------------------------------------------------------------------------
+int check_refine_params(const RefineParams& p, int rows, int cols, int channels)
+{
+    if (rows <= 0 || cols <= 0 || (size_t)rows * cols >= ((size_t)1 << 31) || rows > 4 * 65535) return ASW_ERR_BAD_ARGUMENT;
+    if (p.n < 1 || p.n > 1025 || p.minD < -(1 << 20) || p.minD > (1 << 20)) return ASW_ERR_BAD_ARGUMENT;
+    if (!(p.max_diff >= 0)) return ASW_ERR_BAD_ARGUMENT;
+    if (p.win < 1 || p.win > 35 || p.win % 2 == 0) return ASW_ERR_BAD_ARGUMENT;
+    if (!(p.gamma_c > 0) || !(p.gamma_s > 0)) return ASW_ERR_BAD_ARGUMENT;
+    if (channels != 1 && channels != 3) return ASW_ERR_UNSUPPORTED_LAYOUT;
+    return ASW_OK;
+}
+
+static int ensure_refine_tables(asw_ctx* ctx, int win, double gamma_c, double gamma_s, int channels)
+{
+    RefineTables& t = ctx->refine;
+    if (t.win == win && t.gamma_c == gamma_c && t.gamma_s == gamma_s && t.channels == channels && t.tc.p && t.ts.p) return ASW_OK;
+    t.win = 0;
+    const int k = win / 2, ntc = 255 * channels + 1;
+    std::vector<unsigned> tc(ntc), ts((size_t)(k + 1) * (k + 1));
+    for (int c = 0; c < ntc; c++) tc[c] = (unsigned)floor(4096.0 * exp(-(double)c / gamma_c) + 0.5);
+    for (int j = 0; j <= k; j++)
+        for (int i = 0; i <= k; i++) ts[(size_t)j * (k + 1) + i] = (unsigned)floor(256.0 * exp(-sqrt((double)(i * i + j * j)) / gamma_s) + 0.5);
+    ASW_TRY(t.tc.ensure(tc.size() * sizeof(unsigned)));
+    ASW_TRY(t.ts.ensure(ts.size() * sizeof(unsigned)));
+    ASW_HIP_TRY(hipMemcpyAsync(t.tc.p, tc.data(), tc.size() * sizeof(unsigned), hipMemcpyHostToDevice, ctx->stream));
+    ASW_HIP_TRY(hipMemcpyAsync(t.ts.p, ts.data(), ts.size() * sizeof(unsigned), hipMemcpyHostToDevice, ctx->stream));
+    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));  // the host vectors go out of scope
+    t.win = win; t.gamma_c = gamma_c; t.gamma_s = gamma_s; t.channels = channels; t.ntc = ntc;
+    return ASW_OK;
+}
+
+int run_refine(asw_ctx* ctx, const uint8_t* guide, int channels, const float* dl, const float* dr, int H, int W, const RefineParams& p,
+               float* out, int* n_rejected, int* n_unfillable)
+{
+    ASW_TRY(check_refine_params(p, H, W, channels));
+    ASW_TRY(ensure_refine_tables(ctx, p.win, p.gamma_c, p.gamma_s, channels));
+    const size_t plane = (size_t)H * W;
+    DevBuf& mask = ctx->buf("refine_mask");
+    DevBuf& F = ctx->buf("refine_fill");
+    DevBuf& cnt = ctx->buf("refine_count");
+    ASW_TRY(mask.ensure(plane));
+    ASW_TRY(F.ensure(plane * sizeof(unsigned short)));
+    ASW_TRY(cnt.ensure(3 * sizeof(unsigned)));
+    RefineLaunch a;
+    a.guide = guide; a.C = channels; a.dl = dl; a.dr = dr; a.H = H; a.W = W; a.minD = p.minD; a.n = p.n; a.max_diff = p.max_diff;
+    a.win = p.win; a.tc = ctx->refine.tc.as<unsigned>(); a.ntc = ctx->refine.ntc; a.ts = ctx->refine.ts.as<unsigned>();
+    a.mask = mask.as<uint8_t>(); a.F = F.as<unsigned short>(); a.out = out; a.counters = cnt.as<unsigned>();
+    ASW_TRY(launch_refine(ctx->stream, a));
+    unsigned c[3] = {0, 0, 0};
+    ASW_HIP_TRY(hipMemcpyAsync(c, cnt.p, sizeof(c), hipMemcpyDeviceToHost, ctx->stream));
+    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (c[2]) return ASW_ERR_BAD_ARGUMENT;  // step 0: some dl is not an integer in [minD, minD + n)
+    if (n_rejected) *n_rejected = (int)c[0];
+    if (n_unfillable) *n_unfillable = (int)c[1];
+    return ASW_OK;
+}
+
+// Both directions of `algorithm` (RIGHT, then LEFT), each WTA map swapped out of the frame into context scratch as soon as it exists (the second
+// match cannot overwrite the first, nothing travels through the host), then the refinement into the frame's own map.
+int match_refined(asw_ctx* ctx, Frame* f, int algorithm, int win_size, int min_disparity, int num_disparity, float max_diff,
+                  int refine_win, double gamma_c, double gamma_s, int* n_rejected, int* n_unfillable)
+{
+    f->invalidate_results();
+    if (algorithm == ASW_ALG_SGBM || algorithm == ASW_ALG_BM) return ASW_ERR_UNSUPPORTED_METHOD;  // they carry their own disp12MaxDiff
+    if (num_disparity <= 0 || min_disparity < 0) return ASW_ERR_BAD_ARGUMENT;  // as a plain match (run_method)
+    RefineParams rp;
+    rp.minD = min_disparity; rp.n = asw_volume_planes(algorithm, num_disparity); rp.max_diff = max_diff; rp.win = refine_win;
+    rp.gamma_c = gamma_c; rp.gamma_s = gamma_s;
+    if (rp.n == 0) return ASW_ERR_UNSUPPORTED_METHOD;
+    ASW_TRY(check_refine_params(rp, f->rows, f->cols, f->channels));
+    MatchParams mp;
+    mp.win = win_size; mp.minD = min_disparity; mp.numD = num_disparity;
+    DevBuf* side[2] = {&ctx->buf("refine_left"), &ctx->buf("refine_right")};
+    asw_timing sum = {0, 0, 0, 0};
+    for (int dt = 1; dt >= 0; dt--) {  // RIGHT first: a method whose right branch is not served is refused before any work
+        mp.disparity_type = dt == 0 ? ASW_DISPARITY_LEFT : ASW_DISPARITY_RIGHT;
+        ASW_TRY(run_method(ctx, f, algorithm, mp, false));
+        std::swap(f->disp, *side[dt]);
+        f->invalidate_results();
+        sum.total_ms += ctx->timing.total_ms; sum.aggregate_ms += ctx->timing.aggregate_ms;
+        sum.aggregate_launches += ctx->timing.aggregate_launches;
+    }
+    ASW_TRY(f->disp.ensure((size_t)f->rows * f->cols * sizeof(float)));
+    ASW_HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
+    ASW_TRY(run_refine(ctx, f->L.as<uint8_t>(), f->channels, side[0]->as<float>(), side[1]->as<float>(), f->rows, f->cols, rp,
+                       f->disp.as<float>(), n_rejected, n_unfillable));
+    ASW_HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
+    ASW_HIP_TRY(hipEventSynchronize(ctx->ev[1]));
+    float t = 0;
+    ASW_HIP_TRY(hipEventElapsedTime(&t, ctx->ev[0], ctx->ev[1]));
+    sum.total_ms += t;
+    sum.cost_ms = sum.total_ms - sum.aggregate_ms;
+    ctx->timing = sum;
+    f->has_disp = true; f->disp_rows = f->rows; f->disp_cols = f->cols;
+    return ASW_OK;
+}
+
+extern "C" int asw_match_refined_resident(asw_ctx* ctx, int slot, int algorithm, int win_size, int min_disparity, int num_disparity,
+                                          float max_diff, int refine_win, double gamma_c, double gamma_s, int* n_rejected,
+                                          int* n_unfillable)
+{
+    if (!ctx) return ASW_ERR_BAD_ARGUMENT;
+    Frame* f = frame_slot(ctx, slot, false);
+    if (!f || !f->valid) return ASW_ERR_NO_FRAME;
+    ASW_HIP_TRY(hipSetDevice(ctx->device));
+    return match_refined(ctx, f, algorithm, win_size, min_disparity, num_disparity, max_diff, refine_win, gamma_c, gamma_s, n_rejected,
+                         n_unfillable);
 }
 
 // ---- internal hooks of the batch scheduler (batch.hip): device buffers of a slot, enqueue without waiting ----

@@ -335,6 +335,35 @@ inline AswMat leftRightCheck(AswMat dispLeft, AswMat dispRight, float maxDiff = 
     return rc == ASW_OK ? out : AswMat();
 }
 
+// Not in the reference: left-right refinement (asw_refine_disparity) -- cross-check, scan-line fill of the rejected pixels, weighted
+// median over the filled ones; numValues = number of admissible disparities from minDisparity on.  Throws like leftRightCheck.
+inline AswMat refineDisparity(AswMat guide, AswMat dispLeft, AswMat dispRight, int minDisparity, int numValues, float maxDiff = 1.0f,
+                              int winSize = 15, double gamma_c = 60, double gamma_s = 9, int* nRejected = nullptr,
+                              int* nUnfillable = nullptr)
+{
+    if (dispLeft.rows != dispRight.rows || dispLeft.cols != dispRight.cols || guide.rows != dispLeft.rows || guide.cols != dispLeft.cols)
+        return AswMat();
+    AswMat out = asw::detail::make(dispLeft.rows, dispLeft.cols, ASW_32F, 1);
+    asw_image g = asw::detail::view(guide), a = asw::detail::view(dispLeft), b = asw::detail::view(dispRight), o = asw::detail::view(out);
+    if (a.depth != ASW_32F || b.depth != ASW_32F || a.step != (size_t)a.cols * 4 || b.step != (size_t)b.cols * 4 || o.step != (size_t)o.cols * 4)
+        throw std::runtime_error("refineDisparity: continuous CV_32FC1 maps expected");
+    int rc = asw_refine_disparity(asw::detail::context(), &g, (const float*)a.data, (const float*)b.data, minDisparity, numValues, maxDiff,
+                                  winSize, gamma_c, gamma_s, (float*)o.data, nullptr, nRejected, nUnfillable);
+    asw::detail::raise_unless_ok(rc, "refineDisparity");
+    return rc == ASW_OK ? out : AswMat();
+}
+
+// Not in the reference: stereoMatching in both directions + refineDisparity with srcLeft as guide (asw_stereo_match_refined)
+inline AswMat stereoMatchingRefined(AswMat srcLeft, AswMat srcRight, StereoMatchingAlgorithms algorithmType, int winSize = 15,
+                                    int minDisparity = 0, int numDisparity = 64, float maxDiff = 1.0f, int refineWin = 15,
+                                    double gamma_c = 60, double gamma_s = 9, int* nRejected = nullptr, int* nUnfillable = nullptr)
+{
+    return asw::detail::aggregate(srcLeft, srcRight, [&](asw_ctx* c, asw_image* l, asw_image* r, asw_image* o) {
+        return asw_stereo_match_refined(c, l, r, o, (int)algorithmType, winSize, minDisparity, numDisparity, maxDiff, refineWin, gamma_c,
+                                        gamma_s, nRejected, nUnfillable);
+    }, "stereoMatchingRefined");
+}
+
 // M.h:156 / M.cpp:2442-2503: ONE disparity; the view that is not the reference view arrives bordered by the caller
 // (copyMakeBorder by max_offset, M.cpp:2877-2878).  Empty Mat for an even window or a bordered view that is not wider.
 inline AswMat getCostSAD_d(AswMat leftImg, AswMat rightImg, int disparity, DisparityType dispType = DISPARITY_LEFT, int winSize = 35)

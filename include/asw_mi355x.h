@@ -238,6 +238,42 @@ int asw_wta(asw_ctx* ctx, const float* cost_volume, int n, int rows, int cols, i
  * [0, cols) and |dl(y,x) - dr(y,xr)| <= max_diff, else invalid_value.  n_invalid (optional) receives the number of rejected pixels. */
 int asw_lr_check(asw_ctx* ctx, const float* disp_left, const float* disp_right, int rows, int cols, float max_diff,
                  float invalid_value, float* out, int* n_invalid);
+/* ---- left-right refinement: cross-check, occlusion fill, weighted median (not in the reference) ----
+ * The post-processing Hosni, Bleyer, Gelautz put behind every weight function: asw_lr_check's rule, then every rejected pixel takes
+ * the lower of the nearest valid disparities to its left and right on its row (the one that exists at a border; a row without a
+ * valid pixel is unfillable), then every FILLED pixel takes the weighted median of the filled map over a win_size x win_size window
+ * (taps inside the image, unfillable taps cast no vote).  Weights are integers, w = Tc[sum over channels |G(p) - G(q)|] * Ts[|j|][|i|],
+ * Tc[c] = floor(4096 * exp(-c / gamma_c) + 0.5), Ts[j][i] = floor(256 * exp(-sqrt(i*i + j*j) / gamma_s) + 0.5) (host, double, libm);
+ * the median is the smallest v with 2 * (weight of the votes <= v) >= total weight.  All sums are exact in 32 bits.
+ * asw_refine_disparity: guide ASW_8U with 1 or 3 channels (else ASW_ERR_UNSUPPORTED_LAYOUT), rows x cols (rows <= 262140, rows * cols
+ * < 2^31); disp_left / disp_right / out: dense f32 rows x cols, absolute disparities.  Every disp_left value must be an integer in
+ * [min_disparity, min_disparity + num_values) -- anything else, NaN and inf included, gives ASW_ERR_BAD_ARGUMENT with nothing
+ * written to out / mask_out / the counts; disp_right may hold anything.  1 <= num_values <= 1025 (asw_volume_planes(algorithm,
+ * num_disparity) for a selector method), |min_disparity| <= 2^20, max_diff >= 0, win_size odd in 1..35 (1: cross-check + fill only),
+ * gamma_c > 0, gamma_s > 0; the Python / C++ wrappers default to gamma_c = 60, gamma_s = 9, win_size = 15.  out: disp_left where
+ * valid, the median where filled, min_disparity - 1 where unfillable.  mask_out (optional): one byte per pixel, 0 valid, 1 filled,
+ * 2 unfillable.  n_rejected (optional): pixels the cross-check rejected (= asw_lr_check's n_invalid); n_unfillable (optional).
+ * asw_match_refined_resident: DISPARITY_LEFT and DISPARITY_RIGHT of `algorithm` on the resident pair of `slot`, both winner-take-all
+ * maps kept in HBM, refined with the resident left image as guide (after asw_preprocess_pair: the processed one) and num_values =
+ * asw_volume_planes(algorithm, num_disparity); the refined map becomes the slot's disparity (asw_download_disparity /
+ * asw_download_disparity_u8 as after asw_match_resident; no volume is kept: asw_download_volume gives ASW_ERR_NO_FRAME).  A method
+ * whose DISPARITY_RIGHT match is not served returns that match's status (ASW_ERR_UNSUPPORTED_LAYOUT for 8DIRECT, BILATERAL_GRID,
+ * GUIDED_FILTER_2, MEDIAN) before anything is computed: the RIGHT match runs first.  num_disparity <= 0 or min_disparity < 0:
+ * ASW_ERR_BAD_ARGUMENT, as for asw_match_resident; ASW_ALG_SGBM / ASW_ALG_BM: ASW_ERR_UNSUPPORTED_METHOD (they carry their own disp12MaxDiff).  A matcher's
+ * map leaves the domain above only where the method writes a literal 0: ASW_ALG_NCC leaves unwritten pixels 0 and its DISPARITY_RIGHT
+ * map is all zeros, so with min_disparity > 0 the refined NCC call returns ASW_ERR_BAD_ARGUMENT like the building block.  Any failure
+ * drops the slot's results as a failed asw_match_resident does; the resident pair is never disturbed.
+ * asw_get_timing afterwards: total_ms = the kernels of both matches + the refinement; aggregate_ms / aggregate_launches = the two
+ * matches' aggregation kernels summed; cost_ms = total_ms - aggregate_ms (the cost builders of both matches + the refinement).
+ * asw_stereo_match_refined: the same on host images, on the context's private frame like asw_stereo_match. */
+int asw_refine_disparity(asw_ctx* ctx, const asw_image* guide, const float* disp_left, const float* disp_right,
+                         int min_disparity, int num_values, float max_diff, int win_size, double gamma_c, double gamma_s,
+                         float* out, uint8_t* mask_out, int* n_rejected, int* n_unfillable);
+int asw_match_refined_resident(asw_ctx* ctx, int slot, int algorithm, int win_size, int min_disparity, int num_disparity,
+                               float max_diff, int refine_win, double gamma_c, double gamma_s, int* n_rejected, int* n_unfillable);
+int asw_stereo_match_refined(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp, int algorithm,
+                             int win_size, int min_disparity, int num_disparity, float max_diff, int refine_win, double gamma_c,
+                             double gamma_s, int* n_rejected, int* n_unfillable);
 /* cvtColor(COLOR_BGR2GRAY) as used at M.cpp:1031-1033 */
 int asw_bgr2gray(asw_ctx* ctx, const asw_image* bgr, uint8_t* gray);
 

@@ -14,4 +14,10 @@ for alg, name in ((2, "classic"), (3, "direct8"), (4, "geodesic"), (5, "bilgrid"
         t = c.timing()
         best = min(best, (t["total_ms"], t["aggregate_ms"]))
     print("%-9s total %8.3f ms  aggregate %8.3f ms" % (name, best[0], best[1]), flush=True)
+for alg, name in ((2, "classic"), (4, "geodesic"), (7, "guided"), (9, "guided3"), (11, "ncc")):  # both directions + refinement
+    best = 1e9
+    for i in range(3):
+        c.match_refined_resident(0, alg, 15, 0, D)
+        best = min(best, c.timing()["total_ms"])
+    print("%-9s refined (LEFT + RIGHT + cross-check / fill / median) total %8.3f ms" % (name, best), flush=True)
 c.close()
