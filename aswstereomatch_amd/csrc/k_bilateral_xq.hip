@@ -61,6 +61,9 @@ constexpr int PXW = 64;                   // pixels per workgroup
 constexpr int LWC = PXW + 2 * HH;         // left tile columns  [x0 - 7, x0 + 70]
 constexpr int NSTEP = KS + 3;             // 18 steps: unit row b runs b tap columns behind
 constexpr int RING = 5;                   // tap columns of left weights kept (4 in use + the one being staged)
+constexpr int URI = 3;                    // window rows per body of the row loop (interior tiles)
+constexpr int CROW = 6;                   // rows in front of the mid-step stage_commit
+static_assert(KS % URI == 0 && CROW % URI == 0, "whole bodies");
 constexpr int NCELLCOL = NSTEP + 3;       // cell-table columns kx = -3 .. 17
 constexpr int LW8 = 80;                   // u8 row stride of the left tile (multiple of 4)
 constexpr int LWP = 80;                   // u32 row stride of the left gray tile (multiple of 4 >= LWC)
@@ -74,7 +77,7 @@ constexpr int LWP = 80;                   // u32 row stride of the left gray til
 // LDS layout (bytes): left block [KS] x {float [RING][PXW] left weights, u32 [LWP] left gray} | right block [KS] x {float [2][NPOS]
 // right weights, u32 [RWP] right gray} | u8 [KS][LW8] | u8 [KS][RW8] | u16 [NCELLCOL * KS] packed cell table.  Weights and
 // grays of a window row share one row stride per side, so that every LDS address of the row loop is one of two per-lane bases
-// (three in wave 0) plus an immediate offset: two address increments per row instead of six.
+// (three in wave 0) plus an immediate offset: two address increments per body of three rows.
 // Epilogue (over the dead tiles): double [NFIN][PXW] E | per-part WTA partials double E[NW][PXW], float d[NW][PXW].
 // NW = 8: 70 KB (the epilogue's), two workgroups = 16 wavefronts per CU; NW = 4: 52 KB, three workgroups = 12 wavefronts per CU.
 template <int NW>
@@ -158,7 +161,7 @@ template <int NW> struct Staged { float v[XqCfg<NW>::NROWS][1 + XqCfg<NW>::NPOS 
 
 template <int NW>
 __device__ __forceinline__ void stage_issue(int Kn, const float* __restrict__ lut, const unsigned char* smem, int wave, int lane,
-                                            int ctrL, int pclamp_lo, int pclamp_hi, Staged<NW>& st)
+                                            uint32_t ppack, Staged<NW>& st)
 {
     XQ_CONSTS(NW)
     const uint8_t* sL8 = smem + OFF_L8;
@@ -171,16 +174,15 @@ __device__ __forceinline__ void stage_issue(int Kn, const float* __restrict__ lu
         if (Kn < KS) {        // left column Kn exists
             cell_at<NW>(smem, (Kn + 3) * KS + ky, dxw, dyw, cls);
             const int nb = sL8[(HH + dyw) * LW8 + (lane + HH + dxw)];
-            st.v[rr][0] = lut_at(lut, __builtin_amdgcn_sad_u16(nb, ctrL, cls));
+            st.v[rr][0] = lut_at(lut, __builtin_amdgcn_sad_u16(nb, sL8[HH * LW8 + lane + HH], cls));
         }
 #pragma unroll
         for (int r3 = 0; r3 < NPOS / 64; r3++) {
-            const int p = lane + 64 * r3;
-            const int b = p & 3;  // posmin == Q (mod 4): the unit row a position belongs to is a property of the position
+            const int b = lane & 3;  // of p = lane + 64 * r3; posmin == Q (mod 4): the unit row a position belongs to is a property of the position
             cell_at<NW>(smem, (Kn - b + 3) * KS + ky, dxw, dyw, cls);
             // the weight is evaluated AT max(0, x - d) (M.cpp:1105); its neighbour is clamped from there (tile columns are
             // replicate-clamped, so adding the direction needs no further clamp)
-            const int pc = min(max(p, pclamp_lo), pclamp_hi) + HH;  // tile column of the clamped position
+            const int pc = (int)((ppack >> (8 * r3)) & 255u) + HH;  // tile column of the clamped position
             const int ctr = sR8[HH * RW8 + pc];
             const int nb = sR8[(HH + dyw) * RW8 + pc + dxw];
             st.v[rr][1 + r3] = lut_at(lut, __builtin_amdgcn_sad_u16(nb, ctr, cls));
@@ -206,10 +208,10 @@ __device__ __forceinline__ void stage_commit(int Kn, unsigned char* smem, int wa
 
 template <int NW>
 __device__ __forceinline__ void stage_weights(int Kn, const float* __restrict__ lut, unsigned char* smem, int wave, int lane,
-                                              int ctrL, int pclamp_lo, int pclamp_hi)
+                                              uint32_t ppack)
 {
     Staged<NW> st;
-    stage_issue<NW>(Kn, lut, smem, wave, lane, ctrL, pclamp_lo, pclamp_hi, st);
+    stage_issue<NW>(Kn, lut, smem, wave, lane, ppack, st);
     stage_commit<NW>(Kn, smem, wave, lane, st);
 }
 
@@ -244,9 +246,9 @@ __device__ __forceinline__ void run_step(unsigned char* smem, int g, int qrel, i
             iR[dl + 3] = min(max(rc - (posmin - HH), 0), RWC - 1);
         }
     }
-    // the row loop's LDS addresses: three per-lane bases (left block, right block, wrapped right block) that advance by one row
-    // per iteration; everything else is an immediate offset.  The empty asm hides the bases' relation from the loop
-    // optimiser, which otherwise rebuilds them from an SGPR row counter with one more add per row.
+    // the row loop's LDS addresses: three per-lane bases (left block, right block, wrapped right block) that advance once per
+    // loop body; everything else, the row within the body included, is an immediate offset.  The empty asm hides the bases'
+    // relation from the loop optimiser, which otherwise rebuilds them from an SGPR row counter with one more add per row.
     typedef __attribute__((address_space(3))) const unsigned char lds_u8;
     lds_u8* bL = (lds_u8*)smem + OFF_LB + 16 * g;
     lds_u8* bR = (lds_u8*)smem + OFF_RB + 4 * qrel;
@@ -254,79 +256,125 @@ __device__ __forceinline__ void run_step(unsigned char* smem, int g, int qrel, i
     uint32_t hi0[7];
 #pragma unroll
     for (int i = 0; i < 7; i++) asm volatile("v_mov_b32 %0, 0" : "=v"(hi0[i]));  // seven distinct registers the compiler cannot fold
+    // UR rows per loop body: the row strides fold into the offset fields (UR - 1 rows of the right stride plus the largest in-row
+    // offset stay far below 16 bits), so the bases advance once per body.  A fence after every row keeps the next row's loads
+    // behind it: unfenced, the scheduler hoists them and spills hundreds of registers.  The mid-step stage_commit sits between
+    // two such loops, so no row tests for it.
+    constexpr int UR = EDGE ? 1 : URI;  // the border tiles' per-diagonal addresses leave no registers for it
+    auto rows = [&](int ky0, int nbody) {
 #pragma unroll 1
-    for (int ky = 0; ky < KS; ky++) {
-        if constexpr (COMMIT) {
-            if (ky == KS / 2) stage_commit<NW>(K + 1, smem, wave, lane, st);  // the gathers issued before this loop have landed
-        }
-        double c[7];  // cost samples of the diagonals, scaled domain: |gL - gR| * 2^-1074
-        if constexpr (!EDGE) {
-            const uint32_t gr = *(const __attribute__((address_space(3))) uint32_t*)(bR + 4 * (RGRAY + K));  // tile column of Q + K - 7
-            uint32_t gr2 = gr;
-            if constexpr (WRAPW && (RIGHT ? DHI > 0 : DLO < 0)) gr2 = *(const __attribute__((address_space(3))) uint32_t*)(bR2 + 4 * (RGRAY + K));
-            // the left grays of the step, read as 16-byte aligned quads from a tile column that is a multiple of four (4g, LWP
-            // and E0 are): a run the compiler cannot prove aligned is split into narrower reads (ds_read2_*), which cost
-            // several times the LDS cycles of ds_read_b128
-            constexpr int E0 = (K + DLO) & ~3, NQ = (K + DHI - E0 + 4) / 4;
-            static_assert(E0 >= 0 && E0 + 4 * NQ + 4 * 15 <= LWP, "the quads stay inside a tile row");
-            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-            const __attribute__((address_space(3))) u32x4* pl4 = (const __attribute__((address_space(3))) u32x4*)(bL + 4 * (LGRAY + E0));
-            uint32_t glv[4 * NQ];
+        for (int it = 0; it < nbody; it++) {
 #pragma unroll
-            for (int i = 0; i < NQ; i++) {
-                u32x4 t = pl4[i];
-                asm("" : "+v"(t));  // all four words in use: otherwise the compiler narrows a quad whose first word no diagonal
-                                    // needs into a misaligned 12-byte read and splits that into ds_read2_b32 + ds_read_b32
-                glv[4 * i] = t.x; glv[4 * i + 1] = t.y; glv[4 * i + 2] = t.z; glv[4 * i + 3] = t.w;
+            for (int u = 0; u < UR; u++) {
+                lds_u8* rL = bL + u * 4 * LROW;
+                lds_u8* rR = bR + u * 4 * RROW;
+                lds_u8* rR2 = bR2 + u * 4 * RROW;
+                double c[7];  // cost samples of the diagonals, scaled domain: |gL - gR| * 2^-1074
+                if constexpr (!EDGE) {
+                    const uint32_t gr = *(const __attribute__((address_space(3))) uint32_t*)(rR + 4 * (RGRAY + K));  // tile column of Q + K - 7
+                    uint32_t gr2 = gr;
+                    if constexpr (WRAPW && (RIGHT ? DHI > 0 : DLO < 0)) gr2 = *(const __attribute__((address_space(3))) uint32_t*)(rR2 + 4 * (RGRAY + K));
+                    // the left grays of the step, read as 16-byte aligned quads from a tile column that is a multiple of four (4g, LWP
+                    // and E0 are): a run the compiler cannot prove aligned is split into narrower reads (ds_read2_*), which cost
+                    // several times the LDS cycles of ds_read_b128
+                    constexpr int E0 = (K + DLO) & ~3, NQ = (K + DHI - E0 + 4) / 4;
+                    static_assert(E0 >= 0 && E0 + 4 * NQ + 4 * 15 <= LWP, "the quads stay inside a tile row");
+                    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                    const __attribute__((address_space(3))) u32x4* pl4 = (const __attribute__((address_space(3))) u32x4*)(rL + 4 * (LGRAY + E0));
+                    uint32_t glv[4 * NQ];
+#pragma unroll
+                    for (int i = 0; i < NQ; i++) {
+                        u32x4 t = pl4[i];
+                        asm("" : "+v"(t));  // all four words in use: otherwise the compiler narrows a quad whose first word no diagonal
+                                            // needs into a misaligned 12-byte read and splits that into ds_read2_b32 + ds_read_b32
+                        glv[4 * i] = t.x; glv[4 * i + 1] = t.y; glv[4 * i + 2] = t.z; glv[4 * i + 3] = t.w;
+                    }
+#pragma unroll
+                    for (int dl = DLO; dl <= DHI; dl++) c[dl + 3] = cost_sample(glv[K + dl - E0], (RIGHT ? dl > 0 : dl < 0) ? gr2 : gr, hi0[dl + 3]);
+                } else {
+                    const int ky = ky0 + it * UR + u;
+#pragma unroll
+                    for (int dl = DLO; dl <= DHI; dl++) c[dl + 3] = cost_sample(sLd[ky * LROW + iL[dl + 3]], sRd[ky * RROW + iR[dl + 3]], hi0[dl + 3]);
+                }
+                typedef float f32x4 __attribute__((ext_vector_type(4)));
+                typedef __attribute__((address_space(3))) const f32x4 lds_f32x4;
+                const f32x4 wr4 = *(lds_f32x4*)(rR + 4 * (K & 1) * NPOS);
+                // the right weights as the two register pairs the packed multiplies broadcast from (op_sel picks either half of a
+                // pair).  The upper pair is made opaque: the compiler otherwise copies element 3 into the low half of a fresh pair,
+                // one v_mov per row.
+                typedef float f32x2 __attribute__((ext_vector_type(2)));
+                f32x2 wrp[2] = {{wr4.x, wr4.y}, {wr4.z, wr4.w}};
+                asm("" : "+v"(wrp[1]));
+                f32x2 wr2p[2] = {wrp[0], wrp[1]};
+                if constexpr ((WRAPW || EDGE) && (RIGHT ? BLO <= 2 : BHI >= 1)) {  // some active unit is a wrapped one
+                    const f32x4 w2 = *(lds_f32x4*)(rR2 + 4 * (K & 1) * NPOS);
+                    wr2p[0] = f32x2{w2.x, w2.y};
+                    wr2p[1] = f32x2{w2.z, w2.w};
+                    asm("" : "+v"(wr2p[1]));
+                }
+#pragma unroll
+                for (int b = BLO; b <= BHI; b++) {
+                    const f32x4 wl4 = *(lds_f32x4*)(rL + 4 * ((K - b) % RING) * PXW);
+                    // the f32 products (M.cpp:1104-1105, x 2^120) written as the two packed multiplies they are issued as: pixels
+                    // (a, a + 1) times the position's weight broadcast -- left to the vectoriser, the unrolled body pairs units
+                    // across b and assembles the pairs with moves
+                    float ab[4];
+#pragma unroll
+                    for (int a = 0; a < 4; a += 2) {
+                        const f32x2 wl2 = {wl4[a], wl4[a + 1]};
+                        const bool w0 = RIGHT ? b < a : a < b, w1 = RIGHT ? b < a + 1 : a + 1 < b;  // wrapped units
+                        const f32x2 s0 = (w0 ? wr2p : wrp)[b >> 1], s1 = (w1 ? wr2p : wrp)[b >> 1];
+                        f32x2 wrb;
+                        if (w0 == w1) wrb = (b & 1) ? __builtin_shufflevector(s0, s0, 1, 1) : __builtin_shufflevector(s0, s0, 0, 0);
+                        else wrb = f32x2{s0[b & 1], s1[b & 1]};
+                        const f32x2 pr = wl2 * wrb;
+                        ab[a] = pr.x; ab[a + 1] = pr.y;
+                    }
+#pragma unroll
+                    for (int a = 0; a < 4; a++) {
+                        const double abd = (double)ab[a];
+                        num[a][b] = __builtin_fma(abd, c[a - b + 3], num[a][b]);  // exact product: == num + ab*c (x 2^-954)
+                        den[a][b] = den[a][b] + abd;                              // M.cpp:1107-1108 (x 2^120)
+                    }
+                }
+                // the fence: the row's sums are complete here (the arithmetic has no side effect the barrier alone would order)
+                // and no LDS read crosses
+#pragma unroll
+                for (int b = BLO; b <= BHI; b++)
+                    asm volatile("" :: "v"(num[0][b]), "v"(num[1][b]), "v"(num[2][b]), "v"(num[3][b]),
+                                       "v"(den[0][b]), "v"(den[1][b]), "v"(den[2][b]), "v"(den[3][b]) : "memory");
+                __builtin_amdgcn_sched_barrier(0);
             }
-#pragma unroll
-            for (int dl = DLO; dl <= DHI; dl++) c[dl + 3] = cost_sample(glv[K + dl - E0], (RIGHT ? dl > 0 : dl < 0) ? gr2 : gr, hi0[dl + 3]);
-        } else {
-#pragma unroll
-            for (int dl = DLO; dl <= DHI; dl++) c[dl + 3] = cost_sample(sLd[ky * LROW + iL[dl + 3]], sRd[ky * RROW + iR[dl + 3]], hi0[dl + 3]);
-        }
-        typedef float f32x4 __attribute__((ext_vector_type(4)));
-        typedef __attribute__((address_space(3))) const f32x4 lds_f32x4;
-        const f32x4 wr4 = *(lds_f32x4*)(bR + 4 * (K & 1) * NPOS);
-        const float wr[4] = {wr4.x, wr4.y, wr4.z, wr4.w};
-        float wr2[4] = {wr4.x, wr4.y, wr4.z, wr4.w};
-        if constexpr ((WRAPW || EDGE) && (RIGHT ? BLO <= 2 : BHI >= 1)) {  // some active unit is a wrapped one
-            const f32x4 w2 = *(lds_f32x4*)(bR2 + 4 * (K & 1) * NPOS);
-            wr2[0] = w2.x; wr2[1] = w2.y; wr2[2] = w2.z; wr2[3] = w2.w;
-        }
-#pragma unroll
-        for (int b = BLO; b <= BHI; b++) {
-            const f32x4 wl4 = *(lds_f32x4*)(bL + 4 * ((K - b) % RING) * PXW);
-            const float wl[4] = {wl4.x, wl4.y, wl4.z, wl4.w};
-#pragma unroll
-            for (int a = 0; a < 4; a++) {
-                const float ab = wl[a] * ((RIGHT ? b < a : a < b) ? wr2[b] : wr[b]);  // f32 product, M.cpp:1104-1105 (x 2^120)
-                const double abd = (double)ab;
-                num[a][b] = __builtin_fma(abd, c[a - b + 3], num[a][b]);  // exact product: == num + ab*c (x 2^-954)
-                den[a][b] = den[a][b] + abd;                              // M.cpp:1107-1108 (x 2^120)
+            bL += UR * 4 * LROW;
+            bR += UR * 4 * RROW;
+            asm("" : "+v"(bL), "+v"(bR));
+            if constexpr (WRAPW || EDGE) {
+                bR2 += UR * 4 * RROW;
+                asm("" : "+v"(bR2));
             }
         }
-        bL += 4 * LROW;
-        bR += 4 * RROW;
-        asm("" : "+v"(bL), "+v"(bR));
-        if constexpr (WRAPW || EDGE) {
-            bR2 += 4 * RROW;
-            asm("" : "+v"(bR2));
-        }
+    };
+    if constexpr (COMMIT) {
+        // the gathers issued before this loop have landed after CROW rows
+        rows(0, CROW / UR);
+        stage_commit<NW>(K + 1, smem, wave, lane, st);
+        rows(CROW, (KS - CROW) / UR);
+    } else {
+        rows(0, KS / UR);
     }
 }
 
 // ABL (timing experiments only, results are wrong): bit 0 = no weight staging after step 0, bit 1 = no barriers between steps
 template <int NW, bool EDGE, bool WRAPW, int ABL, bool RIGHT>
-__device__ __forceinline__ void run_all_steps(unsigned char* smem, const float* __restrict__ lut, int wave, int lane, int ctrL,
-                                              int pclamp_lo, int pclamp_hi, int g, int qrel, int qrel2, int xabs, int dbase, int dbase2,
+__device__ __forceinline__ void run_all_steps(unsigned char* smem, const float* __restrict__ lut, int wave, int lane,
+                                              uint32_t ppack, int g, int qrel, int qrel2, int xabs, int dbase, int dbase2,
                                               int W, int x0, int posmin, double (&num)[4][4], double (&den)[4][4])
 {
     Staged<NW> st;
 #define ASW_XQ_STEP(KK)                                                                                        \
     if (!(ABL & 1) && (KK) + 1 < NSTEP) {                                                                        \
-        if constexpr (EDGE) stage_weights<NW>((KK) + 1, lut, smem, wave, lane, ctrL, pclamp_lo, pclamp_hi);  /* border tiles: registers are scarcer there */ \
-        else stage_issue<NW>((KK) + 1, lut, smem, wave, lane, ctrL, pclamp_lo, pclamp_hi, st);                      \
+        if constexpr (EDGE) stage_weights<NW>((KK) + 1, lut, smem, wave, lane, ppack);  /* border tiles: registers are scarcer there */ \
+        else stage_issue<NW>((KK) + 1, lut, smem, wave, lane, ppack, st);                      \
     }                                                                                                           \
     run_step<NW, (KK), EDGE, WRAPW, (!EDGE && !(ABL & 1) && (KK) + 1 < NSTEP), RIGHT>(smem, g, qrel, qrel2, xabs, dbase, dbase2, W, x0, posmin, \
                                                                            num, den, wave, lane, st);          \
@@ -396,10 +444,17 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
     const int xabs = x0 + 4 * g;                           // X
     const int dbase = p.minD + 4 * jl;                     // d of the diagonal a == b
     const int dbase2 = jl == 0 ? p.minD + 4 * NJ : dbase;
-    const int ctrL = smem[OFF_L8 + HH * LW8 + lane + HH];  // this lane's pixel as the centre of left weights it stages
     // positions are clamped into the image before the weight is looked up: max(0, x - d) / min(W-1, x + d) (the other bound
     // only matters for the lanes of a partial tile, whose results are discarded)
     const int pclamp_lo = min(max(0 - posmin, 0), NPOS - 1), pclamp_hi = min(max(W - 1 - posmin, 0), NPOS - 1);
+    // the clamped positions lane + 64 r this lane stages, one byte each in one register that the compiler cannot take apart
+    // again: left to itself it keeps every clamped position, the bounds and more in registers of their own through all
+    // steps, a dozen of the 128
+    static_assert(NPOS <= 256, "a clamped position fits a byte");
+    uint32_t ppack = 0;
+#pragma unroll
+    for (int r3 = 0; r3 < NPOS / 64; r3++) ppack |= (uint32_t)min(max(lane + 64 * r3, pclamp_lo), pclamp_hi) << (8 * r3);
+    asm volatile("" : "+v"(ppack));
 
     double num[4][4], den[4][4];
 #pragma unroll
@@ -407,27 +462,31 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
 #pragma unroll
         for (int b = 0; b < 4; b++) { num[a][b] = 0.0; den[a][b] = 0.0; }
 
-    stage_weights<NW>(0, lut, smem, wave, lane, ctrL, pclamp_lo, pclamp_hi);
+    stage_weights<NW>(0, lut, smem, wave, lane, ppack);
     __syncthreads();
     // wave 0 holds the threads of block j = 0 (the wrapped units): its steps load the second right weights / gray; ONE branch
     // around the whole step sequence (a branch per step made the register allocator spill 488 VGPRs)
     if (EDGE || wave == 0)
-        run_all_steps<NW, EDGE, true, ABL, RIGHT>(smem, lut, wave, lane, ctrL, pclamp_lo, pclamp_hi, g, qrel, qrel2, xabs, dbase, dbase2, W,
+        run_all_steps<NW, EDGE, true, ABL, RIGHT>(smem, lut, wave, lane, ppack, g, qrel, qrel2, xabs, dbase, dbase2, W,
                                                    x0, posmin, num, den);
     else
-        run_all_steps<NW, EDGE, false, ABL, RIGHT>(smem, lut, wave, lane, ctrL, pclamp_lo, pclamp_hi, g, qrel, qrel2, xabs, dbase, dbase2, W,
+        run_all_steps<NW, EDGE, false, ABL, RIGHT>(smem, lut, wave, lane, ppack, g, qrel, qrel2, xabs, dbase, dbase2, W,
                                                     x0, posmin, num, den);
     // (the last step ended with a barrier: the tiles are dead)
 
     // ---- E = num / den (M.cpp:1111) -> LDS [candidate][pixel]; back from the scaled domain first (both ldexp are exact)
+    // (g and jl are taken from the lane number afresh: carried through the steps for this use they cost two of the 128 registers)
+    int le = lane;
+    asm volatile("" : "+v"(le));
+    const int ge = (le & 7) | ((le >> 2) & 8), jle = 4 * wave + ((le >> 3) & 3);
+    const int cb = 4 * jle, cb2 = jle == 0 ? 4 * NJ : cb;  // dbase - minD, dbase2 - minD
     double* sE = reinterpret_cast<double*>(smem + OFF_E64);
 #pragma unroll
     for (int a = 0; a < 4; a++)
 #pragma unroll
         for (int b = 0; b < 4; b++) {
-            const int c = RIGHT ? (b < a ? dbase2 : dbase) - p.minD + b - a
-                                : (a < b ? dbase2 : dbase) - p.minD + a - b;  // in [0, 128) for every unit
-            sE[c * PXW + 4 * g + a] = __builtin_ldexp(num[a][b], 954) / __builtin_ldexp(den[a][b], -120);
+            const int c = RIGHT ? (b < a ? cb2 : cb) + b - a : (a < b ? cb2 : cb) + a - b;  // in [0, 128) for every unit
+            sE[c * PXW + 4 * ge + a] = __builtin_ldexp(num[a][b], 954) / __builtin_ldexp(den[a][b], -120);
         }
     __syncthreads();
     // ---- WTA (strict '<' while d ascends) and volume: thread -> (pixel, 16 consecutive candidates)
@@ -447,13 +506,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
     sPE[part * PXW + px] = be;
     sPD[part * PXW + px] = bd;
     __syncthreads();
-    if (tid < PXW && x < W) {
+    if (wave == 0 && x < W) {  // tid == px there: nothing but the lane number has to outlive the steps
         double e = 1.7976931348623157e308;
         float d = 0.0f;
 #pragma unroll
         for (int q = 0; q < NWAVE; q++) {
-            const double eq = sPE[q * PXW + tid];
-            if (eq < e) { e = eq; d = sPD[q * PXW + tid]; }
+            const double eq = sPE[q * PXW + px];
+            if (eq < e) { e = eq; d = sPD[q * PXW + px]; }
         }
         if (disp) {
             disp[(size_t)y * W + x] = d;
