@@ -28,7 +28,7 @@ __all__ = [
     "stereoMatchingBatch", "computeAdaptiveWeight_BLO1", "computeAdaptiveWeight_direct8", "computeNCC", "computeNCC_costs",
     "computeAdaptiveWeight_GuidedF_3", "getDisparity_SGBM", "sgbm", "filterSpeckles", "getDisparity_BM", "stereoBM",
     "PREFILTER_NORMALIZED_RESPONSE", "PREFILTER_XSOBEL", "refineDisparity", "stereoMatchingRefined",
-    "REFINE_GAMMA_C", "REFINE_GAMMA_S",
+    "REFINE_GAMMA_C", "REFINE_GAMMA_S", "SUBPIXEL_PARABOLA", "SUBPIXEL_EQUIANGULAR",
     "AswError",
 ]
 
@@ -55,6 +55,9 @@ class StereoMatchingAlgorithms(enum.IntEnum):  # parametersStereo.h:10-24
 
 DISPARITY_LEFT = DisparityType.DISPARITY_LEFT
 DISPARITY_RIGHT = DisparityType.DISPARITY_RIGHT
+# Sub-pixel disparity (asw_mi355x.h: ASW_DISPARITY_SUBPIXEL_*): OR one of them into a disparity type,
+# e.g. DISPARITY_LEFT | SUBPIXEL_PARABOLA, or pass it as subpixel= where that keyword exists
+SUBPIXEL_PARABOLA, SUBPIXEL_EQUIANGULAR = 0x100, 0x200
 
 OK, ERR_SIZE_MISMATCH, ERR_EVEN_WINDOW, ERR_UNSUPPORTED_METHOD, ERR_UNSUPPORTED_LAYOUT = 0, 1, 2, 3, 4
 ERR_HIP, ERR_ALLOC, ERR_BAD_ARGUMENT, ERR_NO_FRAME = 5, 6, 7, 8
@@ -146,7 +149,8 @@ class Context:
 
     # ---- whole-method entry point (M.h:91-92) ----
     def stereoMatching(self, srcLeft, srcRight, disparityType, algorithmType, winSize=15, minDisparity=0,
-                       numDisparity=64, return_cost_volume=False):
+                       numDisparity=64, return_cost_volume=False, subpixel=None):
+        """subpixel: None, SUBPIXEL_PARABOLA or SUBPIXEL_EQUIANGULAR, OR-ed into disparityType."""
         li, la = _image(srcLeft)
         ri, ra = _image(srcRight)
         disp = np.zeros((la.shape[0], la.shape[1]), np.float32)
@@ -156,7 +160,7 @@ class Context:
         if return_cost_volume:
             vol = np.zeros((self._candidates(int(algorithmType), numDisparity), la.shape[0], la.shape[1]), np.float32)
             pv = vol.ctypes.data_as(C.c_void_p)
-        rc = self._lib.asw_stereo_match(self._h, C.byref(li), C.byref(ri), C.byref(di), int(disparityType),
+        rc = self._lib.asw_stereo_match(self._h, C.byref(li), C.byref(ri), C.byref(di), int(disparityType) | int(subpixel or 0),
                                         int(algorithmType), winSize, minDisparity, numDisparity, pv, 0 if vol is None else vol.size)
         if not self._finish(rc, "asw_stereo_match"):
             return (None, None) if return_cost_volume else None
@@ -465,9 +469,10 @@ class Context:
         ri, ra = _image(right)
         self._strict(self._lib.asw_upload_pair(self._h, slot, C.byref(li), C.byref(ri)), "asw_upload_pair")
 
-    def match_resident(self, slot, disparityType, algorithmType, winSize, minDisparity, numDisparity, keep_volume=False):
-        rc = self._lib.asw_match_resident(self._h, slot, int(disparityType), int(algorithmType), winSize, minDisparity,
-                                          numDisparity, 1 if keep_volume else 0)
+    def match_resident(self, slot, disparityType, algorithmType, winSize, minDisparity, numDisparity, keep_volume=False,
+                       subpixel=None):
+        rc = self._lib.asw_match_resident(self._h, slot, int(disparityType) | int(subpixel or 0), int(algorithmType), winSize,
+                                          minDisparity, numDisparity, 1 if keep_volume else 0)
         self._strict(rc, "asw_match_resident")
 
     def match_refined_resident(self, slot, algorithmType, winSize, minDisparity, numDisparity, maxDiff=1.0, refineWin=15,
@@ -528,8 +533,9 @@ class Context:
 
 
 def stereoMatchingBatch(lefts, rights, disparityType, algorithmType, winSize=15, minDisparity=0, numDisparity=64,
-                        device_ids=None, out=None):
+                        device_ids=None, out=None, subpixel=None):
     """asw_stereo_match_batch: frame i -> device device_ids[i % len(device_ids)], one host thread per device.
+    subpixel: None, SUBPIXEL_PARABOLA or SUBPIXEL_EQUIANGULAR, OR-ed into disparityType.
 
     out: optional list of C-contiguous float32 (H, W) arrays to receive the disparities (a frame loop that reuses its
     output buffers avoids first-touch page faults on 8 MB per 1080p frame)."""
@@ -556,7 +562,7 @@ def stereoMatchingBatch(lefts, rights, disparityType, algorithmType, winSize=15,
         keep.append((la, ra))
         outs.append(o)
     devs = (C.c_int * len(device_ids))(*device_ids)
-    rc = lib.asw_stereo_match_batch(n, L, R, D, int(disparityType), int(algorithmType), winSize, minDisparity, numDisparity,
+    rc = lib.asw_stereo_match_batch(n, L, R, D, int(disparityType) | int(subpixel or 0), int(algorithmType), winSize, minDisparity, numDisparity,
                                     len(device_ids), devs)
     _state.status = rc
     if rc in _SILENT:

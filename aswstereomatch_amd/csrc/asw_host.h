@@ -12,7 +12,8 @@
     } while (0)
 
 struct MatchParams {
-    int disparity_type, win, minD, numD;
+    int disparity_type, win, minD, numD;  // disparity_type as the caller passed it; run_method strips the sub-pixel flag into `subpixel`
+    int subpixel = 0;                   // 0 | ASW_DISPARITY_SUBPIXEL_PARABOLA | ASW_DISPARITY_SUBPIXEL_EQUIANGULAR
     double gamma_c = 30, gamma_g = 20;  // M.cpp:58
     double eps = 1e-6;                  // M.cpp:73,76
     double rate_s = 10, rate_r = 10;    // M.cpp:82

@@ -119,6 +119,10 @@ int launch_rgb2gray(hipStream_t s, const uint8_t* bgr, int H, int W, uint8_t* gr
 int launch_cost_ad(hipStream_t s, const uint8_t* L, const uint8_t* R, int H, int W, int C, int disp_type, int minD,
                    int numD, int do_thresh /* 0: AD, 1: TAD mask, 2: SD */, int threshold, uint8_t* cost);
 int launch_wta(hipStream_t s, const float* vol, int n, int H, int W, int minD, float* disp);
+// ---- sub-pixel disparity (k_subpixel.hip), DESIGN.md section 4.11 ----
+// mode: ASW_DISPARITY_SUBPIXEL_PARABOLA | ASW_DISPARITY_SUBPIXEL_EQUIANGULAR; vol [n][H][W] (plane k <-> disparity minD + k);
+// disp [H][W]: the integer winner-take-all map, refined in place
+int launch_subpixel(hipStream_t s, int mode, const float* vol, int n, int H, int W, int minD, float* disp);
 
 struct BilateralLaunch {
     const uint8_t* gL;

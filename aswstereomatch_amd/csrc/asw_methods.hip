@@ -789,32 +789,57 @@ int bm_prepare(asw_ctx* ctx, const BmParams& p, int H, int W, BmLaunch* out)
     return ASW_OK;
 }
 
-int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp, bool keep_volume, bool sync)
+// Sub-pixel flags of a caller's disparity_type -> mp.subpixel, mp.disparity_type without them.  A value
+// without a flag bit passes through as it is: the methods refuse what they refused before, with the statuses they had.
+static int decode_subpixel(int algorithm, MatchParams& mp)
+{
+    const int flags = ASW_DISPARITY_SUBPIXEL_PARABOLA | ASW_DISPARITY_SUBPIXEL_EQUIANGULAR;
+    mp.subpixel = 0;
+    // SGBM ignores disparity_type altogether; BM is not served whatever it holds
+    if (algorithm == ASW_ALG_SGBM || algorithm == ASW_ALG_BM || !(mp.disparity_type & flags)) return ASW_OK;
+    if ((mp.disparity_type & flags) == flags) return ASW_ERR_BAD_ARGUMENT;
+    if (mp.disparity_type & ~(flags | ASW_DISPARITY_RIGHT)) return ASW_ERR_BAD_ARGUMENT;
+    // computeNCC's disparity overload has its own candidate range and no selector volume in the RIGHT view
+    if (algorithm == ASW_ALG_NCC) return ASW_ERR_UNSUPPORTED_METHOD;
+    mp.subpixel = mp.disparity_type & flags;
+    mp.disparity_type &= ~flags;
+    return ASW_OK;
+}
+
+int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp_in, bool keep_volume, bool sync)
 {
     f->invalidate_results();  // whatever the slot's disparity / volume were, they are not this call's
+    MatchParams mp = mp_in;
     if (mp.numD <= 0 || mp.minD < 0) return ASW_ERR_BAD_ARGUMENT;
+    ASW_TRY(decode_subpixel(algorithm, mp));
+    // the sub-pixel kernel reads the aggregated volume: the methods that can skip it (bilateral / direct8, geodesic, BLO1, the
+    // bilateral grid) are asked for it; what the CALLER keeps is decided below
+    const bool want_volume = keep_volume || mp.subpixel != 0;
     ASW_HIP_TRY(hipSetDevice(ctx->device));
     ASW_HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
     int rc;
     switch (algorithm) {  // M.cpp:49-87
-    case ASW_ALG_ADAPTIVE_WEIGHT: rc = run_bilateral(ctx, f, mp, keep_volume); break;
-    case ASW_ALG_ADAPTIVE_WEIGHT_8DIRECT: rc = run_bilateral(ctx, f, mp, keep_volume, true); break;
-    case ASW_ALG_ADAPTIVE_WEIGHT_GEODESIC: rc = run_geodesic(ctx, f, mp, keep_volume); break;
-    case ASW_ALG_ADAPTIVE_WEIGHT_BILATERAL_GRID: rc = run_bilgrid(ctx, f, mp, keep_volume); break;
-    case ASW_ALG_ADAPTIVE_WEIGHT_BLO1: rc = run_blo1(ctx, f, mp, keep_volume); break;
-    case ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER: rc = run_guided(ctx, f, mp, keep_volume, GUIDED_SAD6); break;
-    case ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER_2: rc = run_guided(ctx, f, mp, keep_volume, GUIDED_SIM3); break;
-    case ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER_3: rc = run_guided(ctx, f, mp, keep_volume, GUIDED_NCC); break;
-    case ASW_ALG_NCC: rc = run_ncc(ctx, f, mp, keep_volume); break;
-    case ASW_ALG_ADAPTIVE_WEIGHT_MEDIAN: rc = run_wmedian(ctx, f, mp, keep_volume); break;
+    case ASW_ALG_ADAPTIVE_WEIGHT: rc = run_bilateral(ctx, f, mp, want_volume); break;
+    case ASW_ALG_ADAPTIVE_WEIGHT_8DIRECT: rc = run_bilateral(ctx, f, mp, want_volume, true); break;
+    case ASW_ALG_ADAPTIVE_WEIGHT_GEODESIC: rc = run_geodesic(ctx, f, mp, want_volume); break;
+    case ASW_ALG_ADAPTIVE_WEIGHT_BILATERAL_GRID: rc = run_bilgrid(ctx, f, mp, want_volume); break;
+    case ASW_ALG_ADAPTIVE_WEIGHT_BLO1: rc = run_blo1(ctx, f, mp, want_volume); break;
+    case ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER: rc = run_guided(ctx, f, mp, want_volume, GUIDED_SAD6); break;
+    case ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER_2: rc = run_guided(ctx, f, mp, want_volume, GUIDED_SIM3); break;
+    case ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER_3: rc = run_guided(ctx, f, mp, want_volume, GUIDED_NCC); break;
+    case ASW_ALG_NCC: rc = run_ncc(ctx, f, mp, want_volume); break;
+    case ASW_ALG_ADAPTIVE_WEIGHT_MEDIAN: rc = run_wmedian(ctx, f, mp, want_volume); break;
     case ASW_ALG_SGBM: rc = run_sgbm(ctx, f, mp); break;
     default: rc = ASW_ERR_UNSUPPORTED_METHOD; break;
     }
+    if (rc == ASW_OK && mp.subpixel)  // after the aggregation events: counts in total_ms and cost_ms, not in aggregate_ms
+        rc = launch_subpixel(ctx->stream, mp.subpixel, f->vol.as<float>(), asw_volume_planes(algorithm, mp.numD), f->rows, f->cols,
+                             mp.minD, f->disp.as<float>());
     if (rc != ASW_OK) {
         f->invalidate_results();
         return rc;
     }
-    const size_t kept_floats = f->vol_floats;
+    const size_t kept_floats = keep_volume ? f->vol_floats : 0;  // a volume asked for by the sub-pixel step alone is not the caller's
     f->vol_floats = 0;  // restored together with has_disp once nothing can fail any more
     ASW_HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
     if (!sync) {  // pipelined callers (batch scheduler) order and wait on the stream themselves

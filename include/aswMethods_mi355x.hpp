@@ -41,6 +41,8 @@ enum StereoMatchingAlgorithms {
     ADAPTIVE_WEIGHT_GUIDED_FILTER_2 = 8, ADAPTIVE_WEIGHT_GUIDED_FILTER_3 = 9, ADAPTIVE_WEIGHT_MEDIAN = 10, NCC = 11
 };
 #endif
+// Not in the reference: the sub-pixel rules of asw_mi355x.h (ASW_DISPARITY_SUBPIXEL_*), for stereoMatchingSubpixel below
+enum SubpixelMethod { SUBPIXEL_PARABOLA = ASW_DISPARITY_SUBPIXEL_PARABOLA, SUBPIXEL_EQUIANGULAR = ASW_DISPARITY_SUBPIXEL_EQUIANGULAR };
 
 namespace asw {
 
@@ -199,6 +201,21 @@ inline void stereoMatching(AswMat srcLeft, AswMat srcRight, AswMat& disparityMap
         return asw_stereo_match(c, l, r, o, (int)disparityType, (int)algorithmType, winSize, minDisparity, numDisparity, nullptr, 0);
     }, "stereoMatching");
     disparityMap = d;  // `disparityMap = computeAdaptiveWeight...(...)`, M.cpp:58-82 (empty Mat on silent errors)
+}
+
+// Not in the reference: stereoMatching with a sub-pixel disparity map -- the method's winner-take-all
+// map, every pixel moved by at most half a disparity along the parabola / the equiangular V through the three aggregated costs
+// around its winner.  Silent errors leave an empty Mat like stereoMatching; SGBM (its CV_8U map has no fraction), BM and NCC throw.
+inline void stereoMatchingSubpixel(AswMat srcLeft, AswMat srcRight, AswMat& disparityMap, DisparityType disparityType,
+                                   StereoMatchingAlgorithms algorithmType, int winSize = 15, int minDisparity = 0, int numDisparity = 64,
+                                   SubpixelMethod method = SUBPIXEL_PARABOLA)
+{
+    if (algorithmType == SGBM) throw std::runtime_error("stereoMatchingSubpixel: SGBM has no sub-pixel form here");
+    AswMat d = asw::detail::aggregate(srcLeft, srcRight, [&](asw_ctx* c, asw_image* l, asw_image* r, asw_image* o) {
+        return asw_stereo_match(c, l, r, o, (int)disparityType | (int)method, (int)algorithmType, winSize, minDisparity, numDisparity,
+                                nullptr, 0);
+    }, "stereoMatchingSubpixel");
+    disparityMap = d;
 }
 
 // M.h:101-102

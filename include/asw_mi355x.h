@@ -46,6 +46,21 @@ typedef enum asw_status {
 /* parametersStereo.h:4-8 */
 enum { ASW_DISPARITY_LEFT = 0, ASW_DISPARITY_RIGHT = 1 };
 
+/* Sub-pixel disparity (not in the reference): one of these flags OR-ed into the disparity_type of
+ * asw_stereo_match, asw_match_resident, every asw_aggregate_* and asw_stereo_match_batch.  The low bit keeps its meaning and all
+ * its statuses.  After the method's own winner-take-all every pixel whose winner k = d - min_d has two neighbours in the
+ * aggregated volume V (0 < k < asw_volume_planes() - 1), all three costs finite, cm = V[k-1] >= c0 = V[k] <= cp = V[k+1] and
+ * den > 0 becomes (float)((double)d + clamp((cm - cp) / (2 * den), -0.5, 0.5)), all in f64, one IEEE operation each:
+ *   PARABOLA     den = (cm - c0) + (cp - c0)
+ *   EQUIANGULAR  den = max(cm, cp) - c0
+ * Every other pixel keeps d.  The map becomes the call's / the slot's disparity (asw_download_disparity, asw_download_disparity_u8);
+ * the volume a flagged call returns is the unflagged one, and without keep_volume / cost_volume_out none is kept.
+ * Both flags, or a flag with any other bit beside bit 0: ASW_ERR_BAD_ARGUMENT, before the method's own checks (a value with
+ * neither flag is refused by the method as before).  ASW_ALG_NCC (and asw_ncc_disparity) with a flag: ASW_ERR_UNSUPPORTED_METHOD;
+ * ASW_ALG_BM: ASW_ERR_UNSUPPORTED_METHOD as without; ASW_ALG_SGBM ignores disparity_type altogether.  The cost builders, asw_wta
+ * and the refined calls do not take the flags.  asw_get_timing: the extra kernel counts in total_ms and cost_ms. */
+enum { ASW_DISPARITY_SUBPIXEL_PARABOLA = 0x100, ASW_DISPARITY_SUBPIXEL_EQUIANGULAR = 0x200 };
+
 /* parametersStereo.h:10-24 (StereoMatchingAlgorithms) */
 enum {
     ASW_ALG_BM = 0,
