@@ -5,6 +5,12 @@
 Every method of the selector is run through the C-ABI on random shapes / windows / disparity ranges / directions and
 compared with the CPU oracle: WTA index bit-exact everywhere; cost volume bit-exact for the methods whose summation
 order the kernels reproduce, within 1e-4 (relative) for the guided-filter family.
+
+The legs sgbm, bm, speckles, refine and subpixel draw their cases from tests/matcher_cases.py (tie-dense inputs in rotation with
+textured ones, frames from one pixel up, padded rows) and compare exactly with the restatements under tests/; a mismatch prints
+the tag that matcher_cases.build_case(leg, tag[1:]) rebuilds the case from.
+
+    python tools/fuzz_parity.py --seconds 120 --seed 1 --only sgbm,bm,speckles,refine,subpixel
 """
 import argparse
 import os
@@ -18,7 +24,13 @@ import aswstereomatch_amd as asw  # noqa: E402
 from aswstereomatch_amd.synth import make_pair  # noqa: E402
 from oracle import asw_oracle as O  # noqa: E402
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+import matcher_cases as mc  # noqa: E402
+
 A = asw.StereoMatchingAlgorithms
+# checked against the CPU oracle (oracle/); the legs mc.FAMILIES are checked against the restatements under tests/
+ORACLE_METHODS = ["classic", "direct8", "geodesic", "guided", "guided2", "guided3", "wmedian", "blo1", "ncc", "ncc_cost",
+                  "ad_tad", "similarity", "sad", "geodist", "gfilter", "prep", "bilgrid", "lrcheck", "resident", "batch"]
 
 
 def close(a, b):
@@ -42,6 +54,15 @@ def main():
     ap.add_argument("--wm15", type=float, default=0.0, help="share of the cases forced to the 15x15 weighted median (the tile form, k_wmedian_tile.hip)")
     args = ap.parse_args()
     rng = np.random.default_rng(args.seed)
+    # The legs of tests/matcher_cases.py draw from a generator of their own and skip the generic draw below, so a seed gives the
+    # oracle-checked methods the cases it always gave them, with the legs' cases in between (a fifth of all cases by default).
+    rng_mc = np.random.default_rng([args.seed, 1])
+    names = args.only.split(",") if args.only else ORACLE_METHODS + list(mc.FAMILIES)
+    unknown = [m for m in names if m not in ORACLE_METHODS and m not in mc.FAMILIES]
+    if unknown:
+        ap.error("unknown method(s): %s" % ",".join(unknown))
+    legs = [m for m in names if m in mc.FAMILIES]
+    leg_share = len(legs) / len(names)
     ctx = asw.Context(0)
     O.set_threads(O.usable_cores())
     t0 = time.time()
@@ -49,67 +70,73 @@ def main():
     counts = {}
     last = t0
     while time.time() - t0 < args.seconds:
-        H = int(rng.integers(1, args.max_h))
-        W = int(rng.integers(1, args.max_w))
-        win = int(rng.choice([1, 3, 5, 7, 9, 11, 15, 17, 21, 25, 33, 35]))
-        minD = int(rng.choice([0, 0, 0, 1, 3, 17]))
-        numD = int(rng.integers(1, 48))
-        if rng.random() < 0.08:  # long candidate ranges cross the 16-wide chunk and z-split boundaries
-            numD = int(rng.integers(48, 150))
-            H, W = min(H, 24), min(W, 96)
-        dt = int(rng.integers(0, 2))
-        if win > 21:  # big windows: keep the CPU side in the millisecond range
-            H, W, numD = min(H, 40), min(W, 120), min(numD, 12)
-        seed = int(rng.integers(0, 1 << 30))
-        L, R, _ = make_pair(H, W, max(2, numD // 2), seed=seed, block=int(rng.choice([4, 8, 16])))
-        if rng.random() < args.flat:
-            for img in (L, R):
-                for _ in range(int(rng.integers(1, 4))):
-                    y0, x0 = int(rng.integers(0, H)), int(rng.integers(0, W))
-                    img[y0:y0 + int(rng.integers(1, 12)), x0:x0 + int(rng.integers(1, 40))] = rng.integers(0, 256, 3).astype(np.uint8)
-        if rng.random() < 0.15:  # rows with padding: the C-ABI reads them through asw_image.step
-            pad = int(rng.integers(1, 9))
-            Lp = np.zeros((H, W + pad, 3), np.uint8)
-            Rp = np.full((H, W + pad, 3), 255, np.uint8)
-            Lp[:, :W], Rp[:, :W] = L, R
-            L, R = Lp[:, :W], Rp[:, :W]   # non-contiguous views; the oracle wrappers copy them
-        method = str(rng.choice(["classic", "direct8", "geodesic", "guided", "guided2", "guided3", "wmedian", "blo1", "ncc", "ncc_cost",
-                                "ad_tad", "similarity", "sad", "geodist", "gfilter", "prep", "bilgrid", "lrcheck", "resident", "batch"]))
-        if args.only:
-            method = str(rng.choice(args.only.split(",")))
-        if rng.random() < args.xq:
-            method = str(rng.choice(["classic", "geodesic"]))
-            H, W = int(rng.integers(1, 10)), int(rng.integers(64, 420))
-            win, dt = 15, int(rng.integers(0, 2))   # both directions have an xq form
-            minD = int(rng.choice([0, 0, 1, 5, 48, 49, 70])) if method == "classic" else int(rng.choice([0, 0, 2, 33, 130]))
-            numD = int(rng.choice([63, 64, 65, 100, 126, 127, 128, 129, 191, 192, 255, int(rng.integers(63, 128)), int(rng.integers(63, 300))]))
+        if rng_mc.random() < leg_share:  # the integer kernels: inputs and every parameter come from tests/matcher_cases.py
+            method = legs[int(rng_mc.integers(0, len(legs)))]
+            case = mc.random_case(rng_mc, method, n)
+            tag = (method,) + case["tag"]
+        else:
+            H = int(rng.integers(1, args.max_h))
+            W = int(rng.integers(1, args.max_w))
+            win = int(rng.choice([1, 3, 5, 7, 9, 11, 15, 17, 21, 25, 33, 35]))
+            minD = int(rng.choice([0, 0, 0, 1, 3, 17]))
+            numD = int(rng.integers(1, 48))
+            if rng.random() < 0.08:  # long candidate ranges cross the 16-wide chunk and z-split boundaries
+                numD = int(rng.integers(48, 150))
+                H, W = min(H, 24), min(W, 96)
+            dt = int(rng.integers(0, 2))
+            if win > 21:  # big windows: keep the CPU side in the millisecond range
+                H, W, numD = min(H, 40), min(W, 120), min(numD, 12)
             seed = int(rng.integers(0, 1 << 30))
-            L, R, _ = make_pair(H, W, max(2, min(numD, W) // 2), seed=seed, block=int(rng.choice([4, 8, 16])))
-            if rng.random() < 0.3:
+            L, R, _ = make_pair(H, W, max(2, numD // 2), seed=seed, block=int(rng.choice([4, 8, 16])))
+            if rng.random() < args.flat:
                 for img in (L, R):
-                    y0, x0 = int(rng.integers(0, H)), int(rng.integers(0, W))
-                    img[y0:y0 + int(rng.integers(1, 6)), x0:x0 + int(rng.integers(1, 60))] = rng.integers(0, 256, 3).astype(np.uint8)
-        if rng.random() < args.wm15:
-            method, win, dt = "wmedian", 15, 0
-            numD = int(rng.integers(1, 40))
-        if rng.random() < args.wmbig:
-            method, win, dt = "wmedian", int(rng.choice([3, 5, 7, 9, 11, 13, 17, 19, 21, 23, 25, 27, 29, 31, 33, 35, 37, 39, 41])), 0
-            H, W, numD = int(rng.integers(1, 36)), int(rng.integers(1, 90)), int(rng.integers(1, 20))
-            minD = int(rng.choice([0, 0, 1, 4]))
-            seed = int(rng.integers(0, 1 << 30))
-            L, R, _ = make_pair(H, W, max(2, min(numD, W) // 2), seed=seed, block=int(rng.choice([4, 8, 16])))
-            if rng.random() < 0.3:  # flat rectangles: ties
-                for img in (L, R):
-                    y0, x0 = int(rng.integers(0, H)), int(rng.integers(0, W))
-                    img[y0:y0 + int(rng.integers(1, 12)), x0:x0 + int(rng.integers(1, 40))] = rng.integers(0, 256, 3).astype(np.uint8)
-        tag = (method, H, W, win, minD, numD, dt, seed)
+                    for _ in range(int(rng.integers(1, 4))):
+                        y0, x0 = int(rng.integers(0, H)), int(rng.integers(0, W))
+                        img[y0:y0 + int(rng.integers(1, 12)), x0:x0 + int(rng.integers(1, 40))] = rng.integers(0, 256, 3).astype(np.uint8)
+            if rng.random() < 0.15:  # rows with padding: the C-ABI reads them through asw_image.step
+                pad = int(rng.integers(1, 9))
+                Lp = np.zeros((H, W + pad, 3), np.uint8)
+                Rp = np.full((H, W + pad, 3), 255, np.uint8)
+                Lp[:, :W], Rp[:, :W] = L, R
+                L, R = Lp[:, :W], Rp[:, :W]   # non-contiguous views; the oracle wrappers copy them
+            method = str(rng.choice(ORACLE_METHODS))
+            if args.only:
+                method = str(rng.choice([m for m in names if m not in mc.FAMILIES]))
+            if rng.random() < args.xq:
+                method = str(rng.choice(["classic", "geodesic"]))
+                H, W = int(rng.integers(1, 10)), int(rng.integers(64, 420))
+                win, dt = 15, int(rng.integers(0, 2))   # both directions have an xq form
+                minD = int(rng.choice([0, 0, 1, 5, 48, 49, 70])) if method == "classic" else int(rng.choice([0, 0, 2, 33, 130]))
+                numD = int(rng.choice([63, 64, 65, 100, 126, 127, 128, 129, 191, 192, 255, int(rng.integers(63, 128)), int(rng.integers(63, 300))]))
+                seed = int(rng.integers(0, 1 << 30))
+                L, R, _ = make_pair(H, W, max(2, min(numD, W) // 2), seed=seed, block=int(rng.choice([4, 8, 16])))
+                if rng.random() < 0.3:
+                    for img in (L, R):
+                        y0, x0 = int(rng.integers(0, H)), int(rng.integers(0, W))
+                        img[y0:y0 + int(rng.integers(1, 6)), x0:x0 + int(rng.integers(1, 60))] = rng.integers(0, 256, 3).astype(np.uint8)
+            if rng.random() < args.wm15:
+                method, win, dt = "wmedian", 15, 0
+                numD = int(rng.integers(1, 40))
+            if rng.random() < args.wmbig:
+                method, win, dt = "wmedian", int(rng.choice([3, 5, 7, 9, 11, 13, 17, 19, 21, 23, 25, 27, 29, 31, 33, 35, 37, 39, 41])), 0
+                H, W, numD = int(rng.integers(1, 36)), int(rng.integers(1, 90)), int(rng.integers(1, 20))
+                minD = int(rng.choice([0, 0, 1, 4]))
+                seed = int(rng.integers(0, 1 << 30))
+                L, R, _ = make_pair(H, W, max(2, min(numD, W) // 2), seed=seed, block=int(rng.choice([4, 8, 16])))
+                if rng.random() < 0.3:  # flat rectangles: ties
+                    for img in (L, R):
+                        y0, x0 = int(rng.integers(0, H)), int(rng.integers(0, W))
+                        img[y0:y0 + int(rng.integers(1, 12)), x0:x0 + int(rng.integers(1, 40))] = rng.integers(0, 256, 3).astype(np.uint8)
+            tag = (method, H, W, win, minD, numD, dt, seed)
         if args.fresh_every > 0 and n > 0 and n % args.fresh_every == 0:
             ctx.close()
             ctx = asw.Context(0)
         if args.trace:
             print("case", n, tag, flush=True)
         try:
-            if method == "classic":
+            if method in mc.FAMILIES:
+                ok = mc.same(*mc.gpu_result(ctx, case))
+            elif method == "classic":
                 gc, gg = float(rng.choice([30, 5, 0.5, 100])), float(rng.choice([20, 2, 7.5, 60]))
                 rc, dw, vw = O.asw_classic(L, R, gc, gg, dt, win, minD, numD, want_vol=True)
                 d, v = ctx.computeAdaptiveWeight(L, R, gc, gg, dt, win, minD, numD, return_cost_volume=True)
