@@ -26,9 +26,11 @@ __all__ = [
     "computeAdaptiveWeight_geodesic", "getGeodesicDist", "getGuidedFilter", "computeAdaptiveWeight_GuidedF",
     "computeAdaptiveWeight_GuidedF_2", "computeAdaptiveWeight_WeightedMedian", "winnerTakeAll", "last_status",
     "stereoMatchingBatch", "computeAdaptiveWeight_BLO1", "computeAdaptiveWeight_direct8", "computeNCC", "computeNCC_costs",
-    "computeAdaptiveWeight_GuidedF_3", "getDisparity_SGBM", "sgbm", "filterSpeckles", "getDisparity_BM", "stereoBM",
+    "computeAdaptiveWeight_GuidedF_3", "getDisparity_SGBM", "sgbm", "sgbm_paths", "filterSpeckles", "getDisparity_BM", "stereoBM",
     "PREFILTER_NORMALIZED_RESPONSE", "PREFILTER_XSOBEL", "refineDisparity", "stereoMatchingRefined",
     "REFINE_GAMMA_C", "REFINE_GAMMA_S", "SUBPIXEL_PARABOLA", "SUBPIXEL_EQUIANGULAR",
+    "SGBM_PATH_LR", "SGBM_PATH_RL", "SGBM_PATH_TB", "SGBM_PATH_BT", "SGBM_PATH_TLBR", "SGBM_PATH_TRBL", "SGBM_PATH_BRTL",
+    "SGBM_PATH_BLTR", "SGBM_PATHS_3WAY", "SGBM_PATHS_HH4", "SGBM_PATHS_SGBM", "SGBM_PATHS_HH",
     "AswError",
 ]
 
@@ -62,6 +64,11 @@ SUBPIXEL_PARABOLA, SUBPIXEL_EQUIANGULAR = 0x100, 0x200
 OK, ERR_SIZE_MISMATCH, ERR_EVEN_WINDOW, ERR_UNSUPPORTED_METHOD, ERR_UNSUPPORTED_LAYOUT = 0, 1, 2, 3, 4
 ERR_HIP, ERR_ALLOC, ERR_BAD_ARGUMENT, ERR_NO_FRAME = 5, 6, 7, 8
 MODE_SGBM_3WAY = 2  # StereoSGBM::MODE_SGBM_3WAY, the one mode asw_sgbm serves
+# path directions of asw_sgbm_paths (asw_mi355x.h: ASW_SGBM_PATH_* / ASW_SGBM_PATHS_*)
+(SGBM_PATH_LR, SGBM_PATH_RL, SGBM_PATH_TB, SGBM_PATH_BT, SGBM_PATH_TLBR, SGBM_PATH_TRBL, SGBM_PATH_BRTL,
+ SGBM_PATH_BLTR) = (1 << _i for _i in range(8))
+SGBM_PATHS_3WAY, SGBM_PATHS_HH4, SGBM_PATHS_SGBM, SGBM_PATHS_HH = 0x07, 0x0F, 0x37, 0xFF
+_SGBM_MODE_PATHS = 0x40000000  # ASW_SGBM_MODE_PATHS: asw_sgbm's mode carrying a path mask, as the header's inline asw_sgbm_paths forms it
 PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL = 0, 1  # StereoBM::PREFILTER_*; asw_stereo_bm serves XSOBEL
 REFINE_GAMMA_C, REFINE_GAMMA_S = 60.0, 9.0  # default colour / distance gammas of the refinement's weighted median (asw_mi355x.h)
 # statuses for which the reference returns silently / an empty Mat
@@ -263,6 +270,21 @@ class Context:
              uniquenessRatio=0, speckleWindowSize=0, speckleRange=0, mode=MODE_SGBM_3WAY, return_cost_volume=False):
         """StereoSGBM::create(...) + compute(): int16 disparity x 16 (invalid: 16 * (minDisparity - 1)); with return_cost_volume
         also the aggregated cost S, float32 [numDisparities][H][W] (asw_sgbm)."""
+        return self._sgbm_call("asw_sgbm", left, right, minDisparity, numDisparities, blockSize, P1, P2, disp12MaxDiff, preFilterCap,
+                               uniquenessRatio, speckleWindowSize, speckleRange, int(mode), return_cost_volume)
+
+    def sgbm_paths(self, left, right, minDisparity, numDisparities, blockSize, P1=0, P2=0, disp12MaxDiff=0, preFilterCap=0,
+                   uniquenessRatio=0, speckleWindowSize=0, speckleRange=0, paths=SGBM_PATHS_HH, return_cost_volume=False):
+        """sgbm with the aggregated cost summed over the path directions of `paths` (an OR of SGBM_PATH_*, a superset of
+        SGBM_PATHS_3WAY) instead of the three of MODE_SGBM_3WAY; SGBM_PATHS_3WAY gives sgbm's result
+        (asw_sgbm_paths of asw_mi355x.h: asw_sgbm with the mask packed into its mode)."""
+        mask = 0x100 if int(paths) & ~SGBM_PATHS_HH else int(paths)  # an invalid mask travels as the invalid mask 0x100
+        return self._sgbm_call("asw_sgbm_paths", left, right, minDisparity, numDisparities, blockSize, P1, P2, disp12MaxDiff,
+                               preFilterCap, uniquenessRatio, speckleWindowSize, speckleRange, _SGBM_MODE_PATHS | mask,
+                               return_cost_volume)
+
+    def _sgbm_call(self, where, left, right, minDisparity, numDisparities, blockSize, P1, P2, disp12MaxDiff, preFilterCap,
+                   uniquenessRatio, speckleWindowSize, speckleRange, mode, return_cost_volume):
         li, la = _image(left)
         ri, ra = _image(right)
         disp = np.zeros(la.shape[:2], np.int16)
@@ -272,9 +294,9 @@ class Context:
             vol = np.zeros((numDisparities,) + la.shape[:2], np.float32)
             pv = vol.ctypes.data_as(C.c_void_p)
         rc = self._lib.asw_sgbm(self._h, C.byref(li), C.byref(ri), C.byref(di), minDisparity, numDisparities, blockSize, P1, P2,
-                                disp12MaxDiff, preFilterCap, uniquenessRatio, speckleWindowSize, speckleRange, int(mode), pv,
+                                disp12MaxDiff, preFilterCap, uniquenessRatio, speckleWindowSize, speckleRange, mode, pv,
                                 0 if vol is None else vol.size)
-        self._strict(rc, "asw_sgbm")
+        self._strict(rc, where)
         return (disp, vol) if return_cost_volume else disp
 
     # ---- block matching ----
@@ -615,6 +637,7 @@ computeAdaptiveWeight_BLO1 = _bind("computeAdaptiveWeight_BLO1")
 winnerTakeAll = _bind("winnerTakeAll")
 getDisparity_SGBM = _bind("getDisparity_SGBM")
 sgbm = _bind("sgbm")
+sgbm_paths = _bind("sgbm_paths")
 filterSpeckles = _bind("filterSpeckles")
 getDisparity_BM = _bind("getDisparity_BM")
 stereoBM = _bind("stereoBM")

@@ -563,10 +563,11 @@ static int timed_finish(asw_ctx* ctx)
     return ASW_OK;
 }
 
-extern "C" int asw_sgbm(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp16, int min_disparity,
-                        int num_disparities, int block_size, int p1, int p2, int disp12_max_diff, int pre_filter_cap,
-                        int uniqueness_ratio, int speckle_window_size, int speckle_range, int mode, float* cost_volume_out,
-                        size_t cost_volume_floats)
+// asw_sgbm: mode 2 with the three paths of MODE_SGBM_3WAY, or with the mask that asw_sgbm_paths packed into mode
+static int sgbm_host(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp16, int min_disparity,
+                     int num_disparities, int block_size, int p1, int p2, int disp12_max_diff, int pre_filter_cap,
+                     int uniqueness_ratio, int speckle_window_size, int speckle_range, int mode, int paths, float* cost_volume_out,
+                     size_t cost_volume_floats)
 {
     if (!ctx) return ASW_ERR_BAD_ARGUMENT;
     ASW_TRY(check_pair(left, right));
@@ -577,7 +578,7 @@ extern "C" int asw_sgbm(asw_ctx* ctx, const asw_image* left, const asw_image* ri
     SgbmParams p;
     p.minD = min_disparity; p.numD = num_disparities; p.block_size = block_size; p.P1 = p1; p.P2 = p2;
     p.disp12_max_diff = disp12_max_diff; p.pre_filter_cap = pre_filter_cap; p.uniqueness_ratio = uniqueness_ratio;
-    p.speckle_window_size = speckle_window_size; p.speckle_range = speckle_range; p.mode = mode;
+    p.speckle_window_size = speckle_window_size; p.speckle_range = speckle_range; p.mode = mode; p.paths = paths;
     ASW_HIP_TRY(hipSetDevice(ctx->device));
     SgbmLaunch a;
     ASW_TRY(sgbm_prepare(ctx, p, H, W, left->channels, cost_volume_out != nullptr, &a));
@@ -594,13 +595,29 @@ extern "C" int asw_sgbm(asw_ctx* ctx, const asw_image* left, const asw_image* ri
     ASW_HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
     ASW_TRY(launch_sgbm(ctx->stream, a));
     ASW_TRY(timed_finish(ctx));
-    ctx->timing.aggregate_launches = 2;
+    // k_sgbm_top, k_sgbm_row + one k_sgbm_line per line geometry in use (columns, diagonals, anti-diagonals)
+    ctx->timing.aggregate_launches = 2 + !!(paths & ASW_SGBM_PATH_BT) + !!(paths & (ASW_SGBM_PATH_TLBR | ASW_SGBM_PATH_BRTL)) +
+                                     !!(paths & (ASW_SGBM_PATH_TRBL | ASW_SGBM_PATH_BLTR));
     ASW_HIP_TRY(copy_rows(ctx, disp16->data, disp16->step, a.disp16, (size_t)W * sizeof(short), (size_t)W * sizeof(short), H,
                           hipMemcpyDeviceToHost));
     if (cost_volume_out)
         ASW_HIP_TRY(hipMemcpyAsync(cost_volume_out, vol.p, vol_floats * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ASW_OK;
+}
+
+extern "C" int asw_sgbm(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp16, int min_disparity,
+                        int num_disparities, int block_size, int p1, int p2, int disp12_max_diff, int pre_filter_cap,
+                        int uniqueness_ratio, int speckle_window_size, int speckle_range, int mode, float* cost_volume_out,
+                        size_t cost_volume_floats)
+{
+    int paths = ASW_SGBM_PATHS_3WAY;
+    if (mode > 0 && (mode & ASW_SGBM_MODE_PATHS)) {  // asw_sgbm_paths (asw_mi355x.h): the three-path pipeline over a path mask
+        paths = mode & ~ASW_SGBM_MODE_PATHS;
+        mode = 2;
+    }
+    return sgbm_host(ctx, left, right, disp16, min_disparity, num_disparities, block_size, p1, p2, disp12_max_diff, pre_filter_cap,
+                     uniqueness_ratio, speckle_window_size, speckle_range, mode, paths, cost_volume_out, cost_volume_floats);
 }
 
 extern "C" int asw_filter_speckles(asw_ctx* ctx, asw_image* img, int new_val, int max_speckle_size, int max_diff)

@@ -42,6 +42,7 @@ int run_ncc_cost(asw_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int H, int 
 // values of step 0 and sizes the scratch, run_sgbm enqueues the kernels on the context's stream
 struct SgbmParams {
     int minD, numD, block_size, P1, P2, disp12_max_diff, pre_filter_cap, uniqueness_ratio, speckle_window_size, speckle_range, mode;
+    int paths = ASW_SGBM_PATHS_3WAY;  // the ASW_SGBM_PATH_* mask of asw_sgbm_paths (mode stays 2)
 };
 int sgbm_prepare(asw_ctx* ctx, const SgbmParams& p, int H, int W, int cn, bool want_volume, SgbmLaunch* out);
 // StereoBM parameters as StereoBM::create + its setters take them; bm_prepare validates them (step 0) and

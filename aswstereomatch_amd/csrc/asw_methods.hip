@@ -699,12 +699,14 @@ static int run_bilgrid(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_
 int sgbm_prepare(asw_ctx* ctx, const SgbmParams& p, int H, int W, int cn, bool want_volume, SgbmLaunch* out)
 {
     if (p.mode != 2) return ASW_ERR_UNSUPPORTED_METHOD;  // MODE_SGBM_3WAY only
+    if (p.paths & ~ASW_SGBM_PATHS_HH) return ASW_ERR_BAD_ARGUMENT;
+    if ((p.paths & ASW_SGBM_PATHS_3WAY) != ASW_SGBM_PATHS_3WAY) return ASW_ERR_UNSUPPORTED_METHOD;  // the three paths are the frame
     if (p.minD < 0 || p.numD <= 0 || p.numD % 16 != 0 || p.numD > 1024) return ASW_ERR_BAD_ARGUMENT;
     if (cn != 1 && cn != 3) return ASW_ERR_UNSUPPORTED_LAYOUT;
     if (16 * ((long long)p.minD + p.numD) > 32767) return ASW_ERR_BAD_ARGUMENT;  // the scaled map is int16
     if ((size_t)H * W >= ((size_t)1 << 31)) return ASW_ERR_BAD_ARGUMENT;         // pixel indices of the speckle filter are int
     SgbmLaunch a{};
-    a.H = H; a.W = W; a.cn = cn; a.minD = p.minD; a.D = p.numD;
+    a.H = H; a.W = W; a.cn = cn; a.minD = p.minD; a.D = p.numD; a.paths = p.paths;
     // step 0: StereoSGBM::compute's effective parameters
     a.ftzero = std::max(p.pre_filter_cap, 15) | 1;
     a.P1 = p.P1 > 0 ? p.P1 : 2;
@@ -715,9 +717,9 @@ int sgbm_prepare(asw_ctx* ctx, const SgbmParams& p, int H, int W, int cn, bool w
     a.speckle_window = p.speckle_window_size;
     a.speckle_range = (int)std::min<long long>(std::max(p.speckle_range, -(1 << 26)), 1 << 26);  // 16 * range stays an int
     if (a.P1 == INT_MAX) return ASW_ERR_BAD_ARGUMENT;  // P2 >= P1 + 1
-    // every C, L and S is exact in int32: S <= 3 * (C_max + P2); the f32 volume needs the same bound below 2^24
+    // every C, L and S is exact in int32: S <= n * (C_max + P2), n paths; the f32 volume needs the same bound below 2^24
     const double k = 2 * (a.w / 2) + 1;
-    const double bound = 3.0 * ((double)cn * (2.0 * a.ftzero + 63.0) * k * k + a.P2);
+    const double bound = (double)__builtin_popcount(p.paths) * ((double)cn * (2.0 * a.ftzero + 63.0) * k * k + a.P2);
     if (bound >= 2147483648.0) return ASW_ERR_BAD_ARGUMENT;
     if (want_volume && bound >= 16777216.0) return ASW_ERR_BAD_ARGUMENT;
     DevBuf& scratch = ctx->buf("sgbm_scratch");

@@ -1,13 +1,14 @@
 // Semi-global block matching, StereoSGBM MODE_SGBM_3WAY as DESIGN.md section 4.8 states it (OpenCV 4.1.0 stereosgbm.cpp), and
-// cv::filterSpeckles.  Integer arithmetic throughout; every intermediate is exact in 32 bits (the host refuses parameters for which
-// 3 * (C_max + P2) >= 2^31).
+// cv::filterSpeckles; asw_sgbm_paths adds further path directions to the three (section 4.8b).  Integer arithmetic throughout;
+// every intermediate is exact in 32 bits (the host refuses parameters for which n * (C_max + P2) >= 2^31, n paths, n >= 3).
 //
-// Layout: the volumes C (block cost), T (L_tb, then L_tb + L_lr, then S) are int32 [H][Wv][D] with d innermost, over the valid
+// Layout: the volumes C (block cost), T (L_tb, then + the extra paths, + L_lr, then S) are int32 [H][Wv][D] with d innermost, over the valid
 // columns x = x0 + xi, x0 = minX1 = minD + D, Wv = W - x0.  Candidate index d <-> absolute disparity minD + d.
 //
 //   k_sgbm_prefilter  step 1 + the Birchfield-Tomasi interval: {value, min, max} planes of every prefiltered plane
 //   k_sgbm_hcost      steps 2 + horizontal half of 3: one thread per (y, d) walks the row with a running window sum
 //   k_sgbm_top        vertical half of 3 + the top->bottom path: one wavefront per column, candidates in lanes
+//   k_sgbm_line       asw_sgbm_paths only: bottom->top and the four diagonal paths, one wavefront per column / (anti-)diagonal
 //   k_sgbm_row        left->right and right->left paths, winner, uniqueness, subpixel, disp2 keys: one wavefront per row
 //   k_sgbm_lr         the left-right rule of step 6 -> int16 map
 //   k_median3_s16     step 7;  k_spk_*: step 8 (union-find over the whole frame);  k_disp16_to_u8f: step 9
@@ -16,7 +17,7 @@
 
 namespace {
 
-constexpr int SGBM_BIG = 0x3fffffff;  // "no predecessor": above every L (< 2^31 / 3), and BIG + P1 < 2^31
+constexpr int SGBM_BIG = 0x3fffffff;  // "no predecessor": above every L (<= C_max + P2 < 2^31 / 3), and BIG + P1 < 2^31
 
 // {value, min, max} of one prefiltered plane at x of row y; columns 0 and W-1 hold ftzero (OpenCV's border quirk)
 __device__ __forceinline__ int sgbm_pre(const uint8_t* __restrict__ img, int H, int W, int cn, int k, int y, int x, int ftzero)
@@ -247,6 +248,87 @@ __global__ __launch_bounds__(64) void k_sgbm_row(const int* __restrict__ C, int*
     }
 }
 
+// The extra path directions of asw_sgbm_paths: one wavefront per line of the H x Wv rectangle, candidates
+// in lanes, L added into T as it is produced.  Runs between k_sgbm_top (which leaves T = L_tb) and k_sgbm_row.
+//   geom 0: the column xi = line, walked top->bottom
+//   geom 1: the diagonal xi - y = line - (H - 1), walked from its top-left end
+//   geom 2: the anti-diagonal xi + y = line, walked from its top-right end
+// dirs bit 0: walk forth (geom 0..2: PATH_TB, TLBR, TRBL); bit 1: walk back over the same line (PATH_BT, BRTL, BLTR).  The lines
+// of one geometry are disjoint and both walks of a line belong to the same wavefront (lane d touches the same addresses in
+// both), so nothing in a launch shares a T entry between wavefronts.
+// The C row of the next step does not depend on the recurrence: it, and the T row of this step, are loaded before sgbm_step so
+// that the dependent chain never waits on global memory (ASW_SGBM_LINE_NO_PREFETCH: the measurement build without that).
+template <int NPL>
+__device__ __forceinline__ void sgbm_line_walk(const int* __restrict__ C, int* T, ptrdiff_t first, ptrdiff_t stride, int len, int D,
+                                               int P1, int P2, int* lds)
+{
+    const int lane = threadIdx.x;
+    int Lr[NPL], c[NPL], cn[NPL], t[NPL];
+    int m = 0;
+#pragma unroll
+    for (int k = 0; k < NPL; k++) {
+        const int d = k * 64 + lane;
+        Lr[k] = 0;
+        cn[k] = d < D ? C[first + d] : 0;
+    }
+    ptrdiff_t o = first;
+    for (int i = 0; i < len; i++, o += stride) {
+#pragma unroll
+        for (int k = 0; k < NPL; k++) c[k] = cn[k];
+#ifndef ASW_SGBM_LINE_NO_PREFETCH
+        const bool more = i + 1 < len;
+#pragma unroll
+        for (int k = 0; k < NPL; k++) {
+            const int d = k * 64 + lane;
+            if (d < D) {
+                t[k] = T[o + d];
+                if (more) cn[k] = C[o + stride + d];
+            }
+        }
+        sgbm_step<NPL>(Lr, c, m, lds + (i & 1) * D, D, P1, P2);
+#pragma unroll
+        for (int k = 0; k < NPL; k++) {
+            const int d = k * 64 + lane;
+            if (d < D) T[o + d] = t[k] + Lr[k];
+        }
+#else
+        sgbm_step<NPL>(Lr, c, m, lds + (i & 1) * D, D, P1, P2);
+#pragma unroll
+        for (int k = 0; k < NPL; k++) {
+            const int d = k * 64 + lane;
+            if (d < D) {
+                T[o + d] += Lr[k];
+                if (i + 1 < len) cn[k] = C[o + stride + d];
+            }
+        }
+        (void)t;
+#endif
+    }
+}
+
+template <int NPL>
+__global__ __launch_bounds__(64) void k_sgbm_line(const int* __restrict__ C, int* T, int H, int Wv, int D, int P1, int P2, int geom,
+                                                  int dirs)
+{
+    extern __shared__ int lds[];  // [2][D]
+    const int line = blockIdx.x;
+    int y0, x0, len, sx;
+    if (geom == 0) {
+        y0 = 0; x0 = line; len = H; sx = 0;
+    } else if (geom == 1) {
+        y0 = max(0, H - 1 - line); x0 = max(0, line - (H - 1)); len = min(H - y0, Wv - x0); sx = 1;
+    } else {
+        y0 = max(0, line - (Wv - 1)); x0 = line - y0; len = min(H - y0, x0 + 1); sx = -1;
+    }
+    const ptrdiff_t stride = ((ptrdiff_t)Wv + sx) * D;  // one row down, sx columns across
+    const ptrdiff_t first = ((ptrdiff_t)y0 * Wv + x0) * D;
+    if (dirs & 1) sgbm_line_walk<NPL>(C, T, first, stride, len, D, P1, P2, lds);
+    if (dirs & 2) {
+        __syncthreads();  // the forth walk's last LDS row may share its parity with the back walk's first
+        sgbm_line_walk<NPL>(C, T, first + (len - 1) * stride, -stride, len, D, P1, P2, lds);
+    }
+}
+
 // step 6: a pixel is invalidated only when both of its neighbouring integer disparities disagree with the right-view winners
 __global__ __launch_bounds__(256) void k_sgbm_lr(const int* __restrict__ disp_raw, const unsigned long long* __restrict__ key, int H,
                                                  int W, int minD, int D, int M, short* __restrict__ out)
@@ -430,12 +512,22 @@ __global__ __launch_bounds__(256) void k_disp16_to_u8f(const short* __restrict__
 inline unsigned blocks(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 
 template <int NPL>
-int launch_paths(hipStream_t s, const int* hb, int H, int W, int minD, int D, int h, int P1, int P2, int U, int keep_S, int* C, int* T,
-                 int* disp_raw, unsigned long long* key)
+int launch_paths(hipStream_t s, const int* hb, int H, int W, int minD, int D, int h, int P1, int P2, int U, int keep_S, int paths,
+                 int* C, int* T, int* disp_raw, unsigned long long* key)
 {
     const int Wv = W - (minD + D);
     hipLaunchKernelGGL(k_sgbm_top<NPL>, dim3(Wv), dim3(64), 2 * D * sizeof(int), s, hb, H, Wv, D, h, P1, P2, C, T);
     ASW_HIP_TRY(hipGetLastError());
+    // the directions beyond the three of k_sgbm_top / k_sgbm_row: one launch per line geometry, stream order between them
+    const int dirs[3] = {paths & ASW_SGBM_PATH_BT ? 2 : 0,
+                         (paths & ASW_SGBM_PATH_TLBR ? 1 : 0) | (paths & ASW_SGBM_PATH_BRTL ? 2 : 0),
+                         (paths & ASW_SGBM_PATH_TRBL ? 1 : 0) | (paths & ASW_SGBM_PATH_BLTR ? 2 : 0)};
+    for (int geom = 0; geom < 3; geom++) {
+        if (!dirs[geom]) continue;
+        hipLaunchKernelGGL(k_sgbm_line<NPL>, dim3(geom == 0 ? Wv : H + Wv - 1), dim3(64), 2 * D * sizeof(int), s, C, T, H, Wv, D, P1,
+                           P2, geom, dirs[geom]);
+        ASW_HIP_TRY(hipGetLastError());
+    }
     hipLaunchKernelGGL(k_sgbm_row<NPL>, dim3(H), dim3(64), 4 * D * sizeof(int), s, C, T, H, W, minD, D, P1, P2, U, keep_S, disp_raw,
                        key);
     ASW_HIP_TRY(hipGetLastError());
@@ -484,11 +576,11 @@ int launch_sgbm(hipStream_t s, const SgbmLaunch& a)
     ASW_HIP_TRY(hipMemsetAsync(key, 0xff, plane * 8, s));
     const int npl = (D + 63) / 64;
     if (a.ev_agg0) ASW_HIP_TRY(hipEventRecord(a.ev_agg0, s));
-    if (npl <= 1) ASW_TRY(launch_paths<1>(s, hb, H, W, minD, D, a.w / 2, a.P1, a.P2, a.U, a.vol != nullptr, C, T, disp_raw, key));
-    else if (npl <= 2) ASW_TRY(launch_paths<2>(s, hb, H, W, minD, D, a.w / 2, a.P1, a.P2, a.U, a.vol != nullptr, C, T, disp_raw, key));
-    else if (npl <= 4) ASW_TRY(launch_paths<4>(s, hb, H, W, minD, D, a.w / 2, a.P1, a.P2, a.U, a.vol != nullptr, C, T, disp_raw, key));
-    else if (npl <= 8) ASW_TRY(launch_paths<8>(s, hb, H, W, minD, D, a.w / 2, a.P1, a.P2, a.U, a.vol != nullptr, C, T, disp_raw, key));
-    else if (npl <= 16) ASW_TRY(launch_paths<16>(s, hb, H, W, minD, D, a.w / 2, a.P1, a.P2, a.U, a.vol != nullptr, C, T, disp_raw, key));
+    if (npl <= 1) ASW_TRY(launch_paths<1>(s, hb, H, W, minD, D, a.w / 2, a.P1, a.P2, a.U, a.vol != nullptr, a.paths, C, T, disp_raw, key));
+    else if (npl <= 2) ASW_TRY(launch_paths<2>(s, hb, H, W, minD, D, a.w / 2, a.P1, a.P2, a.U, a.vol != nullptr, a.paths, C, T, disp_raw, key));
+    else if (npl <= 4) ASW_TRY(launch_paths<4>(s, hb, H, W, minD, D, a.w / 2, a.P1, a.P2, a.U, a.vol != nullptr, a.paths, C, T, disp_raw, key));
+    else if (npl <= 8) ASW_TRY(launch_paths<8>(s, hb, H, W, minD, D, a.w / 2, a.P1, a.P2, a.U, a.vol != nullptr, a.paths, C, T, disp_raw, key));
+    else if (npl <= 16) ASW_TRY(launch_paths<16>(s, hb, H, W, minD, D, a.w / 2, a.P1, a.P2, a.U, a.vol != nullptr, a.paths, C, T, disp_raw, key));
     else return ASW_ERR_BAD_ARGUMENT;
     if (a.ev_agg1) ASW_HIP_TRY(hipEventRecord(a.ev_agg1, s));
     if (a.vol) {

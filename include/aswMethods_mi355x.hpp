@@ -175,6 +175,42 @@ inline void getDisparity_SGBM(AswMat srcLeft, AswMat srcRight, AswMat& disparity
     disparityMap = asw::detail::f32_to_u8(d);
 }
 
+// Not in the reference: getDisparity_SGBM with the aggregated cost summed over the path directions of `paths` (an OR of
+// ASW_SGBM_PATH_*, asw_sgbm_paths) instead of the three of MODE_SGBM_3WAY.  The same StereoSGBM settings,
+// the same CV_8U result (convertTo(CV_8U, 1/16) of the int16 map: round half to even, saturate) and the same throwing behaviour.
+inline void getDisparity_SGBM_paths(AswMat srcLeft, AswMat srcRight, AswMat& disparityMap, int winSize = 15, int minDisparity = 0,
+                                    int numDisparity = 64, int paths = ASW_SGBM_PATHS_HH)
+{
+    if (srcLeft.empty() || srcRight.empty()) throw std::runtime_error("getDisparity_SGBM_paths: one of the input images is empty");
+    const int w = winSize > 0 ? winSize : 3;
+    int rc = numDisparity % 16 != 0 || winSize % 2 == 0 ? ASW_ERR_UNSUPPORTED_METHOD : w > 4096 ? ASW_ERR_BAD_ARGUMENT : ASW_OK;
+    const int H = srcLeft.rows, W = srcLeft.cols;
+    std::vector<short> d16((size_t)H * W);
+    if (rc == ASW_OK) {
+        asw_image li = asw::detail::view(srcLeft), ri = asw::detail::view(srcRight);
+        asw_image di{d16.data(), H, W, 1, ASW_16S, (size_t)W * sizeof(short)};
+        const int cn = li.channels;
+        rc = asw_sgbm_paths(asw::detail::context(), &li, &ri, &di, minDisparity, numDisparity, w, 8 * cn * w * w, 32 * cn * w * w, 200,
+                            10, 10, 175, 32, paths, nullptr, 0);
+    }
+    asw::detail::raise_unless_ok(rc, "getDisparity_SGBM_paths");
+    if (rc != ASW_OK) {
+        disparityMap = AswMat();
+        return;
+    }
+    AswMat u = asw::detail::make(H, W, ASW_8U, 1);
+    asw_image ui = asw::detail::view(u);
+    for (int y = 0; y < H; y++) {
+        uint8_t* dst = (uint8_t*)ui.data + (size_t)y * ui.step;
+        for (int x = 0; x < W; x++) {
+            const int v = d16[(size_t)y * W + x], q = v >> 4, r = v & 15;  // v / 16 = q + r / 16, q = floor
+            const int n = q + (r > 8 || (r == 8 && (q & 1)));
+            dst[x] = (uint8_t)(n < 0 ? 0 : n > 255 ? 255 : n);
+        }
+    }
+    disparityMap = u;
+}
+
 // M.h:93 / aswMethods.cpp:100-146: StereoBM (PREFILTER_XSOBEL) with the reference's settings, CV_8U result; a 3-channel image is
 // converted to gray first.  The CV_Error cases (numDisparity % 16 != 0, even winSize, an empty image, a block size outside
 // 5..min(rows, cols, 255)) throw, and so does every other failure.  stereoMatching(..., BM, ...) is not routed here.

@@ -299,7 +299,7 @@ int asw_bgr2gray(asw_ctx* ctx, const asw_image* bgr, uint8_t* gray);
  * the reference) give ASW_ERR_UNSUPPORTED_METHOD; disparity_type is ignored (the left-view map); it has no cost volume.
  * asw_sgbm: StereoSGBM::create(min_disparity, num_disparities, block_size, p1, p2, disp12_max_diff, pre_filter_cap, uniqueness_ratio,
  * speckle_window_size, speckle_range, mode) + compute().  disp16: ASW_16S, 1 channel (else ASW_ERR_UNSUPPORTED_LAYOUT, as for
- * asw_filter_speckles), rows x cols: disparity x 16, invalid pixels 16 * (min_disparity - 1).  mode: 2 (MODE_SGBM_3WAY) only, else ASW_ERR_UNSUPPORTED_METHOD.  num_disparities: a positive multiple of
+ * asw_filter_speckles), rows x cols: disparity x 16, invalid pixels 16 * (min_disparity - 1).  mode: 2 (MODE_SGBM_3WAY), or the value asw_sgbm_paths below forms; else ASW_ERR_UNSUPPORTED_METHOD.  num_disparities: a positive multiple of
  * 16, at most 1024; min_disparity >= 0; 16 * (min_disparity + num_disparities) <= 32767; 1 or 3 channels.  Parameters for which a sum
  * could leave int32 (3 * (C_max + P2) >= 2^31, C_max = cn * (2 * ftzero + 63) * w^2) are refused with ASW_ERR_BAD_ARGUMENT.
  * cost_volume_out (optional): the aggregated cost S of the three paths, f32 [num_disparities][rows][cols] (plane k <-> disparity
@@ -309,6 +309,42 @@ int asw_sgbm(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_im
              int num_disparities, int block_size, int p1, int p2, int disp12_max_diff, int pre_filter_cap,
              int uniqueness_ratio, int speckle_window_size, int speckle_range, int mode, float* cost_volume_out,
              size_t cost_volume_floats);
+/* asw_sgbm_paths: asw_sgbm with the aggregated cost S summed over a chosen set of path directions instead of
+ * the three of MODE_SGBM_3WAY; everything before and after the aggregation is asw_sgbm's, and every other argument behaves as
+ * there, with the same statuses in the same order.  A direction is the step (dx, dy) from a pixel's predecessor to the pixel; a
+ * path starts (previous L = 0) wherever the predecessor lies outside the valid columns x >= min_disparity + num_disparities or the
+ * rows of the frame.  paths: an OR of ASW_SGBM_PATH_*; a bit outside ASW_SGBM_PATHS_HH: ASW_ERR_BAD_ARGUMENT; a mask without all
+ * of ASW_SGBM_PATHS_3WAY: ASW_ERR_UNSUPPORTED_METHOD.  ASW_SGBM_PATHS_3WAY returns bit for bit what asw_sgbm returns.  The named
+ * masks read OpenCV's modes as path sets (MODE_HH4: 4 paths, MODE_SGBM: 5, MODE_HH: 8); parity with OpenCV in those modes is not
+ * pinned.  With n paths the int32 and f32 bounds become n * (C_max + P2) >= 2^31 and >= 2^24 (ASW_ERR_BAD_ARGUMENT).
+ * It is an inline function of this header, not a symbol of the library (the exported set stays as it is): it hands the mask to
+ * asw_sgbm in its mode argument, ASW_SGBM_MODE_PATHS | paths, a value no StereoSGBM mode takes; a mask with a bit outside
+ * ASW_SGBM_PATHS_HH travels as the invalid mask 0x100, so that it is refused where asw_sgbm refuses a mode. */
+enum {
+    ASW_SGBM_PATH_LR = 0x01,   /* (1, 0)   left -> right */
+    ASW_SGBM_PATH_RL = 0x02,   /* (-1, 0)  right -> left */
+    ASW_SGBM_PATH_TB = 0x04,   /* (0, 1)   top -> bottom */
+    ASW_SGBM_PATH_BT = 0x08,   /* (0, -1)  bottom -> top */
+    ASW_SGBM_PATH_TLBR = 0x10, /* (1, 1)   top-left -> bottom-right */
+    ASW_SGBM_PATH_TRBL = 0x20, /* (-1, 1)  top-right -> bottom-left */
+    ASW_SGBM_PATH_BRTL = 0x40, /* (-1, -1) bottom-right -> top-left */
+    ASW_SGBM_PATH_BLTR = 0x80, /* (1, -1)  bottom-left -> top-right */
+    ASW_SGBM_PATHS_3WAY = 0x07,
+    ASW_SGBM_PATHS_HH4 = 0x0F,
+    ASW_SGBM_PATHS_SGBM = 0x37, /* the four paths from the top-left half plane + right -> left */
+    ASW_SGBM_PATHS_HH = 0xFF,
+    ASW_SGBM_MODE_PATHS = 0x40000000 /* asw_sgbm's mode: the low bits hold a path mask */
+};
+static inline int asw_sgbm_paths(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp16, int min_disparity,
+                                 int num_disparities, int block_size, int p1, int p2, int disp12_max_diff, int pre_filter_cap,
+                                 int uniqueness_ratio, int speckle_window_size, int speckle_range, int paths, float* cost_volume_out,
+                                 size_t cost_volume_floats)
+{
+    const int mask = (paths & ~ASW_SGBM_PATHS_HH) ? 0x100 : paths;
+    return asw_sgbm(ctx, left, right, disp16, min_disparity, num_disparities, block_size, p1, p2, disp12_max_diff, pre_filter_cap,
+                    uniqueness_ratio, speckle_window_size, speckle_range, ASW_SGBM_MODE_PATHS | mask, cost_volume_out,
+                    cost_volume_floats);
+}
 /* cv::filterSpeckles, in place: 4-connected components of pixels != new_val whose neighbours differ by at most max_diff; every
  * component of at most max_speckle_size pixels becomes new_val.  img: ASW_16S, 1 channel (ASW_8U: ASW_ERR_UNSUPPORTED_LAYOUT). */
 int asw_filter_speckles(asw_ctx* ctx, asw_image* img, int new_val, int max_speckle_size, int max_diff);
