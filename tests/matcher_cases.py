@@ -1,10 +1,12 @@
-"""Inputs on which winner-take-all matchers go wrong first, and a seeded case generator for the integer kernels (SGBM, StereoBM,
-filterSpeckles, the left-right refinement, the sub-pixel flag).  Plain numpy: nothing here needs a GPU.  TEST INFRASTRUCTURE ONLY.
+"""Inputs on which winner-take-all matchers go wrong first, and a seeded case generator for the integer kernels (SGBM, SGBM over a
+mask of path directions, StereoBM, filterSpeckles, the left-right refinement, the sub-pixel flag).  Plain numpy: nothing here needs
+a GPU.  TEST INFRASTRUCTURE ONLY.
 
 Three parts:
 
   the tie-dense pair generators (`constant`, `periodic`, `row_constant`, `quantised`, `flat_rects`; `textured` is plain
-  make_pair) and `tie_share`, which measures on a cost volume how often the minimum is shared;
+  make_pair) and `tie_share`, which measures on a cost volume how often the minimum is shared; `tie_pair`, `noise` and
+  `SGBM_TINY_FRAMES` are the fixed inputs that the degenerate-input files of SGBM and of SGBM over path masks share;
 
   `random_case(rng, family, index)` / `build_case(family, tag)`: a case is rebuilt from its tag alone, so the tuple an assertion
   prints is enough to run that case again;
@@ -20,17 +22,18 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import refine_ref  # noqa: E402
+import sgbm_paths_ref  # noqa: E402
 import sgbm_ref  # noqa: E402
 import stereobm_ref  # noqa: E402
 import subpixel_ref  # noqa: E402
 from aswstereomatch_amd.synth import make_pair  # noqa: E402
 
-FAMILIES = ("sgbm", "bm", "speckles", "refine", "subpixel")
+FAMILIES = ("sgbm", "bm", "speckles", "refine", "subpixel", "sgbm_paths")
 KINDS = ("constant", "periodic", "row_constant", "quantised", "flat_rects", "textured")
 # the seeds and case counts of the sweep in tests/test_gpu_matcher_degenerate.py; tests/test_matcher_cases_cpu.py runs the
 # restatements over the same cases
 SWEEP_SEEDS = (20261, 20262)
-SWEEP_COUNTS = {"sgbm": 30, "bm": 30, "speckles": 30, "refine": 12, "subpixel": 12}
+SWEEP_COUNTS = {"sgbm": 30, "bm": 30, "speckles": 30, "refine": 12, "subpixel": 12, "sgbm_paths": 30}
 
 # selector value, DISPARITY_RIGHT served (the nine methods that take the sub-pixel flag; tests/test_gpu_subpixel.py METHODS)
 SUBPIXEL_METHODS = {
@@ -111,6 +114,60 @@ def make_input(kind, H, W, cn, seed, D=16):
     raise ValueError(kind)
 
 
+# the tie table of tests/test_gpu_matcher_degenerate.py and tests/test_gpu_sgbm_paths_degenerate.py: "periodic4" and "periodic8" are
+# periodic(4, 3) and periodic(8, 3)
+TIE_KINDS = ["constant", "periodic4", "periodic8", "row_constant", "quantised", "flat_rects"]
+
+
+def tie_pair(kind, H, W, cn):
+    if kind == "constant":
+        return constant(H, W, cn)
+    if kind.startswith("periodic"):
+        return periodic(H, W, cn, int(kind[8:]), 3)
+    if kind == "row_constant":
+        return row_constant(H, W, cn, seed=5)
+    if kind == "quantised":
+        return quantised(H, W, cn, seed=6, D=32)
+    return flat_rects(H, W, cn, seed=7, D=32)
+
+
+def noise(H, W, seed):
+    """two unrelated uint8 noise images"""
+    rng = np.random.default_rng(seed)
+    return rng.integers(0, 256, (H, W)).astype(np.uint8), rng.integers(0, 256, (H, W)).astype(np.uint8)
+
+
+# H, W, minD, D, block
+SGBM_TINY_FRAMES = [
+    (1, 17, 0, 16, 1), (1, 18, 0, 16, 3),                       # Wv = 1 and 2, one row
+    (2, 80, 0, 16, 5),
+    (3, 16 + 63, 0, 16, 7), (3, 16 + 64, 0, 16, 7), (3, 16 + 65, 0, 16, 7),   # Wv around one wavefront
+    (4, 57, 7, 48, 3), (5, 81, 0, 80, 5),
+]
+
+
+def sgbm_tiny_settings(w):
+    """(P1, P2, disp12MaxDiff, preFilterCap, uniquenessRatio): P1 = P2 = 0 with the uniqueness rule off; the binding's own defaults
+    (all zero: the same penalties, uniqueness 0 in force); and the customary 8 w^2 / 32 w^2 with a left-right check and a prefilter
+    cap, where the penalties and the later stages do work"""
+    return ((0, 0, 0, 0, -1), (0, 0, 0, 0, 0), (8 * w * w, 32 * w * w, 1, 10, 0))
+
+
+# Turning a pair upside down turns the result of SGBM over a path mask upside down when the mask is turned with it
+# (sgbm_paths_ref.vflip): tests/test_sgbm_paths_cpu.py shows it on the restatement, tests/test_gpu_sgbm_paths_degenerate.py on the GPU
+PATHS_FLIP_KINDS = ["textured", "flat_rects", "quantised"]
+PATHS_FLIP_MASKS = [0x0F, 0x17, 0x27, 0x47, 0x87, 0x37, 0xFF]   # bottom->top, each diagonal alone, five paths, all eight
+
+
+def paths_flip_pair(kind, cn):
+    return make_input(kind, 23, 90, cn, seed=11, D=32)
+
+
+def paths_flip_args(cn):
+    """minD, D, block, P1, P2, disp12MaxDiff, preFilterCap, uniquenessRatio, speckleWindowSize, speckleRange"""
+    return (1, 32, 5, 8 * cn * 25, 32 * cn * 25, 1, 10, 10, 20, 2)
+
+
 def padded_view(img, pad, fill):
     """the same pixels as a view into rows that are `pad` pixels longer (step > cols * channels); the padding holds `fill`"""
     if pad <= 0:
@@ -149,15 +206,32 @@ def _matcher_draws(rng, family, index):
     return kind, H, W, minD, D, w, pad, seed
 
 
+def _sgbm_tag(rng, kind, H, W, minD, D, w, pad, seed):
+    cn = _pick(rng, (1, 3))
+    pens = (0, 8 * cn * w * w, 32 * cn * w * w, 10, 100, 600, 2400)
+    return (kind, H, W, cn, minD, D, w, _pick(rng, pens), _pick(rng, pens), _pick(rng, (-1, 0, 1, 3, 200)),
+            _pick(rng, (0, 1, 10, 31, 63)), _pick(rng, (-1, 0, 5, 10, 50)), _pick(rng, (0, 10, 100)), _pick(rng, (0, 1, 2, 32)),
+            pad, seed)
+
+
 def random_case(rng, family, index=None):
     """One case of `family`, drawn from `rng`.  The input kind cycles with `index` over KINDS (drawn when index is None)."""
     if family == "sgbm":
-        kind, H, W, minD, D, w, pad, seed = _matcher_draws(rng, family, index)
-        cn = _pick(rng, (1, 3))
-        pens = (0, 8 * cn * w * w, 32 * cn * w * w, 10, 100, 600, 2400)
-        tag = (kind, H, W, cn, minD, D, w, _pick(rng, pens), _pick(rng, pens), _pick(rng, (-1, 0, 1, 3, 200)),
-               _pick(rng, (0, 1, 10, 31, 63)), _pick(rng, (-1, 0, 5, 10, 50)), _pick(rng, (0, 10, 100)), _pick(rng, (0, 1, 2, 32)),
-               pad, seed)
+        tag = _sgbm_tag(rng, *_matcher_draws(rng, family, index))
+    elif family == "sgbm_paths":
+        # the sgbm tag followed by a mask that contains the three paths.  The added directions work on the valid columns
+        # [minD + D, W) only, so nine cases in ten get 1..120 of them whatever minD and D are; the tenth keeps any width from 1 up
+        # (W <= minD + D included: the all-INVALID answer)
+        kind = KINDS[(int(rng.integers(0, len(KINDS))) if index is None else index) % len(KINDS)]
+        w = 2 * int(rng.integers(0, 11)) + 1
+        H = int(rng.integers(1, 41))
+        D = _pick(rng, (16, 32, 48, 64, 80, 128))
+        minD = _pick(rng, (0, 1, 5, 17))
+        Wv, anyW = int(rng.integers(1, 121)), int(rng.integers(1, 221))
+        W = minD + D + Wv if rng.random() < 0.9 else anyW
+        pad = int(rng.integers(1, 9)) if rng.random() < 1.0 / 7 else 0
+        tag = _sgbm_tag(rng, kind, H, W, minD, D, w, pad, int(rng.integers(0, 1 << 30)))
+        tag += (0x07 | (int(rng.integers(0, 32)) << 3),)
     elif family == "bm":
         kind, H, W, minD, D, w, pad, seed = _matcher_draws(rng, family, index)
         tag = (kind, H, W, minD, D, w, _pick(rng, (1, 5, 31, 63)), _pick(rng, (0, 10, 500)), _pick(rng, (0, 15, 100)),
@@ -225,6 +299,8 @@ def build_case(family, tag):
         kind, H, W, cn, minD, D, w, P1, P2, m12, cap, U, sw, sr, pad, seed = tag
         L, R = make_input(kind, H, W, cn, seed, D)
         c.update(L=padded_view(L, pad, 0), R=padded_view(R, pad, 255), args=(minD, D, w, P1, P2, m12, cap, U, sw, sr))
+    elif family == "sgbm_paths":
+        c.update(build_case("sgbm", tag[:-1]), family=family, tag=tuple(tag), paths=tag[-1])
     elif family == "bm":
         kind, H, W, minD, D, w, cap, tex, U, m12, sw, sr, pad, seed = tag
         L, R = make_input(kind, H, W, 1, seed, D)
@@ -252,6 +328,9 @@ def reference(case):
     if f == "sgbm":
         want = sgbm_ref.sgbm(case["L"], case["R"], *case["args"])
         return {"disp": want["disp"], "vol": np.moveaxis(want["S"], 2, 0).astype(np.float32)}
+    if f == "sgbm_paths":
+        want = sgbm_paths_ref.sgbm_paths(case["L"], case["R"], *case["args"], case["paths"])
+        return {"disp": want["disp"], "vol": np.moveaxis(want["S"], 2, 0).astype(np.float32)}
     if f == "bm":
         minD, D, w, cap, tex, U, sw, sr, m12 = case["args"]
         want = stereobm_ref.stereo_bm(case["L"], case["R"], minD, D, w, cap, tex, U, sw, sr, m12)
@@ -272,6 +351,9 @@ def gpu_result(ctx, case):
     f = case["family"]
     if f == "sgbm":
         disp, vol = ctx.sgbm(case["L"], case["R"], *case["args"], return_cost_volume=True)
+        return {"disp": disp, "vol": vol}, reference(case)
+    if f == "sgbm_paths":
+        disp, vol = ctx.sgbm_paths(case["L"], case["R"], *case["args"], paths=case["paths"], return_cost_volume=True)
         return {"disp": disp, "vol": vol}, reference(case)
     if f == "bm":
         minD, D, w, cap, tex, U, sw, sr, m12 = case["args"]

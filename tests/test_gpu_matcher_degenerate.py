@@ -37,20 +37,12 @@ def ctx():
     c.close()
 
 
-# kind -> pair of H x W (x cn); "periodic4" and "periodic8" are periodic(4, 3) and periodic(8, 3)
+# kind -> pair of H x W (x cn)
 def _tie_pair(kind, cn):
-    if kind == "constant":
-        return mc.constant(H, W, cn)
-    if kind.startswith("periodic"):
-        return mc.periodic(H, W, cn, int(kind[8:]), 3)
-    if kind == "row_constant":
-        return mc.row_constant(H, W, cn, seed=5)
-    if kind == "quantised":
-        return mc.quantised(H, W, cn, seed=6, D=32)
-    return mc.flat_rects(H, W, cn, seed=7, D=32)
+    return mc.tie_pair(kind, H, W, cn)
 
 
-TIE_KINDS = ["constant", "periodic4", "periodic8", "row_constant", "quantised", "flat_rects"]
+TIE_KINDS = mc.TIE_KINDS
 
 
 def _sgbm_check(ctx, L, R, minD, D, w, P1, P2, m12, cap, U, sw=0, sr=0):
@@ -131,24 +123,14 @@ def test_selector_entries_on_tied_costs(ctx, kind):
 
 
 # ---------------------------------------------------------------- tiny and ragged frames
-def _noise(Hn, Wn, seed):
-    rng = np.random.default_rng(seed)
-    return rng.integers(0, 256, (Hn, Wn)).astype(np.uint8), rng.integers(0, 256, (Hn, Wn)).astype(np.uint8)
+_noise = mc.noise
 
 
-# H, W, minD, D, block
-@pytest.mark.parametrize("Hn,Wn,minD,D,w", [
-    (1, 17, 0, 16, 1), (1, 18, 0, 16, 3),                       # Wv = 1 and 2, one row
-    (2, 80, 0, 16, 5),
-    (3, 16 + 63, 0, 16, 7), (3, 16 + 64, 0, 16, 7), (3, 16 + 65, 0, 16, 7),   # Wv around one wavefront
-    (4, 57, 7, 48, 3), (5, 81, 0, 80, 5),
-])
+@pytest.mark.parametrize("Hn,Wn,minD,D,w", mc.SGBM_TINY_FRAMES)
 def test_sgbm_tiny_and_ragged_frames(ctx, Hn, Wn, minD, D, w):
     L, R = _noise(Hn, Wn, Hn * 1000 + Wn)
     assert Wn - minD - D >= 1
-    # P1 = P2 = 0 with the uniqueness rule off; the binding's own defaults (all zero: the same penalties, uniqueness 0 in force); and
-    # the customary 8 w^2 / 32 w^2 with a left-right check and a prefilter cap, where the penalties and the later stages do work
-    for P1, P2, m12, cap, U in ((0, 0, 0, 0, -1), (0, 0, 0, 0, 0), (8 * w * w, 32 * w * w, 1, 10, 0)):
+    for P1, P2, m12, cap, U in mc.sgbm_tiny_settings(w):
         want = _sgbm_check(ctx, L, R, minD, D, w, P1, P2, m12, cap, U)
         assert want["S"][:, minD + D:].any()
     L3 = np.stack([L, R, L], axis=2)

@@ -100,12 +100,12 @@ def test_random_case_is_deterministic_and_rebuilds_from_its_tag(family):
 
 
 @pytest.mark.parametrize("seed", mc.SWEEP_SEEDS)
-@pytest.mark.parametrize("family", ["sgbm", "bm", "speckles", "refine"])
+@pytest.mark.parametrize("family", ["sgbm", "bm", "speckles", "refine", "sgbm_paths"])
 def test_restatements_accept_every_sweep_case(family, seed):
     padded = 0
     for case in mc.cases(family, seed):
         want = mc.reference(case)
-        if family in ("sgbm", "bm"):
+        if family in ("sgbm", "bm", "sgbm_paths"):
             Hc, Wc = case["L"].shape[:2]
             padded += case["L"].strides[0] > Wc * (case["L"].shape[2] if case["L"].ndim == 3 else 1)
             assert want["disp"].shape == (Hc, Wc) and want["disp"].dtype == np.int16, case["tag"]
@@ -114,8 +114,30 @@ def test_restatements_accept_every_sweep_case(family, seed):
             assert want["map"].shape == case["map"].shape and want["map"].dtype == np.int16, case["tag"]
         else:
             assert want["out"].shape == case["dl"].shape and want["counts"][0] >= want["counts"][1], case["tag"]
-    if family in ("sgbm", "bm"):
+    if family in ("sgbm", "bm", "sgbm_paths"):
         print("%s seed %d: %d padded cases" % (family, seed, padded))
+
+
+@pytest.mark.parametrize("seed", mc.SWEEP_SEEDS)
+def test_sgbm_paths_sweep_gives_the_line_kernel_work(seed):
+    # the added directions run over the valid columns [minD + D, W) only: a family that drew W as the sgbm family does would leave
+    # about a third of its cases without any
+    cases = mc.cases("sgbm_paths", seed)
+    assert len(cases) == 30
+    empty = diagonal = 0
+    for case in cases:
+        kind, Hc, Wc, cn, minD, Dc, w, P1, P2, m12, cap, U = case["tag"][:12]
+        paths = case["tag"][-1]
+        assert case["paths"] == paths and paths & 0x07 == 0x07 and 0 <= paths <= 0xFF and Hc <= 40, case["tag"]
+        assert case["L"].shape[:2] == (Hc, Wc) and case["args"][:3] == (minD, Dc, w), case["tag"]
+        empty += Wc <= minD + Dc
+        diagonal += Hc >= 2 and Wc - minD - Dc >= 2      # a diagonal longer than one pixel exists
+        # the f32 volume is exact, so no case has to drop its comparison (n (C_max + P2) < 2^24)
+        w_, ftzero, _, P2e, _, _ = sgbm_ref.effective_params(w, P1, P2, m12, cap, U)
+        assert bin(paths).count("1") * (sgbm_ref.cost_bound(cn, w_, ftzero) + P2e) < 1 << 24, case["tag"]
+    print("sgbm_paths seed %d: %d cases without a valid column, %d with a diagonal of two pixels or more, %d masks"
+          % (seed, empty, diagonal, len({c["tag"][-1] for c in cases})))
+    assert empty <= 3 and diagonal >= 20
 
 
 @pytest.mark.parametrize("seed", mc.SWEEP_SEEDS)

@@ -1,6 +1,7 @@
 """CPU-side checks of the multi-path semi-global matcher's restatement (tests/sgbm_paths_ref.py): the
-three-path mask reproduces tests/sgbm_ref.py, the vectorised and the scalar statement agree on every direction, and flipping the
-cost volume permutes the directions as it must (no GPU needed)."""
+three-path mask reproduces tests/sgbm_ref.py, the vectorised and the scalar statement agree on every direction (on textured and on
+tie-dense inputs), flipping the cost volume permutes the directions as it must, the whole pipeline commutes with turning the pair
+upside down, and the tie-dense pairs of tests/matcher_cases.py still tie once the added directions are summed in (no GPU needed)."""
 import os
 import sys
 
@@ -11,6 +12,7 @@ import aswstereomatch_amd as asw
 from aswstereomatch_amd.synth import make_pair
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import matcher_cases as mc  # noqa: E402
 import sgbm_paths_ref as pref  # noqa: E402
 import sgbm_ref as ref  # noqa: E402
 
@@ -78,6 +80,67 @@ def test_mirror_property(shape):
     assert np.array_equal(L[0], C[0]) and np.array_equal(L[:, 0], C[:, 0])
     L = pref.path(C, 7, 30, -1, -1)
     assert np.array_equal(L[-1], C[-1]) and np.array_equal(L[:, -1], C[:, -1])
+
+
+@pytest.mark.parametrize("cn", [1, 3])
+@pytest.mark.parametrize("kind", mc.PATHS_FLIP_KINDS)
+def test_whole_pipeline_commutes_with_a_vertical_flip(kind, cn):
+    # Every stage is symmetric under y -> H-1-y (the prefilter's vertical taps 1 2 1, the block window, the 3x3 median, the
+    # 4-connected speckle components; ties are broken along d and x only), and the directions permute by vflip.  For 0x0F this
+    # ties PATH_BT to PATH_TB, which tests/test_sgbm_cpu.py pins through the three-path matcher.
+    L, R = mc.paths_flip_pair(kind, cn)
+    assert [0x07 | b for b in pref.NEW_BITS[1:]] == mc.PATHS_FLIP_MASKS[1:5]
+    # with PATH_BT added to each mask as well: those are the masks whose flip the library serves (a superset of the three paths)
+    for m in mc.PATHS_FLIP_MASKS + sorted({m | pref.PATH_BT for m in mc.PATHS_FLIP_MASKS} - set(mc.PATHS_FLIP_MASKS)):
+        want = pref.sgbm_paths(L, R, *mc.paths_flip_args(cn), m)
+        got = pref.sgbm_paths(L[::-1], R[::-1], *mc.paths_flip_args(cn), pref.vflip(m))
+        assert np.array_equal(got["S"][::-1], want["S"]), hex(m)
+        assert np.array_equal(got["disp"][::-1], want["disp"]), hex(m)
+        invalid = float((want["disp"] == 0).mean())       # INVALID = 16 (minD - 1) = 0
+        assert 0.2 < invalid < 0.8, (hex(m), invalid)     # neither all rejected nor nothing for steps 5-9 to do
+        if pref.vflip(m) != m:                            # the unflipped mask on the flipped pair is another result
+            assert not np.array_equal(pref.sgbm_paths(L[::-1], R[::-1], *mc.paths_flip_args(cn), m)["S"][::-1], want["S"]), hex(m)
+
+
+TIE_H, TIE_W, TIE_D, TIE_BLOCK = 20, 150, 32, 5   # tests/test_matcher_cases_cpu.py
+
+
+def paths_tie_shares(want, minD, D):
+    """(tie share of S over the valid columns, share of the map that is not INVALID)"""
+    return mc.tie_share(want["S"][:, minD + D:], 2), float((want["disp"] != 16 * (minD - 1)).mean())
+
+
+@pytest.mark.parametrize("paths", [pref.PATHS_3WAY, pref.PATHS_HH4, pref.PATHS_SGBM, pref.PATHS_HH])
+def test_tie_generators_tie_under_every_named_mask(paths):
+    # the floors of test_matcher_cases_cpu.py::test_tie_generators_really_tie, with the added directions summed into S
+    want = pref.sgbm_paths(*mc.periodic(TIE_H, TIE_W, 1, 4, 3), 0, TIE_D, TIE_BLOCK, 200, 800, -1, 10, 0, 0, 0, paths)
+    ties, alive = paths_tie_shares(want, 0, TIE_D)
+    print("paths 0x%02X periodic(4, 3): tie share %.3f, not-invalid share %.3f" % (paths, ties, alive))
+    assert ties >= 0.5 and alive >= 0.5
+    want = pref.sgbm_paths(*mc.constant(TIE_H, TIE_W, 1), 5, TIE_D, TIE_BLOCK, 200, 800, -1, 10, 0, 0, 0, paths)
+    ties, _ = paths_tie_shares(want, 5, TIE_D)
+    print("paths 0x%02X constant minD 5: tie share %.3f" % (paths, ties))
+    assert ties >= 0.5
+    assert (want["disp"][:, 5 + TIE_D:] == 16 * 5).all()   # the smallest disparity, whatever the directions
+
+
+@pytest.mark.parametrize("paths", [pref.PATHS_HH4, pref.PATHS_SGBM, pref.PATHS_HH])
+@pytest.mark.parametrize("kind,H,Wv,cn,minD", [
+    ("constant", 4, 7, 1, 2), ("constant", 6, 3, 3, 5),      # at minD 0 a constant pair does not tie under SGBM
+    ("periodic", 5, 10, 1, 0), ("periodic", 3, 9, 3, 1),
+    ("quantised", 6, 10, 1, 0), ("quantised", 6, 8, 3, 3),
+])
+def test_scalar_equals_vectorised_on_tied_inputs(kind, H, Wv, cn, minD, paths):
+    D = 16
+    W = minD + D + Wv
+    L, R = {"constant": lambda: mc.constant(H, W, cn), "periodic": lambda: mc.periodic(H, W, cn, 4, 3),
+            "quantised": lambda: mc.quantised(H, W, cn, seed=H + Wv, D=D)}[kind]()
+    got = pref.sgbm_paths(L, R, minD, D, 3, 20, 80, 1, 10, 10, 0, 0, paths)
+    S, disp = pref.sgbm_paths_scalar(L, R, minD, D, 3, 20, 80, 1, 10, 10, paths)
+    assert np.array_equal(got["S"], np.array(S, np.int64))
+    assert np.array_equal(got["raw"], np.array(disp, np.int16))
+    if kind != "quantised":   # plateaus, not exact ties everywhere
+        assert mc.tie_share(got["S"][:, minD + D:], 2) >= 0.5
 
 
 def test_named_masks_of_every_layer():
