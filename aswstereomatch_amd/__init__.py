@@ -31,6 +31,7 @@ __all__ = [
     "REFINE_GAMMA_C", "REFINE_GAMMA_S", "SUBPIXEL_PARABOLA", "SUBPIXEL_EQUIANGULAR",
     "SGBM_PATH_LR", "SGBM_PATH_RL", "SGBM_PATH_TB", "SGBM_PATH_BT", "SGBM_PATH_TLBR", "SGBM_PATH_TRBL", "SGBM_PATH_BRTL",
     "SGBM_PATH_BLTR", "SGBM_PATHS_3WAY", "SGBM_PATHS_HH4", "SGBM_PATHS_SGBM", "SGBM_PATHS_HH",
+    "cross_algorithm", "computeAdaptiveWeight_cross",
     "AswError",
 ]
 
@@ -53,6 +54,7 @@ class StereoMatchingAlgorithms(enum.IntEnum):  # parametersStereo.h:10-24
     ADAPTIVE_WEIGHT_GUIDED_FILTER_3 = 9
     ADAPTIVE_WEIGHT_MEDIAN = 10
     NCC = 11
+    ADAPTIVE_WEIGHT_CROSS = 12  # not in the reference: cross-based support regions
 
 
 DISPARITY_LEFT = DisparityType.DISPARITY_LEFT
@@ -69,6 +71,18 @@ MODE_SGBM_3WAY = 2  # StereoSGBM::MODE_SGBM_3WAY, the one mode asw_sgbm serves
  SGBM_PATH_BLTR) = (1 << _i for _i in range(8))
 SGBM_PATHS_3WAY, SGBM_PATHS_HH4, SGBM_PATHS_SGBM, SGBM_PATHS_HH = 0x07, 0x0F, 0x37, 0xFF
 _SGBM_MODE_PATHS = 0x40000000  # ASW_SGBM_MODE_PATHS: asw_sgbm's mode carrying a path mask, as the header's inline asw_sgbm_paths forms it
+_ALG_CROSS_PARAMS = 0x40000000  # ASW_ALG_CROSS_PARAMS
+
+
+def cross_algorithm(tau=20, trunc=20):
+    """asw_alg_cross of asw_mi355x.h: the value of `algorithmType` that runs ADAPTIVE_WEIGHT_CROSS with colour threshold tau (0..255)
+    and cost truncation trunc (1..255) in every call that takes an algorithm; an argument out of range gives a value the library
+    refuses with ERR_BAD_ARGUMENT (bit 24)."""
+    tau, trunc = int(tau), int(trunc)
+    bad = 0x01000000 if (tau < 0 or tau > 255 or trunc < 1 or trunc > 255) else 0
+    return _ALG_CROSS_PARAMS | bad | ((trunc & 0xFF) << 16) | ((tau & 0xFF) << 8) | int(StereoMatchingAlgorithms.ADAPTIVE_WEIGHT_CROSS)
+
+
 PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL = 0, 1  # StereoBM::PREFILTER_*; asw_stereo_bm serves XSOBEL
 REFINE_GAMMA_C, REFINE_GAMMA_S = 60.0, 9.0  # default colour / distance gammas of the refinement's weighted median (asw_mi355x.h)
 # statuses for which the reference returns silently / an empty Mat
@@ -256,6 +270,15 @@ class Context:
         return self._aggregate(self._lib.asw_aggregate_wmedian, "asw_aggregate_wmedian", numDisparity, leftImg, rightImg,
                                (int(dispType), winSize, float(sampleRateS), float(sampleRateR), minDisparity, numDisparity),
                                return_cost_volume)
+
+    def computeAdaptiveWeight_cross(self, leftImg, rightImg, dispType=DISPARITY_LEFT, tau=20, trunc=20, winSize=15, minDisparity=0,
+                                    numDisparity=64, return_cost_volume=False):
+        """Cross-based support-region aggregation (asw_aggregate_cross; not in the reference): the truncated
+        AD cost summed over every pixel's cross-shaped region, exact integers and one f32 division; 1- or 3-channel pairs."""
+        def call(h, l, r, d, *args):
+            return self._lib.asw_stereo_match(h, l, r, d, int(dispType), cross_algorithm(tau, trunc), winSize, minDisparity,
+                                              numDisparity, *args)
+        return self._aggregate(call, "asw_aggregate_cross", numDisparity, leftImg, rightImg, (), return_cost_volume)
 
     # ---- semi-global block matching (DESIGN.md section 4.8) ----
     def getDisparity_SGBM(self, srcLeft, srcRight, winSize=15, minDisparity=0, numDisparity=64):
@@ -634,6 +657,7 @@ computeAdaptiveWeight_GuidedF = _bind("computeAdaptiveWeight_GuidedF")
 computeAdaptiveWeight_GuidedF_2 = _bind("computeAdaptiveWeight_GuidedF_2")
 computeAdaptiveWeight_WeightedMedian = _bind("computeAdaptiveWeight_WeightedMedian")
 computeAdaptiveWeight_BLO1 = _bind("computeAdaptiveWeight_BLO1")
+computeAdaptiveWeight_cross = _bind("computeAdaptiveWeight_cross")
 winnerTakeAll = _bind("winnerTakeAll")
 getDisparity_SGBM = _bind("getDisparity_SGBM")
 sgbm = _bind("sgbm")

@@ -36,8 +36,22 @@ int match_host(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_
     return ASW_OK;
 }
 
+int decode_algorithm(int algorithm, int* method, int* tau, int* trunc)
+{
+    *method = algorithm;
+    if (!(algorithm & ASW_ALG_CROSS_PARAMS)) return ASW_OK;
+    if ((algorithm & 0xFF) != ASW_ALG_ADAPTIVE_WEIGHT_CROSS) return ASW_ERR_UNSUPPORTED_METHOD;
+    const int t = (algorithm >> 16) & 0xFF;
+    if (t == 0 || (algorithm & 0x3F000000) || algorithm < 0) return ASW_ERR_BAD_ARGUMENT;  // bits 24..29 and 31 stay clear
+    *method = ASW_ALG_ADAPTIVE_WEIGHT_CROSS;
+    if (tau) *tau = (algorithm >> 8) & 0xFF;
+    if (trunc) *trunc = t;
+    return ASW_OK;
+}
+
 extern "C" int asw_volume_planes(int algorithm, int num_disparity)
 {
+    if (decode_algorithm(algorithm, &algorithm, nullptr, nullptr) != ASW_OK) return 0;
     switch (algorithm) {
     case ASW_ALG_ADAPTIVE_WEIGHT:            // offset <= max_offset, M.cpp:1021,1074
     case ASW_ALG_ADAPTIVE_WEIGHT_8DIRECT:    // M.cpp:1171
@@ -50,6 +64,7 @@ extern "C" int asw_volume_planes(int algorithm, int num_disparity)
     case ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER_3:
     case ASW_ALG_ADAPTIVE_WEIGHT_MEDIAN:
     case ASW_ALG_NCC:
+    case ASW_ALG_ADAPTIVE_WEIGHT_CROSS:
         return num_disparity;
     default:
         return 0;

@@ -19,7 +19,12 @@ struct MatchParams {
     double rate_s = 10, rate_r = 10;    // M.cpp:82
     double blo_rate_r = 0.015;          // M.cpp:70
     double grid_rate_s = 10, grid_rate_r = 10;  // M.cpp:67
+    int cross_tau = 20, cross_trunc = 20;       // ASW_ALG_ADAPTIVE_WEIGHT_CROSS; an encoded selector value replaces them
 };
+// The selector's `algorithm` as a caller passes it -> the plain enum value in *method and, for an asw_alg_cross() value, its
+// parameters in *tau / *trunc (left alone otherwise; either may be null).  ASW_ERR_UNSUPPORTED_METHOD / ASW_ERR_BAD_ARGUMENT for the
+// encodings asw_mi355x.h refuses; a value without ASW_ALG_CROSS_PARAMS passes through as it is.
+int decode_algorithm(int algorithm, int* method, int* tau, int* trunc);
 
 int check_u8_image(const asw_image* im);
 int check_pair(const asw_image* L, const asw_image* R);

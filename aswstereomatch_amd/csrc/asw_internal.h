@@ -291,6 +291,13 @@ int bilgrid_dims(int H, int W, double rate_s, double rate_r, int* nx, int* ny, i
 int launch_bilgrid(hipStream_t s, const uint8_t* gl, const uint8_t* gr, int H, int W, double rate_s, double rate_r, int minD,
                    int numD, double* F, int* S, double* best, float* vol, float* disp);
 
+// ---- cross-based support regions (k_cross.hip), DESIGN.md section 4.12 ----
+// arms [H][W]: left | right << 8 | up << 16 | down << 24 of the view image (C = 1 or 3 channels), cnt [H][W]: the region size N
+int launch_cross_arms(hipStream_t s, const uint8_t* img, int H, int W, int C, int win, int tau, uint32_t* arms, uint16_t* cnt);
+// cost: the u8 AD volume [numD][H][W] of launch_cost_ad; vol (optional) [numD][H][W]; disp [H][W]: WTA, strict '<' in ascending d
+int launch_cross_aggregate(hipStream_t s, const uint8_t* cost, const uint32_t* arms, const uint16_t* cnt, int H, int W, int win,
+                           int trunc, int minD, int numD, float* vol, float* disp);
+
 // ---- hooks for the batch scheduler (batch.hip) ----
 int asw_internal_stage_slot(asw_ctx* ctx, int slot, int rows, int cols, int channels, Frame** out);
 int asw_internal_enqueue_match(asw_ctx* ctx, int slot, int disparity_type, int algorithm, int win_size, int min_disparity,

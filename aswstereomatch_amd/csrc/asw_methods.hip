@@ -791,6 +791,47 @@ int bm_prepare(asw_ctx* ctx, const BmParams& p, int H, int W, BmLaunch* out)
     return ASW_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// cross-based support regions (Zhang, Lu, Lafruit 2009): DESIGN.md section 4.12; not in the reference
+// ------------------------------------------------------------------------------------------
+static int run_cross(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_volume)
+{
+    if (mp.win % 2 == 0) return ASW_ERR_EVEN_WINDOW;
+    if (mp.win < 1 || mp.win > 35) return ASW_ERR_BAD_ARGUMENT;
+    if (f->channels != 3 && f->channels != 1) return ASW_ERR_UNSUPPORTED_LAYOUT;  // what asw_cost_ad takes
+    if (mp.disparity_type != ASW_DISPARITY_LEFT && mp.disparity_type != ASW_DISPARITY_RIGHT) return ASW_ERR_BAD_ARGUMENT;
+    if (mp.cross_tau < 0 || mp.cross_tau > 255 || mp.cross_trunc < 1 || mp.cross_trunc > 255) return ASW_ERR_BAD_ARGUMENT;
+    const int H = f->rows, W = f->cols, n = mp.numD;
+    // the sums the kernel keeps are local to a tile (a row prefix < 255 * 99, a column prefix < 255 * 35 * 66): no frame can take them
+    // out of int32; what a frame can overflow is the int row / column arithmetic on H and W
+    if ((size_t)H * W >= ((size_t)1 << 31)) return ASW_ERR_BAD_ARGUMENT;
+    if (H > 4 * 65535) return ASW_ERR_BAD_ARGUMENT;  // the arm kernels put four rows on a workgroup of grid.y
+    const size_t plane = (size_t)H * W;
+    DevBuf& raw = ctx->buf("cross_cost");   // u8 AD volume: a quarter of the f32 volume
+    DevBuf& arms = ctx->buf("cross_arms");
+    DevBuf& cnt = ctx->buf("cross_count");
+    ASW_TRY(raw.ensure(plane * n));
+    ASW_TRY(arms.ensure(plane * sizeof(uint32_t)));
+    ASW_TRY(cnt.ensure(plane * sizeof(uint16_t)));
+    ASW_TRY(f->disp.ensure(plane * 4));
+    f->vol_floats = 0;
+    if (keep_volume) {
+        ASW_TRY(f->vol.ensure(plane * n * 4));
+        f->vol_floats = plane * n;
+    }
+    const uint8_t* dL = f->L.as<uint8_t>();
+    const uint8_t* dR = f->R.as<uint8_t>();
+    ASW_TRY(launch_cost_ad(ctx->stream, dL, dR, H, W, f->channels, mp.disparity_type, mp.minD, n, 0, 0, raw.as<uint8_t>()));
+    ASW_HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
+    ASW_TRY(launch_cross_arms(ctx->stream, mp.disparity_type == ASW_DISPARITY_RIGHT ? dR : dL, H, W, f->channels, mp.win, mp.cross_tau,
+                              arms.as<uint32_t>(), cnt.as<uint16_t>()));
+    ASW_TRY(launch_cross_aggregate(ctx->stream, raw.as<uint8_t>(), arms.as<uint32_t>(), cnt.as<uint16_t>(), H, W, mp.win, mp.cross_trunc,
+                                   mp.minD, n, keep_volume ? f->vol.as<float>() : nullptr, f->disp.as<float>()));
+    ASW_HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
+    ctx->timing.aggregate_launches = 3;  // arms, region sizes, aggregation + WTA
+    return ASW_OK;
+}
+
 // Sub-pixel flags of a caller's disparity_type -> mp.subpixel, mp.disparity_type without them.  A value
 // without a flag bit passes through as it is: the methods refuse what they refused before, with the statuses they had.
 static int decode_subpixel(int algorithm, MatchParams& mp)
@@ -813,6 +854,7 @@ int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp_in, 
     f->invalidate_results();  // whatever the slot's disparity / volume were, they are not this call's
     MatchParams mp = mp_in;
     if (mp.numD <= 0 || mp.minD < 0) return ASW_ERR_BAD_ARGUMENT;
+    ASW_TRY(decode_algorithm(algorithm, &algorithm, &mp.cross_tau, &mp.cross_trunc));  // asw_alg_cross() values -> 12 + parameters
     ASW_TRY(decode_subpixel(algorithm, mp));
     // the sub-pixel kernel reads the aggregated volume: the methods that can skip it (bilateral / direct8, geodesic, BLO1, the
     // bilateral grid) are asked for it; what the CALLER keeps is decided below
@@ -832,6 +874,7 @@ int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp_in, 
     case ASW_ALG_NCC: rc = run_ncc(ctx, f, mp, want_volume); break;
     case ASW_ALG_ADAPTIVE_WEIGHT_MEDIAN: rc = run_wmedian(ctx, f, mp, want_volume); break;
     case ASW_ALG_SGBM: rc = run_sgbm(ctx, f, mp); break;
+    case ASW_ALG_ADAPTIVE_WEIGHT_CROSS: rc = run_cross(ctx, f, mp, want_volume); break;
     default: rc = ASW_ERR_UNSUPPORTED_METHOD; break;
     }
     if (rc == ASW_OK && mp.subpixel)  // after the aggregation events: counts in total_ms and cost_ms, not in aggregate_ms
@@ -937,6 +980,8 @@ int match_refined(asw_ctx* ctx, Frame* f, int algorithm, int win_size, int min_d
     f->invalidate_results();
     if (algorithm == ASW_ALG_SGBM || algorithm == ASW_ALG_BM) return ASW_ERR_UNSUPPORTED_METHOD;  // they carry their own disp12MaxDiff
     if (num_disparity <= 0 || min_disparity < 0) return ASW_ERR_BAD_ARGUMENT;  // as a plain match (run_method)
+    int plain;  // unused: a bad asw_alg_cross() value is refused here with its own status, as a plain match refuses it
+    ASW_TRY(decode_algorithm(algorithm, &plain, nullptr, nullptr));
     RefineParams rp;
     rp.minD = min_disparity; rp.n = asw_volume_planes(algorithm, num_disparity); rp.max_diff = max_diff; rp.win = refine_win;
     rp.gamma_c = gamma_c; rp.gamma_s = gamma_s;

@@ -38,7 +38,8 @@ enum DisparityType { DISPARITY_LEFT = 0, DISPARITY_RIGHT = 1 };
 enum StereoMatchingAlgorithms {
     BM = 0, SGBM = 1, ADAPTIVE_WEIGHT = 2, ADAPTIVE_WEIGHT_8DIRECT = 3, ADAPTIVE_WEIGHT_GEODESIC = 4,
     ADAPTIVE_WEIGHT_BILATERAL_GRID = 5, ADAPTIVE_WEIGHT_BLO1 = 6, ADAPTIVE_WEIGHT_GUIDED_FILTER = 7,
-    ADAPTIVE_WEIGHT_GUIDED_FILTER_2 = 8, ADAPTIVE_WEIGHT_GUIDED_FILTER_3 = 9, ADAPTIVE_WEIGHT_MEDIAN = 10, NCC = 11
+    ADAPTIVE_WEIGHT_GUIDED_FILTER_2 = 8, ADAPTIVE_WEIGHT_GUIDED_FILTER_3 = 9, ADAPTIVE_WEIGHT_MEDIAN = 10, NCC = 11,
+    ADAPTIVE_WEIGHT_CROSS = 12  // not in the reference: cross-based support regions (asw_mi355x.h)
 };
 #endif
 // Not in the reference: the sub-pixel rules of asw_mi355x.h (ASW_DISPARITY_SUBPIXEL_*), for stereoMatchingSubpixel below
@@ -372,6 +373,16 @@ inline AswMat computeAdaptiveWeight_BLO1(AswMat leftImg, AswMat rightImg, Dispar
     return asw::detail::aggregate(leftImg, rightImg, [&](asw_ctx* c, asw_image* l, asw_image* r, asw_image* o) {
         return asw_aggregate_blo1(c, l, r, o, (int)dispType, sampleRateR, winSize, minDisparity, numDisparity, nullptr, 0);
     }, "computeAdaptiveWeight_BLO1");
+}
+
+// Not in the reference: cross-based support-region aggregation (asw_aggregate_cross) -> the f32 map; empty Mat
+// for an even window
+inline AswMat computeAdaptiveWeight_cross(AswMat leftImg, AswMat rightImg, DisparityType dispType = DISPARITY_LEFT, int tau = 20,
+                                          int trunc = 20, int winSize = 15, int minDisparity = 0, int numDisparity = 64)
+{
+    return asw::detail::aggregate(leftImg, rightImg, [&](asw_ctx* c, asw_image* l, asw_image* r, asw_image* o) {
+        return asw_aggregate_cross(c, l, r, o, (int)dispType, tau, trunc, winSize, minDisparity, numDisparity, nullptr, 0);
+    }, "computeAdaptiveWeight_cross");
 }
 
 // Not in the reference: the cross-check that consumes a DISPARITY_LEFT and a DISPARITY_RIGHT map (asw_lr_check)

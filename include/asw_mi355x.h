@@ -74,8 +74,34 @@ enum {
     ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER_2 = 8,
     ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER_3 = 9,
     ASW_ALG_ADAPTIVE_WEIGHT_MEDIAN = 10,
-    ASW_ALG_NCC = 11
+    ASW_ALG_NCC = 11,
+    ASW_ALG_ADAPTIVE_WEIGHT_CROSS = 12 /* not in the reference: cross-based support regions, below */
 };
+
+/* ---- cross-based support-region aggregation (Zhang, Lu, Lafruit 2009; not in the reference) ----
+ * Selector entry 12 of every call that takes `algorithm` (asw_stereo_match, asw_match_resident, asw_stereo_match_batch,
+ * asw_match_refined_resident, asw_stereo_match_refined); both directions, 1- or 3-channel 8U pairs, the sub-pixel flags as for the
+ * other methods.  I = the view image (left for DISPARITY_LEFT, right for DISPARITY_RIGHT), L = win_size / 2, all integer:
+ *   e(x,y,d) = min(trunc, AD(x,y,d)), AD the u8 value asw_cost_ad returns for the same direction (borders included);
+ *   arm a_u(p), u = left / right / up / down: the largest r in [0, L] with p + k u inside the image and
+ *     max_c |I_c(p + k u) - I_c(p)| <= tau for every k = 1..r (against the anchor p);
+ *   S(p,d) = sum over y' = y - up(p) .. y + down(p) of sum over x' = x - left(x,y') .. x + right(x,y') of e(x',y',d), N(p) the same
+ *     sum of 1 (<= 35 * 35; S < 2^24);
+ *   volume E = (float)S / (float)N, one correctly rounded division, [num_d][rows][cols]; map: strict '<' in ascending d, min_d + index.
+ * win_size odd in 1..35 (even: ASW_ERR_EVEN_WINDOW, above 35: ASW_ERR_BAD_ARGUMENT); rows * cols < 2^31 and rows <= 262140 (the sums the kernels keep are
+ * local to a tile and cannot leave int32).  The plain value 12 runs tau = 20, trunc = 20; asw_alg_cross(tau, trunc) forms a value of
+ * `algorithm` that carries other parameters: bits 0-7 = 12, bits 8-15 = tau (0..255), bits 16-23 = trunc (1..255), bit 30 set
+ * (ASW_ALG_CROSS_PARAMS), bits 24-29 and 31 clear.  With bit 30 set a low byte other than 12 gives ASW_ERR_UNSUPPORTED_METHOD, and
+ * trunc = 0 or any of bits 24-29 / 31 gives ASW_ERR_BAD_ARGUMENT (asw_alg_cross sets bit 24 for an argument out of range);
+ * asw_volume_planes is num_disparity for 12 and every valid encoded value, 0 for the invalid ones.  asw_get_timing: aggregate_ms /
+ * aggregate_launches cover the arm, region-size and aggregation kernels, cost_ms the rest.  asw_aggregate_cross (an inline function,
+ * after asw_stereo_match below) is the per-method form; neither is a symbol of the library. */
+enum { ASW_ALG_CROSS_PARAMS = 0x40000000 };
+static inline int asw_alg_cross(int tau, int trunc)
+{
+    const int bad = (tau < 0 || tau > 255 || trunc < 1 || trunc > 255) ? 0x01000000 : 0;
+    return ASW_ALG_CROSS_PARAMS | bad | ((trunc & 0xFF) << 16) | ((tau & 0xFF) << 8) | ASW_ALG_ADAPTIVE_WEIGHT_CROSS;
+}
 
 /* cv::Mat depth codes */
 enum { ASW_8U = 0, ASW_16S = 3, ASW_32F = 5 };
@@ -128,6 +154,15 @@ int asw_set_gray_bits(asw_ctx* ctx, int bits);
 int asw_stereo_match(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp,
                      int disparity_type, int algorithm, int win_size, int min_disparity, int num_disparity,
                      float* cost_volume_out, size_t cost_volume_floats);
+
+/* Cross-based support regions with explicit parameters (above): asw_stereo_match with algorithm = asw_alg_cross(tau, trunc). */
+static inline int asw_aggregate_cross(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp, int disparity_type,
+                                      int tau, int trunc, int win_size, int min_disparity, int num_disparity, float* cost_volume_out,
+                                      size_t cost_volume_floats)
+{
+    return asw_stereo_match(ctx, left, right, disp, disparity_type, asw_alg_cross(tau, trunc), win_size, min_disparity, num_disparity,
+                            cost_volume_out, cost_volume_floats);
+}
 
 /* Planes of the cost volume `algorithm` produces for num_disparity candidates (what cost_volume_out must hold);
  * 0 for an algorithm without a selector volume: BM (not served) and SGBM (a non-NULL cost_volume_out is refused with

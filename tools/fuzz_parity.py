@@ -15,6 +15,11 @@ mismatch prints the tag that matcher_cases.build_case(leg, tag[1:]) rebuilds the
 The leg sgbm_paths is asw_sgbm_paths against tests/sgbm_paths_ref.py, map and volume: its tag is an sgbm tag followed by a random
 admissible mask of path directions (a superset of the three), its widths drawn so that nine cases in ten have valid columns for the
 added directions to work on.
+
+The leg cross is the cross-based support-region method (selector entry 12) against tests/cross_ref.py, volume and map, with and
+without the kept volume; its cases come from cross_ref.random_case and a mismatch prints the tag cross_ref.build_case rebuilds.
+
+    python tools/fuzz_parity.py --seconds 120 --seed 1 --only cross
 """
 import argparse
 import os
@@ -29,11 +34,12 @@ from aswstereomatch_amd.synth import make_pair  # noqa: E402
 from oracle import asw_oracle as O  # noqa: E402
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+import cross_ref as cr  # noqa: E402
 import matcher_cases as mc  # noqa: E402
 
 A = asw.StereoMatchingAlgorithms
 # checked against the CPU oracle (oracle/); the legs (mc.FAMILIES) are checked against the restatements under tests/
-LEGS = tuple(mc.FAMILIES)
+LEGS = tuple(mc.FAMILIES) + ("cross",)
 ORACLE_METHODS = ["classic", "direct8", "geodesic", "guided", "guided2", "guided3", "wmedian", "blo1", "ncc", "ncc_cost",
                   "ad_tad", "similarity", "sad", "geodist", "gfilter", "prep", "bilgrid", "lrcheck", "resident", "batch"]
 
@@ -77,7 +83,7 @@ def main():
     while time.time() - t0 < args.seconds:
         if rng_mc.random() < leg_share:  # the integer kernels: inputs and every parameter come from tests/matcher_cases.py
             method = legs[int(rng_mc.integers(0, len(legs)))]
-            case = mc.random_case(rng_mc, method, n)
+            case = cr.random_case(rng_mc, n) if method == "cross" else mc.random_case(rng_mc, method, n)
             tag = (method,) + case["tag"]
         else:
             H = int(rng.integers(1, args.max_h))
@@ -139,7 +145,10 @@ def main():
         if args.trace:
             print("case", n, tag, flush=True)
         try:
-            if method in mc.FAMILIES:
+            if method == "cross":
+                (v, d, d2), (vw, dw) = cr.gpu_result(ctx, case)
+                ok = np.array_equal(v, vw) and np.array_equal(d, dw) and np.array_equal(d2, dw)
+            elif method in mc.FAMILIES:
                 ok = mc.same(*mc.gpu_result(ctx, case))
             elif method == "classic":
                 gc, gg = float(rng.choice([30, 5, 0.5, 100])), float(rng.choice([20, 2, 7.5, 60]))
