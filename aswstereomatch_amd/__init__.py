@@ -57,6 +57,7 @@ class StereoMatchingAlgorithms(enum.IntEnum):  # parametersStereo.h:10-24
     ADAPTIVE_WEIGHT_CROSS = 12  # not in the reference: cross-based support regions
 
 
+_A = StereoMatchingAlgorithms
 DISPARITY_LEFT = DisparityType.DISPARITY_LEFT
 DISPARITY_RIGHT = DisparityType.DISPARITY_RIGHT
 # Sub-pixel disparity (asw_mi355x.h: ASW_DISPARITY_SUBPIXEL_*): OR one of them into a disparity type,
@@ -187,14 +188,17 @@ class Context:
             return (None, None) if return_cost_volume else None
         return (disp, vol) if return_cost_volume else disp
 
-    def _aggregate(self, fn, name, n_vol, leftImg, rightImg, args, return_cost_volume):
+    def _aggregate(self, name, algorithm, numDisparity, leftImg, rightImg, args, return_cost_volume, fn=None):
+        """One per-method entry point `name` (or the call `fn` standing for it); the library says how many planes the volume of
+        `algorithm` has (asw_volume_planes)."""
+        fn = fn or getattr(self._lib, name)
         li, la = _image(leftImg)
         ri, ra = _image(rightImg)
         disp = np.zeros((la.shape[0], la.shape[1]), np.float32)
         di, _ = _image(disp, 5)
         vol, pv = None, None
         if return_cost_volume:
-            vol = np.zeros((n_vol, la.shape[0], la.shape[1]), np.float32)
+            vol = np.zeros((self._candidates(algorithm, numDisparity), la.shape[0], la.shape[1]), np.float32)
             pv = vol.ctypes.data_as(C.c_void_p)
         rc = fn(self._h, C.byref(li), C.byref(ri), C.byref(di), *args, pv, 0 if vol is None else vol.size)
         if not self._finish(rc, name):
@@ -204,35 +208,35 @@ class Context:
     # ---- per-method entry points (M.h:133-182) ----
     def computeAdaptiveWeight(self, leftImg, rightImg, gamma_c=30, gamma_g=2, dispType=DISPARITY_LEFT, winSize=7,
                               minDisparity=186, numDisparity=144, return_cost_volume=False):
-        return self._aggregate(self._lib.asw_aggregate_bilateral, "asw_aggregate_bilateral", numDisparity + 1, leftImg,
-                               rightImg, (float(gamma_c), float(gamma_g), int(dispType), winSize, minDisparity, numDisparity),
+        return self._aggregate("asw_aggregate_bilateral", _A.ADAPTIVE_WEIGHT, numDisparity, leftImg, rightImg,
+                               (float(gamma_c), float(gamma_g), int(dispType), winSize, minDisparity, numDisparity),
                                return_cost_volume)
 
     def computeAdaptiveWeight_direct8(self, leftImg, rightImg, dispType=DISPARITY_LEFT, winSize=7, minDisparity=186,
                                       numDisparity=144, return_cost_volume=False):
         """M.h:135-136, M.cpp:1167-1319 (DISPARITY_LEFT only: the reference's RIGHT branch is undefined behaviour)."""
-        return self._aggregate(self._lib.asw_aggregate_direct8, "asw_aggregate_direct8", numDisparity + 1, leftImg,
-                               rightImg, (int(dispType), winSize, minDisparity, numDisparity), return_cost_volume)
+        return self._aggregate("asw_aggregate_direct8", _A.ADAPTIVE_WEIGHT_8DIRECT, numDisparity, leftImg, rightImg,
+                               (int(dispType), winSize, minDisparity, numDisparity), return_cost_volume)
 
     def computeAdaptiveWeight_geodesic(self, leftImg, rightImg, dispType=DISPARITY_LEFT, winSize=7, minDisparity=186,
                                        numDisparity=144, return_cost_volume=False):
-        return self._aggregate(self._lib.asw_aggregate_geodesic, "asw_aggregate_geodesic", numDisparity + 1, leftImg,
-                               rightImg, (int(dispType), winSize, minDisparity, numDisparity), return_cost_volume)
+        return self._aggregate("asw_aggregate_geodesic", _A.ADAPTIVE_WEIGHT_GEODESIC, numDisparity, leftImg, rightImg,
+                               (int(dispType), winSize, minDisparity, numDisparity), return_cost_volume)
 
     def computeAdaptiveWeight_GuidedF(self, leftImg, rightImg, dispType=DISPARITY_LEFT, eps=1e-8, winSize=35,
                                       minDisparity=186, numDisparity=144, return_cost_volume=False):
-        return self._aggregate(self._lib.asw_aggregate_guided, "asw_aggregate_guided", numDisparity, leftImg, rightImg,
+        return self._aggregate("asw_aggregate_guided", _A.ADAPTIVE_WEIGHT_GUIDED_FILTER, numDisparity, leftImg, rightImg,
                                (int(dispType), float(eps), winSize, minDisparity, numDisparity), return_cost_volume)
 
     def computeAdaptiveWeight_GuidedF_2(self, leftImg, rightImg, dispType=DISPARITY_LEFT, eps=1e-8, winSize=35,
                                         minDisparity=186, numDisparity=144, return_cost_volume=False):
-        return self._aggregate(self._lib.asw_aggregate_guided2, "asw_aggregate_guided2", numDisparity, leftImg, rightImg,
+        return self._aggregate("asw_aggregate_guided2", _A.ADAPTIVE_WEIGHT_GUIDED_FILTER_2, numDisparity, leftImg, rightImg,
                                (int(dispType), float(eps), winSize, minDisparity, numDisparity), return_cost_volume)
 
     def computeAdaptiveWeight_GuidedF_3(self, leftImg, rightImg, dispType=DISPARITY_LEFT, eps=1e-6, winSize=35,
                                         minDisparity=186, numDisparity=144, return_cost_volume=False):
         """M.h:174-176, M.cpp:3063-3137: NCC costs + guided filter."""
-        return self._aggregate(self._lib.asw_aggregate_guided3, "asw_aggregate_guided3", numDisparity, leftImg, rightImg,
+        return self._aggregate("asw_aggregate_guided3", _A.ADAPTIVE_WEIGHT_GUIDED_FILTER_3, numDisparity, leftImg, rightImg,
                                (int(dispType), float(eps), winSize, minDisparity, numDisparity), return_cost_volume)
 
     def computeNCC(self, leftImg, rightImg, dispType=DISPARITY_LEFT, winSize=7, minDisparity=0, numDisparity=30):
@@ -254,20 +258,20 @@ class Context:
 
     def computeAdaptiveWeight_BLO1(self, leftImg, rightImg, dispType=DISPARITY_LEFT, sampleRateR=10, winSize=35,
                                    minDisparity=186, numDisparity=144, return_cost_volume=False):
-        return self._aggregate(self._lib.asw_aggregate_blo1, "asw_aggregate_blo1", numDisparity, leftImg, rightImg,
+        return self._aggregate("asw_aggregate_blo1", _A.ADAPTIVE_WEIGHT_BLO1, numDisparity, leftImg, rightImg,
                                (int(dispType), float(sampleRateR), winSize, minDisparity, numDisparity), return_cost_volume)
 
     def computeAdaptiveWeight_bilateralGrid(self, leftImg, rightImg, dispType=DISPARITY_LEFT, sampleRateS=10, sampleRateR=10,
                                             minDisparity=186, numDisparity=144, return_cost_volume=False):
         """M.h:155-157, M.cpp:2253-2430 (DISPARITY_LEFT only: the reference's RIGHT branch reads past the image row)."""
-        return self._aggregate(self._lib.asw_aggregate_bilgrid, "asw_aggregate_bilgrid", numDisparity + 1, leftImg, rightImg,
+        return self._aggregate("asw_aggregate_bilgrid", _A.ADAPTIVE_WEIGHT_BILATERAL_GRID, numDisparity, leftImg, rightImg,
                                (int(dispType), float(sampleRateS), float(sampleRateR), minDisparity, numDisparity),
                                return_cost_volume)
 
     def computeAdaptiveWeight_WeightedMedian(self, leftImg, rightImg, dispType=DISPARITY_LEFT, winSize=35,
                                              sampleRateS=10, sampleRateR=10, minDisparity=186, numDisparity=144,
                                              return_cost_volume=False):
-        return self._aggregate(self._lib.asw_aggregate_wmedian, "asw_aggregate_wmedian", numDisparity, leftImg, rightImg,
+        return self._aggregate("asw_aggregate_wmedian", _A.ADAPTIVE_WEIGHT_MEDIAN, numDisparity, leftImg, rightImg,
                                (int(dispType), winSize, float(sampleRateS), float(sampleRateR), minDisparity, numDisparity),
                                return_cost_volume)
 
@@ -278,7 +282,8 @@ class Context:
         def call(h, l, r, d, *args):
             return self._lib.asw_stereo_match(h, l, r, d, int(dispType), cross_algorithm(tau, trunc), winSize, minDisparity,
                                               numDisparity, *args)
-        return self._aggregate(call, "asw_aggregate_cross", numDisparity, leftImg, rightImg, (), return_cost_volume)
+        return self._aggregate("asw_aggregate_cross", _A.ADAPTIVE_WEIGHT_CROSS, numDisparity, leftImg, rightImg, (), return_cost_volume,
+                               fn=call)
 
     # ---- semi-global block matching ----
     def getDisparity_SGBM(self, srcLeft, srcRight, winSize=15, minDisparity=0, numDisparity=64):

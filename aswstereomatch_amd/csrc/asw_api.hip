@@ -20,7 +20,8 @@ int match_host(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_
     ASW_TRY(check_pair(left, right));
     ASW_TRY(check_disp_out(disp, left->rows, left->cols));
     if (cost_volume_out) {  // the caller states what its buffer holds; a short one is refused before anything is written
-        if (algorithm == ASW_ALG_SGBM) return ASW_ERR_BAD_ARGUMENT;  // the selector's SGBM has no volume (asw_sgbm has S)
+        const MethodInfo* m = method_info(algorithm);
+        if (m && m->run && m->no_volume) return ASW_ERR_BAD_ARGUMENT;  // the selector's SGBM has no volume (asw_sgbm has S)
         const int planes = asw_volume_planes(algorithm, mp.numD);
         if (planes > 0 && cost_volume_floats < (size_t)planes * left->rows * left->cols) return ASW_ERR_BAD_ARGUMENT;
     }
@@ -40,10 +41,11 @@ int decode_algorithm(int algorithm, int* method, int* tau, int* trunc)
 {
     *method = algorithm;
     if (!(algorithm & ASW_ALG_CROSS_PARAMS)) return ASW_OK;
-    if ((algorithm & 0xFF) != ASW_ALG_ADAPTIVE_WEIGHT_CROSS) return ASW_ERR_UNSUPPORTED_METHOD;
+    const MethodInfo* m = method_info(algorithm & 0xFF);
+    if (!m || !m->packed_params) return ASW_ERR_UNSUPPORTED_METHOD;
     const int t = (algorithm >> 16) & 0xFF;
     if (t == 0 || (algorithm & 0x3F000000) || algorithm < 0) return ASW_ERR_BAD_ARGUMENT;  // bits 24..29 and 31 stay clear
-    *method = ASW_ALG_ADAPTIVE_WEIGHT_CROSS;
+    *method = m->algorithm;
     if (tau) *tau = (algorithm >> 8) & 0xFF;
     if (trunc) *trunc = t;
     return ASW_OK;
@@ -52,40 +54,23 @@ int decode_algorithm(int algorithm, int* method, int* tau, int* trunc)
 extern "C" int asw_volume_planes(int algorithm, int num_disparity)
 {
     if (decode_algorithm(algorithm, &algorithm, nullptr, nullptr) != ASW_OK) return 0;
-    switch (algorithm) {
-    case ASW_ALG_ADAPTIVE_WEIGHT:            // offset <= max_offset, M.cpp:1021,1074
-    case ASW_ALG_ADAPTIVE_WEIGHT_8DIRECT:    // M.cpp:1171
-    case ASW_ALG_ADAPTIVE_WEIGHT_GEODESIC:   // M.cpp:1447,1467
-    case ASW_ALG_ADAPTIVE_WEIGHT_BILATERAL_GRID:  // M.cpp:2256,2280
-        return num_disparity + 1;
-    case ASW_ALG_ADAPTIVE_WEIGHT_BLO1:
-    case ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER:
-    case ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER_2:
-    case ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER_3:
-    case ASW_ALG_ADAPTIVE_WEIGHT_MEDIAN:
-    case ASW_ALG_NCC:
-    case ASW_ALG_ADAPTIVE_WEIGHT_CROSS:
-        return num_disparity;
-    default:
-        return 0;
-    }
+    const MethodInfo* m = method_info(algorithm);
+    return m ? m->planes(num_disparity) : 0;
 }
 
 extern "C" int asw_stereo_match(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp,
                                 int disparity_type, int algorithm, int win_size, int min_disparity,
                                 int num_disparity, float* cost_volume_out, size_t cost_volume_floats)
 {
-    MatchParams mp;
-    mp.disparity_type = disparity_type; mp.win = win_size; mp.minD = min_disparity; mp.numD = num_disparity;
-    return match_host(ctx, left, right, disp, algorithm, mp, cost_volume_out, cost_volume_floats);
+    return match_host(ctx, left, right, disp, algorithm, match_params(disparity_type, win_size, min_disparity, num_disparity),
+                      cost_volume_out, cost_volume_floats);
 }
 
 extern "C" int asw_aggregate_bilateral(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp,
                                        double gamma_c, double gamma_g, int disparity_type, int win_size,
                                        int min_disparity, int num_disparity, float* cost_volume_out, size_t cost_volume_floats)
 {
-    MatchParams mp;
-    mp.disparity_type = disparity_type; mp.win = win_size; mp.minD = min_disparity; mp.numD = num_disparity;
+    MatchParams mp = match_params(disparity_type, win_size, min_disparity, num_disparity);
     mp.gamma_c = gamma_c; mp.gamma_g = gamma_g;
     return match_host(ctx, left, right, disp, ASW_ALG_ADAPTIVE_WEIGHT, mp, cost_volume_out, cost_volume_floats);
 }
@@ -94,14 +79,32 @@ extern "C" int asw_aggregate_direct8(asw_ctx* ctx, const asw_image* left, const 
                                      int disparity_type, int win_size, int min_disparity, int num_disparity,
                                      float* cost_volume_out, size_t cost_volume_floats)
 {
-    MatchParams mp;
-    mp.disparity_type = disparity_type; mp.win = win_size; mp.minD = min_disparity; mp.numD = num_disparity;
-    return match_host(ctx, left, right, disp, ASW_ALG_ADAPTIVE_WEIGHT_8DIRECT, mp, cost_volume_out, cost_volume_floats);
+    return match_host(ctx, left, right, disp, ASW_ALG_ADAPTIVE_WEIGHT_8DIRECT,
+                      match_params(disparity_type, win_size, min_disparity, num_disparity), cost_volume_out, cost_volume_floats);
 }
 
 // ------------------------------------------------------------------------------------------
 // cost builders and small building blocks
 // ------------------------------------------------------------------------------------------
+// the caller's two images into the stage buffers "stageL" / "stageR" (shared by every building block on purpose)
+static int upload_stage_pair(asw_ctx* ctx, const asw_image* a, const asw_image* b, const uint8_t** da, const uint8_t** db)
+{
+    DevBuf& sa = ctx->buf("stageL");
+    DevBuf& sb = ctx->buf("stageR");
+    ASW_TRY(upload_image(ctx, a, sa));
+    ASW_TRY(upload_image(ctx, b, sb));
+    *da = sa.as<uint8_t>(); *db = sb.as<uint8_t>();
+    return ASW_OK;
+}
+
+// a device result into the caller's buffer; returns once it is there
+static int download_sync(asw_ctx* ctx, void* dst, const void* src, size_t bytes)
+{
+    ASW_HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ASW_OK;
+}
+
 static int cost_ad_common(asw_ctx* ctx, const asw_image* left, const asw_image* right, uint8_t* cost, int disparity_type,
                           int do_thresh, int threshold, int minD, int numD)
 {
@@ -112,18 +115,13 @@ static int cost_ad_common(asw_ctx* ctx, const asw_image* left, const asw_image* 
     if (disparity_type != ASW_DISPARITY_LEFT && disparity_type != ASW_DISPARITY_RIGHT) return ASW_ERR_BAD_ARGUMENT;
     ASW_HIP_TRY(hipSetDevice(ctx->device));
     const int H = left->rows, W = left->cols, C = left->channels;
-    DevBuf& dl = ctx->buf("stageL");
-    DevBuf& dr = ctx->buf("stageR");
+    const uint8_t *dl, *dr;
     DevBuf& dc = ctx->buf("cost_u8");
-    ASW_TRY(upload_image(ctx, left, dl));
-    ASW_TRY(upload_image(ctx, right, dr));
+    ASW_TRY(upload_stage_pair(ctx, left, right, &dl, &dr));
     size_t bytes = (size_t)numD * H * W;
     ASW_TRY(dc.ensure(bytes));
-    ASW_TRY(launch_cost_ad(ctx->stream, dl.as<uint8_t>(), dr.as<uint8_t>(), H, W, C, disparity_type, minD, numD, do_thresh,
-                           threshold, dc.as<uint8_t>()));
-    ASW_HIP_TRY(hipMemcpyAsync(cost, dc.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return ASW_OK;
+    ASW_TRY(launch_cost_ad(ctx->stream, dl, dr, H, W, C, disparity_type, minD, numD, do_thresh, threshold, dc.as<uint8_t>()));
+    return download_sync(ctx, cost, dc.p, bytes);
 }
 
 extern "C" int asw_cost_ad(asw_ctx* ctx, const asw_image* left, const asw_image* right, uint8_t* cost,
@@ -156,9 +154,7 @@ extern "C" int asw_bgr2gray(asw_ctx* ctx, const asw_image* bgr, uint8_t* gray)
     size_t n = (size_t)bgr->rows * bgr->cols;
     ASW_TRY(g.ensure(n));
     ASW_TRY(launch_bgr2gray(ctx->stream, d.as<uint8_t>(), bgr->rows, bgr->cols, g.as<uint8_t>(), ctx->gray_bits));
-    ASW_HIP_TRY(hipMemcpyAsync(gray, g.p, n, hipMemcpyDeviceToHost, ctx->stream));
-    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return ASW_OK;
+    return download_sync(ctx, gray, g.p, n);
 }
 
 extern "C" int asw_wta(asw_ctx* ctx, const float* cost_volume, int n, int rows, int cols, int min_disparity, float* disp)
@@ -172,9 +168,7 @@ extern "C" int asw_wta(asw_ctx* ctx, const float* cost_volume, int n, int rows, 
     ASW_TRY(d.ensure(plane * 4));
     ASW_HIP_TRY(hipMemcpyAsync(v.p, cost_volume, plane * n * 4, hipMemcpyHostToDevice, ctx->stream));
     ASW_TRY(launch_wta(ctx->stream, v.as<float>(), n, rows, cols, min_disparity, d.as<float>()));
-    ASW_HIP_TRY(hipMemcpyAsync(disp, d.p, plane * 4, hipMemcpyDeviceToHost, ctx->stream));
-    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return ASW_OK;
+    return download_sync(ctx, disp, d.p, plane * 4);
 }
 
 extern "C" int asw_lr_check(asw_ctx* ctx, const float* disp_left, const float* disp_right, int rows, int cols, float max_diff,
@@ -206,8 +200,8 @@ extern "C" int asw_aggregate_guided(asw_ctx* ctx, const asw_image* left, const a
                                     int disparity_type, double eps, int win_size, int min_disparity, int num_disparity,
                                     float* cost_volume_out, size_t cost_volume_floats)
 {
-    MatchParams mp;
-    mp.disparity_type = disparity_type; mp.win = win_size; mp.minD = min_disparity; mp.numD = num_disparity; mp.eps = eps;
+    MatchParams mp = match_params(disparity_type, win_size, min_disparity, num_disparity);
+    mp.eps = eps;
     return match_host(ctx, left, right, disp, ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER, mp, cost_volume_out, cost_volume_floats);
 }
 
@@ -215,8 +209,8 @@ extern "C" int asw_aggregate_guided2(asw_ctx* ctx, const asw_image* left, const 
                                      int disparity_type, double eps, int win_size, int min_disparity, int num_disparity,
                                      float* cost_volume_out, size_t cost_volume_floats)
 {
-    MatchParams mp;
-    mp.disparity_type = disparity_type; mp.win = win_size; mp.minD = min_disparity; mp.numD = num_disparity; mp.eps = eps;
+    MatchParams mp = match_params(disparity_type, win_size, min_disparity, num_disparity);
+    mp.eps = eps;
     return match_host(ctx, left, right, disp, ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER_2, mp, cost_volume_out, cost_volume_floats);
 }
 
@@ -232,14 +226,11 @@ extern "C" int asw_cost_similarity(asw_ctx* ctx, const asw_image* left, const as
     if (left->channels != 3 || disparity_type != ASW_DISPARITY_LEFT) return ASW_ERR_UNSUPPORTED_LAYOUT;
     ASW_HIP_TRY(hipSetDevice(ctx->device));
     const int H = left->rows, W = left->cols, n = num_disparity, h = win_size / 2;
-    DevBuf& dl = ctx->buf("stageL");
-    DevBuf& dr = ctx->buf("stageR");
+    const uint8_t *dl, *dr;
     DevBuf& raw = ctx->buf("g_raw");
-    ASW_TRY(upload_image(ctx, left, dl));
-    ASW_TRY(upload_image(ctx, right, dr));
+    ASW_TRY(upload_stage_pair(ctx, left, right, &dl, &dr));
     ASW_TRY(raw.ensure((size_t)n * H * W * 4));
-    ASW_TRY(build_similarity_volume(ctx, dl.as<uint8_t>(), dr.as<uint8_t>(), H, W, min_disparity, n, regularity, thres_c, thres_g,
-                                    raw.as<float>()));
+    ASW_TRY(build_similarity_volume(ctx, dl, dr, H, W, min_disparity, n, regularity, thres_c, thres_g, raw.as<float>()));
     const float* src = raw.as<float>();
     size_t out_floats = (size_t)n * H * W;
     if (win_size > 0) {
@@ -249,9 +240,7 @@ extern "C" int asw_cost_similarity(asw_ctx* ctx, const asw_image* left, const as
         ASW_TRY(launch_pad_reflect(ctx->stream, raw.as<float>(), n, H, W, h, pad.as<float>()));
         src = pad.as<float>();
     }
-    ASW_HIP_TRY(hipMemcpyAsync(cost, src, out_floats * 4, hipMemcpyDeviceToHost, ctx->stream));
-    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return ASW_OK;
+    return download_sync(ctx, cost, src, out_floats * 4);
 }
 
 extern "C" int asw_cost_sad(asw_ctx* ctx, const asw_image* left, const asw_image* right, float* cost, int disparity_type,
@@ -265,26 +254,13 @@ extern "C" int asw_cost_sad(asw_ctx* ctx, const asw_image* left, const asw_image
     if (disparity_type != ASW_DISPARITY_LEFT && disparity_type != ASW_DISPARITY_RIGHT) return ASW_ERR_BAD_ARGUMENT;
     ASW_HIP_TRY(hipSetDevice(ctx->device));
     const int H = left->rows, W = left->cols, n = num_disparity;
-    DevBuf& dl = ctx->buf("stageL");
-    DevBuf& dr = ctx->buf("stageR");
-    DevBuf& gl = ctx->buf("grayL");
-    DevBuf& gr = ctx->buf("grayR");
+    const uint8_t *pl, *pr;
     DevBuf& raw = ctx->buf("g_raw");
-    ASW_TRY(upload_image(ctx, left, dl));
-    ASW_TRY(upload_image(ctx, right, dr));
+    ASW_TRY(upload_stage_pair(ctx, left, right, &pl, &pr));
     ASW_TRY(raw.ensure((size_t)n * H * W * 4));
-    const uint8_t *pl = dl.as<uint8_t>(), *pr = dr.as<uint8_t>();
-    if (left->channels == 3) {  // M.cpp:2446-2456
-        ASW_TRY(gl.ensure((size_t)H * W));
-        ASW_TRY(gr.ensure((size_t)H * W));
-        ASW_TRY(launch_bgr2gray(ctx->stream, pl, H, W, gl.as<uint8_t>(), ctx->gray_bits));
-        ASW_TRY(launch_bgr2gray(ctx->stream, pr, H, W, gr.as<uint8_t>(), ctx->gray_bits));
-        pl = gl.as<uint8_t>(); pr = gr.as<uint8_t>();
-    }
+    ASW_TRY(gray_pair(ctx, pl, pr, left->channels, H, W, &pl, &pr));  // M.cpp:2446-2456
     ASW_TRY(launch_cost_sad(ctx->stream, pl, pr, H, W, disparity_type, win_size, min_disparity, n, raw.as<float>()));
-    ASW_HIP_TRY(hipMemcpyAsync(cost, raw.p, (size_t)n * H * W * 4, hipMemcpyDeviceToHost, ctx->stream));
-    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return ASW_OK;
+    return download_sync(ctx, cost, raw.p, (size_t)n * H * W * 4);
 }
 
 // getCostSAD_d (M.cpp:2442-2503) as the reference declares it: one disparity, the other view pre-bordered by the caller
@@ -307,20 +283,16 @@ extern "C" int asw_cost_sad_d(asw_ctx* ctx, const asw_image* left, const asw_ima
     const int x0 = lref ? Wb - W - disparity : disparity;  // M.cpp:2478 / 2493
     if (x0 < 0 || x0 + W > Wb) return ASW_ERR_BAD_ARGUMENT;
     ASW_HIP_TRY(hipSetDevice(ctx->device));
-    DevBuf& dref = ctx->buf("stageL");
-    DevBuf& dbord = ctx->buf("stageR");
+    const uint8_t *pref, *pbord;
     DevBuf& gref = ctx->buf("grayL");
     DevBuf& gbord = ctx->buf("sadd_gray_wide");
     DevBuf& gcrop = ctx->buf("grayR");
     DevBuf& raw = ctx->buf("g_raw");
-    ASW_TRY(upload_image(ctx, ref, dref));
-    ASW_TRY(upload_image(ctx, bord, dbord));
+    ASW_TRY(upload_stage_pair(ctx, ref, bord, &pref, &pbord));
     ASW_TRY(gref.ensure((size_t)H * W));
     ASW_TRY(gbord.ensure((size_t)H * Wb));
     ASW_TRY(gcrop.ensure((size_t)H * W));
     ASW_TRY(raw.ensure((size_t)H * W * 4));
-    const uint8_t* pref = dref.as<uint8_t>();
-    const uint8_t* pbord = dbord.as<uint8_t>();
     if (ref->channels == 3) {  // M.cpp:2446-2456
         ASW_TRY(launch_bgr2gray(ctx->stream, pref, H, W, gref.as<uint8_t>(), ctx->gray_bits));
         pref = gref.as<uint8_t>();
@@ -332,9 +304,7 @@ extern "C" int asw_cost_sad_d(asw_ctx* ctx, const asw_image* left, const asw_ima
     // the ROI of the bordered view as a dense plane; then |ref - roi| -> f32 -> boxFilter mean is launch_cost_sad at offset 0
     ASW_HIP_TRY(hipMemcpy2DAsync(gcrop.p, (size_t)W, pbord + x0, (size_t)Wb, (size_t)W, H, hipMemcpyDeviceToDevice, ctx->stream));
     ASW_TRY(launch_cost_sad(ctx->stream, pref, gcrop.as<uint8_t>(), H, W, ASW_DISPARITY_LEFT, win_size, 0, 1, raw.as<float>()));
-    ASW_HIP_TRY(hipMemcpyAsync(cost, raw.p, (size_t)H * W * 4, hipMemcpyDeviceToHost, ctx->stream));
-    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return ASW_OK;
+    return download_sync(ctx, cost, raw.p, (size_t)H * W * 4);
 }
 
 extern "C" int asw_cost_ncc(asw_ctx* ctx, const asw_image* left, const asw_image* right, float* cost, int disparity_type,
@@ -349,14 +319,11 @@ extern "C" int asw_cost_ncc(asw_ctx* ctx, const asw_image* left, const asw_image
     ASW_HIP_TRY(hipSetDevice(ctx->device));
     const int H = left->rows, W = left->cols, n = num_disparity;
     const size_t plane = (size_t)H * W;
-    DevBuf& dl = ctx->buf("stageL");
-    DevBuf& dr = ctx->buf("stageR");
+    const uint8_t *dl, *dr;
     DevBuf& raw = ctx->buf("g_raw");
-    ASW_TRY(upload_image(ctx, left, dl));
-    ASW_TRY(upload_image(ctx, right, dr));
+    ASW_TRY(upload_stage_pair(ctx, left, right, &dl, &dr));
     ASW_TRY(raw.ensure(plane * n * 4));
-    ASW_TRY(run_ncc_cost(ctx, dl.as<uint8_t>(), dr.as<uint8_t>(), H, W, disparity_type, win_size, min_disparity, n, raw.as<float>(),
-                         nullptr, 0, left->channels));
+    ASW_TRY(run_ncc_cost(ctx, dl, dr, H, W, disparity_type, win_size, min_disparity, n, raw.as<float>(), nullptr, 0, left->channels));
     if (normalized) {  // normalize(curCost_, curCost_norm, 0, 1, NORM_MINMAX), M.cpp:981-983
         DevBuf& ord = ctx->buf("g_ord");
         DevBuf& psc = ctx->buf("g_pscales");
@@ -365,25 +332,22 @@ extern "C" int asw_cost_ncc(asw_ctx* ctx, const asw_image* left, const asw_image
         ASW_TRY(launch_slice_scales(ctx->stream, raw.as<float>(), n, plane, ord.as<uint32_t>(), psc.as<float2>()));
         ASW_TRY(launch_apply_scales(ctx->stream, raw.as<float>(), n, plane, psc.as<float2>()));
     }
-    ASW_HIP_TRY(hipMemcpyAsync(cost, raw.p, plane * n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return ASW_OK;
+    return download_sync(ctx, cost, raw.p, plane * n * 4);
 }
 
 extern "C" int asw_ncc_disparity(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp, int disparity_type,
                                  int win_size, int min_disparity, int num_disparity)
 {
-    MatchParams mp;
-    mp.disparity_type = disparity_type; mp.win = win_size; mp.minD = min_disparity; mp.numD = num_disparity;
-    return match_host(ctx, left, right, disp, ASW_ALG_NCC, mp, nullptr, 0);
+    return match_host(ctx, left, right, disp, ASW_ALG_NCC, match_params(disparity_type, win_size, min_disparity, num_disparity), nullptr,
+                      0);
 }
 
 extern "C" int asw_aggregate_guided3(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp,
                                      int disparity_type, double eps, int win_size, int min_disparity, int num_disparity,
                                      float* cost_volume_out, size_t cost_volume_floats)
 {
-    MatchParams mp;
-    mp.disparity_type = disparity_type; mp.win = win_size; mp.minD = min_disparity; mp.numD = num_disparity; mp.eps = eps;
+    MatchParams mp = match_params(disparity_type, win_size, min_disparity, num_disparity);
+    mp.eps = eps;
     return match_host(ctx, left, right, disp, ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER_3, mp, cost_volume_out, cost_volume_floats);
 }
 
@@ -432,18 +396,15 @@ extern "C" int asw_guided_filter(asw_ctx* ctx, const asw_image* guide, const flo
     a.ab_floats = ab_floats; a.fused = 0;
     a.tune = &ctx->tune;
     ASW_TRY(launch_guided(ctx->stream, a));
-    ASW_HIP_TRY(hipMemcpyAsync(q, qv.p, plane * 4, hipMemcpyDeviceToHost, ctx->stream));
-    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return ASW_OK;
+    return download_sync(ctx, q, qv.p, plane * 4);
 }
 
 extern "C" int asw_aggregate_geodesic(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp,
                                       int disparity_type, int win_size, int min_disparity, int num_disparity,
                                       float* cost_volume_out, size_t cost_volume_floats)
 {
-    MatchParams mp;
-    mp.disparity_type = disparity_type; mp.win = win_size; mp.minD = min_disparity; mp.numD = num_disparity;
-    return match_host(ctx, left, right, disp, ASW_ALG_ADAPTIVE_WEIGHT_GEODESIC, mp, cost_volume_out, cost_volume_floats);
+    return match_host(ctx, left, right, disp, ASW_ALG_ADAPTIVE_WEIGHT_GEODESIC,
+                      match_params(disparity_type, win_size, min_disparity, num_disparity), cost_volume_out, cost_volume_floats);
 }
 
 extern "C" int asw_geodesic_dist(asw_ctx* ctx, const asw_image* img, float* out, int win_size, int iter_time)
@@ -467,17 +428,14 @@ extern "C" int asw_geodesic_dist(asw_ctx* ctx, const asw_image* img, float* out,
     ASW_TRY(launch_pack_bgrx(ctx->stream, di.as<uint8_t>(), H, W, px.as<uint32_t>()));
     ASW_TRY(launch_geodesic_weights_f32(ctx->stream, px.as<uint32_t>(), H, W, win_size, iter_time, pf.as<float>()));
     ASW_TRY(launch_planes_to_windows(ctx->stream, pf.as<float>(), H, W, cells, wo.as<float>()));
-    ASW_HIP_TRY(hipMemcpyAsync(out, wo.p, plane * cells * 4, hipMemcpyDeviceToHost, ctx->stream));
-    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return ASW_OK;
+    return download_sync(ctx, out, wo.p, plane * cells * 4);
 }
 
 extern "C" int asw_aggregate_blo1(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp,
                                   int disparity_type, double sample_rate_r, int win_size, int min_disparity,
                                   int num_disparity, float* cost_volume_out, size_t cost_volume_floats)
 {
-    MatchParams mp;
-    mp.disparity_type = disparity_type; mp.win = win_size; mp.minD = min_disparity; mp.numD = num_disparity;
+    MatchParams mp = match_params(disparity_type, win_size, min_disparity, num_disparity);
     mp.blo_rate_r = sample_rate_r;
     return match_host(ctx, left, right, disp, ASW_ALG_ADAPTIVE_WEIGHT_BLO1, mp, cost_volume_out, cost_volume_floats);
 }
@@ -486,8 +444,7 @@ extern "C" int asw_aggregate_bilgrid(asw_ctx* ctx, const asw_image* left, const 
                                      int disparity_type, double sample_rate_s, double sample_rate_r, int min_disparity,
                                      int num_disparity, float* cost_volume_out, size_t cost_volume_floats)
 {
-    MatchParams mp;
-    mp.disparity_type = disparity_type; mp.win = 1; mp.minD = min_disparity; mp.numD = num_disparity;
+    MatchParams mp = match_params(disparity_type, 1, min_disparity, num_disparity);
     mp.grid_rate_s = sample_rate_s; mp.grid_rate_r = sample_rate_r;
     return match_host(ctx, left, right, disp, ASW_ALG_ADAPTIVE_WEIGHT_BILATERAL_GRID, mp, cost_volume_out, cost_volume_floats);
 }
@@ -496,8 +453,7 @@ extern "C" int asw_aggregate_wmedian(asw_ctx* ctx, const asw_image* left, const 
                                      int disparity_type, int win_size, double rate_s, double rate_r, int min_disparity,
                                      int num_disparity, float* cost_volume_out, size_t cost_volume_floats)
 {
-    MatchParams mp;
-    mp.disparity_type = disparity_type; mp.win = win_size; mp.minD = min_disparity; mp.numD = num_disparity;
+    MatchParams mp = match_params(disparity_type, win_size, min_disparity, num_disparity);
     mp.rate_s = rate_s; mp.rate_r = rate_r;
     return match_host(ctx, left, right, disp, ASW_ALG_ADAPTIVE_WEIGHT_MEDIAN, mp, cost_volume_out, cost_volume_floats);
 }
@@ -564,17 +520,40 @@ static int check_s16_image(const asw_image* im)
     return ASW_OK;
 }
 
-// events around a host-buffer call that does not go through run_method
-static int timed_finish(asw_ctx* ctx)
+// The staged-pair + disp16 path of asw_sgbm, asw_stereo_bm and asw_get_disparity_bm, around each one's own checks and launches.
+// disp16_stage: the caller's volume buffer checked against numD planes, the pair into the context's private frame, the volume scratch
+// `vol_name` sized (*vol_dev; null when no volume is asked for), the clock started.
+static int disp16_stage(asw_ctx* ctx, const asw_image* left, const asw_image* right, int numD, const char* vol_name,
+                        const float* cost_volume_out, size_t cost_volume_floats, Frame** frame, float** vol_dev)
 {
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
+    const size_t vol_floats = (size_t)left->rows * left->cols * (size_t)numD;
+    if (cost_volume_out && cost_volume_floats < vol_floats) return ASW_ERR_BAD_ARGUMENT;
+    Frame* f = &ctx->host_frame;
+    ASW_TRY(upload_pair_into(ctx, f, left, right));
+    f->invalidate_results();
+    *vol_dev = nullptr;
+    if (cost_volume_out) {
+        DevBuf& vol = ctx->buf(vol_name);
+        ASW_TRY(vol.ensure(vol_floats * sizeof(float)));
+        *vol_dev = vol.as<float>();
+    }
+    *frame = f;
+    ASW_HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
+    return ASW_OK;
+}
+
+// disp16_finish: the clock stopped, the device map (elements of `elem` bytes) into the caller's pitched map, the volume into its buffer
+static int disp16_finish(asw_ctx* ctx, int launches, asw_image* map, const void* map_dev, size_t elem, float* cost_volume_out,
+                         const float* vol_dev, int numD)
+{
+    ASW_TRY(timed_finish(ctx));
+    ctx->timing.aggregate_launches = launches;
+    const size_t row = (size_t)map->cols * elem;
+    ASW_HIP_TRY(copy_rows(ctx, map->data, map->step, map_dev, row, row, map->rows, hipMemcpyDeviceToHost));
+    if (cost_volume_out)
+        ASW_HIP_TRY(hipMemcpyAsync(cost_volume_out, vol_dev, (size_t)map->rows * map->cols * numD * sizeof(float), hipMemcpyDeviceToHost,
+                                   ctx->stream));
     ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    float t = 0;
-    ASW_HIP_TRY(hipEventElapsedTime(&t, ctx->ev[0], ctx->ev[1]));
-    ctx->timing.total_ms = t;
-    ASW_HIP_TRY(hipEventElapsedTime(&t, ctx->ev[2], ctx->ev[3]));
-    ctx->timing.aggregate_ms = t;
-    ctx->timing.cost_ms = ctx->timing.total_ms - ctx->timing.aggregate_ms;
     return ASW_OK;
 }
 
@@ -597,28 +576,15 @@ static int sgbm_host(asw_ctx* ctx, const asw_image* left, const asw_image* right
     ASW_HIP_TRY(hipSetDevice(ctx->device));
     SgbmLaunch a;
     ASW_TRY(sgbm_prepare(ctx, p, H, W, left->channels, cost_volume_out != nullptr, &a));
-    const size_t plane = (size_t)H * W, vol_floats = plane * (size_t)num_disparities;
-    if (cost_volume_out && cost_volume_floats < vol_floats) return ASW_ERR_BAD_ARGUMENT;
-    Frame* f = &ctx->host_frame;
-    ASW_TRY(upload_pair_into(ctx, f, left, right));
-    f->invalidate_results();
-    DevBuf& vol = ctx->buf("sgbm_volume");
-    if (cost_volume_out) ASW_TRY(vol.ensure(vol_floats * sizeof(float)));
+    Frame* f;
+    ASW_TRY(disp16_stage(ctx, left, right, num_disparities, "sgbm_volume", cost_volume_out, cost_volume_floats, &f, &a.vol));
     a.L = f->L.as<uint8_t>(); a.R = f->R.as<uint8_t>();
-    a.vol = cost_volume_out ? vol.as<float>() : nullptr;
     a.ev_agg0 = ctx->ev[2]; a.ev_agg1 = ctx->ev[3];
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
     ASW_TRY(launch_sgbm(ctx->stream, a));
-    ASW_TRY(timed_finish(ctx));
     // k_sgbm_top, k_sgbm_row + one k_sgbm_line per line geometry in use (columns, diagonals, anti-diagonals)
-    ctx->timing.aggregate_launches = 2 + !!(paths & ASW_SGBM_PATH_BT) + !!(paths & (ASW_SGBM_PATH_TLBR | ASW_SGBM_PATH_BRTL)) +
-                                     !!(paths & (ASW_SGBM_PATH_TRBL | ASW_SGBM_PATH_BLTR));
-    ASW_HIP_TRY(copy_rows(ctx, disp16->data, disp16->step, a.disp16, (size_t)W * sizeof(short), (size_t)W * sizeof(short), H,
-                          hipMemcpyDeviceToHost));
-    if (cost_volume_out)
-        ASW_HIP_TRY(hipMemcpyAsync(cost_volume_out, vol.p, vol_floats * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return ASW_OK;
+    const int launches = 2 + !!(paths & ASW_SGBM_PATH_BT) + !!(paths & (ASW_SGBM_PATH_TLBR | ASW_SGBM_PATH_BRTL)) +
+                         !!(paths & (ASW_SGBM_PATH_TRBL | ASW_SGBM_PATH_BLTR));
+    return disp16_finish(ctx, launches, disp16, a.disp16, sizeof(short), cost_volume_out, a.vol, num_disparities);
 }
 
 extern "C" int asw_sgbm(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp16, int min_disparity,
@@ -662,15 +628,6 @@ extern "C" int asw_filter_speckles(asw_ctx* ctx, asw_image* img, int new_val, in
 }
 
 // ---- block matching (StereoBM::compute with PREFILTER_XSOBEL) and the reference's getDisparity_BM ----
-static int bm_run_host(asw_ctx* ctx, BmLaunch& a, const uint8_t* dL, const uint8_t* dR, float* vol_dev)
-{
-    a.L = dL; a.R = dR;
-    a.vol = vol_dev;
-    a.ev_agg0 = ctx->ev[2]; a.ev_agg1 = ctx->ev[3];
-    ASW_TRY(launch_bm(ctx->stream, a));
-    return ASW_OK;
-}
-
 extern "C" int asw_stereo_bm(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp16, int min_disparity,
                              int num_disparities, int block_size, int pre_filter_type, int pre_filter_size, int pre_filter_cap,
                              int texture_threshold, int uniqueness_ratio, int speckle_window_size, int speckle_range,
@@ -690,23 +647,12 @@ extern "C" int asw_stereo_bm(asw_ctx* ctx, const asw_image* left, const asw_imag
     ASW_HIP_TRY(hipSetDevice(ctx->device));
     BmLaunch a;
     ASW_TRY(bm_prepare(ctx, p, H, W, &a));
-    const size_t plane = (size_t)H * W, vol_floats = plane * (size_t)num_disparities;
-    if (cost_volume_out && cost_volume_floats < vol_floats) return ASW_ERR_BAD_ARGUMENT;
-    Frame* f = &ctx->host_frame;
-    ASW_TRY(upload_pair_into(ctx, f, left, right));
-    f->invalidate_results();
-    DevBuf& vol = ctx->buf("bm_volume");
-    if (cost_volume_out) ASW_TRY(vol.ensure(vol_floats * sizeof(float)));
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
-    ASW_TRY(bm_run_host(ctx, a, f->L.as<uint8_t>(), f->R.as<uint8_t>(), cost_volume_out ? vol.as<float>() : nullptr));
-    ASW_TRY(timed_finish(ctx));
-    ctx->timing.aggregate_launches = 1;
-    ASW_HIP_TRY(copy_rows(ctx, disp16->data, disp16->step, a.disp16, (size_t)W * sizeof(short), (size_t)W * sizeof(short), H,
-                          hipMemcpyDeviceToHost));
-    if (cost_volume_out)
-        ASW_HIP_TRY(hipMemcpyAsync(cost_volume_out, vol.p, vol_floats * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return ASW_OK;
+    Frame* f;
+    ASW_TRY(disp16_stage(ctx, left, right, num_disparities, "bm_volume", cost_volume_out, cost_volume_floats, &f, &a.vol));
+    a.L = f->L.as<uint8_t>(); a.R = f->R.as<uint8_t>();
+    a.ev_agg0 = ctx->ev[2]; a.ev_agg1 = ctx->ev[3];
+    ASW_TRY(launch_bm(ctx->stream, a));
+    return disp16_finish(ctx, 1, disp16, a.disp16, sizeof(short), cost_volume_out, a.vol, num_disparities);
 }
 
 // getDisparity_BM (aswMethods.cpp:100-146): the CV_Error cases (numDisparity % 16 != 0, an even winSize, an empty image, and
@@ -736,29 +682,13 @@ extern "C" int asw_get_disparity_bm(asw_ctx* ctx, const asw_image* left, const a
     BmLaunch a;
     ASW_TRY(bm_prepare(ctx, p, H, W, &a));
     const size_t plane = (size_t)H * W;
-    Frame* f = &ctx->host_frame;
-    ASW_TRY(upload_pair_into(ctx, f, left, right));
-    f->invalidate_results();
     DevBuf& u8 = ctx->buf("bm_u8");
     ASW_TRY(u8.ensure(plane));
-    const uint8_t* dL = f->L.as<uint8_t>();
-    const uint8_t* dR = f->R.as<uint8_t>();
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
-    if (cn == 3) {
-        DevBuf& gl = ctx->buf("grayL");
-        DevBuf& gr = ctx->buf("grayR");
-        ASW_TRY(gl.ensure(plane));
-        ASW_TRY(gr.ensure(plane));
-        ASW_TRY(launch_bgr2gray(ctx->stream, dL, H, W, gl.as<uint8_t>(), ctx->gray_bits));
-        ASW_TRY(launch_bgr2gray(ctx->stream, dR, H, W, gr.as<uint8_t>(), ctx->gray_bits));
-        dL = gl.as<uint8_t>();
-        dR = gr.as<uint8_t>();
-    }
-    ASW_TRY(bm_run_host(ctx, a, dL, dR, nullptr));
+    Frame* f;
+    ASW_TRY(disp16_stage(ctx, left, right, num_disparities, nullptr, nullptr, 0, &f, &a.vol));
+    ASW_TRY(gray_pair(ctx, f->L.as<uint8_t>(), f->R.as<uint8_t>(), cn, H, W, &a.L, &a.R));
+    a.ev_agg0 = ctx->ev[2]; a.ev_agg1 = ctx->ev[3];
+    ASW_TRY(launch_bm(ctx->stream, a));
     ASW_TRY(launch_disp16_to_u8(ctx->stream, a.disp16, plane, u8.as<uint8_t>()));
-    ASW_TRY(timed_finish(ctx));
-    ctx->timing.aggregate_launches = 1;
-    ASW_HIP_TRY(copy_rows(ctx, disp_u8->data, disp_u8->step, u8.p, (size_t)W, (size_t)W, H, hipMemcpyDeviceToHost));
-    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return ASW_OK;
+    return disp16_finish(ctx, 1, disp_u8, u8.p, 1, nullptr, nullptr, 0);
 }

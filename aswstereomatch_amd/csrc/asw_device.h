@@ -1,4 +1,4 @@
-// Device-side helpers shared by the kernels: OpenCV border index maps.
+// Device-side helpers shared by the kernels: OpenCV border index maps, the wavefront minimum.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,4 +16,12 @@ __device__ __forceinline__ int reflect101_idx(int p, int len)
     if (len == 1) return 0;
     while ((unsigned)p >= (unsigned)len) p = p < 0 ? -p : 2 * len - 2 - p;
     return p;
+}
+
+// minimum over the 64 lanes of a wavefront, in every lane
+__device__ __forceinline__ int wave_min(int v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
+    return v;
 }

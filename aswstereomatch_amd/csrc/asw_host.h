@@ -1,8 +1,10 @@
 // Host-side pieces shared by the three translation units behind the C-ABI:
 //   asw_context.hip  context, frame slots, host <-> HBM plumbing, pre/post-processing entry points
-//   asw_methods.hip  the method runners (tables, scratch, launch sequences) and the selector
+//   asw_methods.hip  the method table, the method runners (tables, scratch, launch sequences) and the selector
 //   asw_api.hip      the per-method / cost-builder / building-block entry points of include/asw_mi355x.h
 #pragma once
+#include <type_traits>
+
 #include "asw_internal.h"
 
 #define ASW_TRY(expr)                  \
@@ -10,6 +12,22 @@
         int _rc = (expr);              \
         if (_rc != ASW_OK) return _rc; \
     } while (0)
+
+inline unsigned blocks(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
+
+// Kernels that keep D candidates in the lanes of one wavefront (k = c * 64 + lane) are templates on the candidates per lane:
+// f(std::integral_constant<int, NPL>) with the smallest NPL of 1, 2, 4, 8, 16 that holds D; ASW_ERR_BAD_ARGUMENT beyond 1024
+template <typename F>
+int dispatch_npl(int D, F&& f)
+{
+    const int npl = (D + 63) / 64;
+    if (npl <= 1) return f(std::integral_constant<int, 1>());
+    if (npl <= 2) return f(std::integral_constant<int, 2>());
+    if (npl <= 4) return f(std::integral_constant<int, 4>());
+    if (npl <= 8) return f(std::integral_constant<int, 8>());
+    if (npl <= 16) return f(std::integral_constant<int, 16>());
+    return ASW_ERR_BAD_ARGUMENT;
+}
 
 struct MatchParams {
     int disparity_type, win, minD, numD;  // disparity_type as the caller passed it; run_method strips the sub-pixel flag into `subpixel`
@@ -21,6 +39,28 @@ struct MatchParams {
     double grid_rate_s = 10, grid_rate_r = 10;  // M.cpp:67
     int cross_tau = 20, cross_trunc = 20;       // ASW_ALG_ADAPTIVE_WEIGHT_CROSS; an encoded selector value replaces them
 };
+inline MatchParams match_params(int disparity_type, int win, int minD, int numD)
+{
+    MatchParams mp;
+    mp.disparity_type = disparity_type; mp.win = win; mp.minD = minD; mp.numD = numD;
+    return mp;
+}
+
+// One row per selector value (asw_methods.hip: k_methods).  Everything the host layer knows about a method beyond its runner is a
+// field here: asw_volume_planes, run_method, match_host, the sub-pixel decoding and match_refined read the row, the runners of the
+// inclusive ranges take their candidate count from it.
+struct MethodInfo {
+    int algorithm;     // the ASW_ALG_* value == the row's index
+    int extra_planes;  // candidates / volume planes = numD + extra_planes: 1 where the reference's range is inclusive (offset <= max_offset)
+    int (*run)(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_volume);  // null: the selector does not serve the value
+    bool no_volume;               // no selector volume (0 planes), hence no sub-pixel step and no refinement either
+    bool ignores_disparity_type;  // whatever disparity_type holds, sub-pixel flags included, is not looked at
+    bool no_subpixel;             // a sub-pixel flag is refused with ASW_ERR_UNSUPPORTED_METHOD
+    bool packed_params;           // the selector value may carry the method's parameters (ASW_ALG_CROSS_PARAMS, asw_alg_cross())
+    int planes(int numD) const { return no_volume ? 0 : numD + extra_planes; }
+};
+const MethodInfo* method_info(int method);  // the row of a plain (decoded) selector value; null for a value outside the table
+
 // The selector's `algorithm` as a caller passes it -> the plain enum value in *method and, for an asw_alg_cross() value, its
 // parameters in *tau / *trunc (left alone otherwise; either may be null).  ASW_ERR_UNSUPPORTED_METHOD / ASW_ERR_BAD_ARGUMENT for the
 // encodings asw_mi355x.h refuses; a value without ASW_ALG_CROSS_PARAMS passes through as it is.
@@ -37,6 +77,10 @@ Frame* frame_slot(asw_ctx* ctx, int slot, bool create);
 int upload_pair_into(asw_ctx* ctx, Frame* f, const asw_image* left, const asw_image* right);
 int download_disparity_from(asw_ctx* ctx, Frame* f, asw_image* disp);
 int download_volume_from(asw_ctx* ctx, Frame* f, float* out, size_t n_floats);
+// 3 channels: cvtColor(BGR2GRAY) of both images into the scratch planes "grayL" / "grayR"; 1 channel: the images as they are
+int gray_pair(asw_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int channels, int H, int W, const uint8_t** gl, const uint8_t** gr);
+// records ev[1], waits for the stream and fills ctx->timing's three times from ev[0..3]
+int timed_finish(asw_ctx* ctx);
 int build_similarity_volume(asw_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int H, int W, int minD, int numD,
                                    double regularity, double thresC, double thresG, float* cost,
                                    uint32_t* ord_scratch = nullptr, float2* scales = nullptr);

@@ -322,7 +322,10 @@ size_t sgbm_scratch_bytes(int H, int W, int cn, int minD, int D);
 int launch_sgbm(hipStream_t s, const SgbmLaunch& a);
 int launch_filter_speckles(hipStream_t s, short* img, int H, int W, int new_val, int max_size, int max_diff,
                            int* scratch /* 2 * H * W ints */);
+int launch_fill_s16(hipStream_t s, short* out, size_t n, short v);
+// convertTo(CV_8U, 1/16) of a disp16 map: as f32 (the selector's CV_32F result) and as u8 (getDisparity_BM)
 int launch_disp16_to_u8f(hipStream_t s, const short* disp16, size_t n, float* out);
+int launch_disp16_to_u8(hipStream_t s, const short* disp16, size_t n, uint8_t* out);
 
 // ---- block matching (k_bm.hip): StereoBM PREFILTER_XSOBEL + validateDisparity + filterSpeckles, DESIGN.md section 4.9 ----
 struct BmLaunch {
@@ -339,4 +342,3 @@ struct BmLaunch {
 };
 size_t bm_scratch_bytes(int H, int W);
 int launch_bm(hipStream_t s, const BmLaunch& a);
-int launch_disp16_to_u8(hipStream_t s, const short* disp16, size_t n, uint8_t* out);

@@ -14,6 +14,78 @@
 #include "asw_host.h"
 
 // ------------------------------------------------------------------------------------------
+// pieces every runner is made of
+// ------------------------------------------------------------------------------------------
+static int check_direction(int disparity_type)
+{
+    return disparity_type == ASW_DISPARITY_LEFT || disparity_type == ASW_DISPARITY_RIGHT ? ASW_OK : ASW_ERR_BAD_ARGUMENT;
+}
+
+// the frame's disparity map and, when the caller keeps it (or the method's own WTA pass reads it: volume_needed), its volume of
+// `planes` planes; f->vol_floats = what the caller keeps
+static int ensure_outputs(Frame* f, int planes, bool keep_volume, bool volume_needed = false)
+{
+    const size_t plane = (size_t)f->rows * f->cols;
+    ASW_TRY(f->disp.ensure(plane * 4));
+    f->vol_floats = 0;
+    if (keep_volume || volume_needed) ASW_TRY(f->vol.ensure(plane * planes * 4));
+    if (keep_volume) f->vol_floats = plane * planes;
+    return ASW_OK;
+}
+
+int gray_pair(asw_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int channels, int H, int W, const uint8_t** gl, const uint8_t** gr)
+{
+    *gl = dL; *gr = dR;
+    if (channels != 3) return ASW_OK;
+    DevBuf& l = ctx->buf("grayL");
+    DevBuf& r = ctx->buf("grayR");
+    ASW_TRY(l.ensure((size_t)H * W));
+    ASW_TRY(r.ensure((size_t)H * W));
+    ASW_TRY(launch_bgr2gray(ctx->stream, dL, H, W, l.as<uint8_t>(), ctx->gray_bits));
+    ASW_TRY(launch_bgr2gray(ctx->stream, dR, H, W, r.as<uint8_t>(), ctx->gray_bits));
+    *gl = l.as<uint8_t>(); *gr = r.as<uint8_t>();
+    return ASW_OK;
+}
+
+// per-slice winners of a candidate range split over slices: [slices][plane] costs and disparities
+static int slice_scratch(asw_ctx* ctx, int slices, size_t plane, double** E, float** D)
+{
+    DevBuf& pe = ctx->buf("bil_partE");
+    DevBuf& pd = ctx->buf("bil_partD");
+    ASW_TRY(pe.ensure((size_t)slices * plane * sizeof(double)));
+    ASW_TRY(pd.ensure((size_t)slices * plane * sizeof(float)));
+    *E = pe.as<double>(); *D = pd.as<float>();
+    return ASW_OK;
+}
+
+// the event pair around a method's aggregation kernels (asw_timing::aggregate_ms) and the launch count that goes with it
+static int agg_begin(asw_ctx* ctx)
+{
+    ASW_HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
+    return ASW_OK;
+}
+
+static int agg_end(asw_ctx* ctx, int launches)
+{
+    ASW_HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
+    ctx->timing.aggregate_launches = launches;
+    return ASW_OK;
+}
+
+int timed_finish(asw_ctx* ctx)
+{
+    ASW_HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
+    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    float t = 0;
+    ASW_HIP_TRY(hipEventElapsedTime(&t, ctx->ev[0], ctx->ev[1]));
+    ctx->timing.total_ms = t;
+    ASW_HIP_TRY(hipEventElapsedTime(&t, ctx->ev[2], ctx->ev[3]));
+    ctx->timing.aggregate_ms = t;
+    ctx->timing.cost_ms = ctx->timing.total_ms - ctx->timing.aggregate_ms;
+    return ASW_OK;
+}
+
+// ------------------------------------------------------------------------------------------
 // classic bilateral ASW: host-side tables (tap list with the reference's two index conventions,
 // weight LUT with the reference's expression) -- M.cpp:1044-1066, 1088-1102, SURVEY App. B-2
 // ------------------------------------------------------------------------------------------
@@ -119,35 +191,27 @@ static int ensure_bilateral_tables(asw_ctx* ctx, int kind, int win, double gamma
 // computeAdaptiveWeight (direct8 = false) and computeAdaptiveWeight_direct8 (direct8 = true: sparse support, its own
 // gamma_g, DISPARITY_LEFT only -- the RIGHT branch of the reference indexes its weight vectors with a negative tap
 // coordinate, M.cpp:1291-1295)
-static int run_bilateral(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_volume, bool direct8 = false)
+static int run_bilateral(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_volume, bool direct8)
 {
     if (mp.win % 2 == 0) return ASW_ERR_EVEN_WINDOW;  // build decision: the reference has no guard
     if (mp.win < 1) return ASW_ERR_BAD_ARGUMENT;
     if (f->channels != 3) return ASW_ERR_UNSUPPORTED_LAYOUT;  // cvtColor(BGR2GRAY) asserts scn==3/4
-    if (mp.disparity_type != ASW_DISPARITY_LEFT && mp.disparity_type != ASW_DISPARITY_RIGHT) return ASW_ERR_BAD_ARGUMENT;
+    ASW_TRY(check_direction(mp.disparity_type));
     if (direct8 && mp.disparity_type != ASW_DISPARITY_LEFT) return ASW_ERR_UNSUPPORTED_LAYOUT;
     const int flip = mp.disparity_type == ASW_DISPARITY_RIGHT ? 1 : 0;
     if (mp.win > 127) return ASW_ERR_BAD_ARGUMENT;
-    const int H = f->rows, W = f->cols, nD = mp.numD + 1;  // inclusive range, M.cpp:1021,1074
+    const int H = f->rows, W = f->cols;
+    const int nD = method_info(direct8 ? ASW_ALG_ADAPTIVE_WEIGHT_8DIRECT : ASW_ALG_ADAPTIVE_WEIGHT)->planes(mp.numD);
     if (direct8)
         ASW_TRY(ensure_bilateral_tables(ctx, 1, mp.win, 30.0, (double)(mp.win * 2 / 3), 0));  // M.cpp:1175: integer division
     else
         ASW_TRY(ensure_bilateral_tables(ctx, 0, mp.win, mp.gamma_c, mp.gamma_g, flip));
-    DevBuf& gl = ctx->buf("grayL");
-    DevBuf& gr = ctx->buf("grayR");
-    ASW_TRY(gl.ensure((size_t)H * W));
-    ASW_TRY(gr.ensure((size_t)H * W));
-    ASW_TRY(f->disp.ensure((size_t)H * W * 4));
-    f->vol_floats = 0;
-    if (keep_volume) {
-        ASW_TRY(f->vol.ensure((size_t)nD * H * W * 4));
-        f->vol_floats = (size_t)nD * H * W;
-    }
-    ASW_TRY(launch_bgr2gray(ctx->stream, f->L.as<uint8_t>(), H, W, gl.as<uint8_t>(), ctx->gray_bits));
-    ASW_TRY(launch_bgr2gray(ctx->stream, f->R.as<uint8_t>(), H, W, gr.as<uint8_t>(), ctx->gray_bits));
+    const uint8_t *gl, *gr;
+    ASW_TRY(ensure_outputs(f, nD, keep_volume));
+    ASW_TRY(gray_pair(ctx, f->L.as<uint8_t>(), f->R.as<uint8_t>(), 3, H, W, &gl, &gr));
     BilateralLaunch a;
-    a.gL = flip ? gr.as<uint8_t>() : gl.as<uint8_t>();  // RIGHT: reference image = right, read mirrored in the kernel
-    a.gR = flip ? gl.as<uint8_t>() : gr.as<uint8_t>();
+    a.gL = flip ? gr : gl;  // RIGHT: reference image = right, read mirrored in the kernel
+    a.gR = flip ? gl : gr;
     a.flip = flip;
     a.H = H; a.W = W; a.win = mp.win; a.minD = mp.minD; a.nD = nD;
     a.taps = ctx->bil.taps.as<int4>(); a.lut = ctx->bil.lut.as<float>(); a.ntaps = ctx->bil.ntaps;
@@ -165,16 +229,13 @@ static int run_bilateral(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool kee
     const int xq_waves = nD >= bilateral_xq_candidates(8) ? 8 : 4;
     const bool use_xq = !direct8 && mp.win == 15 && nD >= bilateral_xq_candidates(xq_waves) && mp.minD >= 0 && xq_fits && W >= 64 &&
                         ctx->bil.xq_lut_ok && ctx->tune.bilateral_xq != 0;
+    const size_t plane = (size_t)H * W;
     if (use_xq) {
-        DevBuf& pe = ctx->buf("bil_partE");
-        DevBuf& pd = ctx->buf("bil_partD");
-        const size_t plane = (size_t)H * W;
-        ASW_TRY(pe.ensure(2 * plane * sizeof(double)));
-        ASW_TRY(pd.ensure(2 * plane * sizeof(float)));
-        a.partE = pe.as<double>(); a.partD = pd.as<float>(); a.max_slices = 2;
+        a.max_slices = 2;
+        ASW_TRY(slice_scratch(ctx, a.max_slices, plane, &a.partE, &a.partD));
         a.c_begin = bilateral_xq_candidates(xq_waves);
         const bool tail = nD > a.c_begin;  // numDisparity = 127 / 63 ends exactly at the xq kernel's 128 / 64 candidates
-        ASW_HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
+        ASW_TRY(agg_begin(ctx));
         // fork: border tiles and the tail are independent of the interior launch (they write other pixels / another slice of the
         // per-slice winners); on side streams they overlap it instead of adding two latency-bound 0.5 ms launches to the frame
         ASW_HIP_TRY(hipEventRecord(ctx->aux_ev[0], ctx->stream));
@@ -191,23 +252,25 @@ static int run_bilateral(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool kee
         }
         ASW_HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->aux_ev[1], 0));  // join
         if (tail) ASW_TRY(launch_merge_slices(ctx->stream, a.partE, a.partD, 2, plane, a.disp));  // strict '<', ascending d
-        ASW_HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
-        ctx->timing.aggregate_launches = tail ? 4 : 2;
-        return ASW_OK;
+        return agg_end(ctx, tail ? 4 : 2);
     }
-    if ((size_t)H * W <= (size_t)1 << 20) {  // small frames only: scratch for the grid.z split of the disparity range
-        const int max_slices = 8;
-        DevBuf& pe = ctx->buf("bil_partE");
-        DevBuf& pd = ctx->buf("bil_partD");
-        ASW_TRY(pe.ensure((size_t)max_slices * H * W * sizeof(double)));
-        ASW_TRY(pd.ensure((size_t)max_slices * H * W * sizeof(float)));
-        a.partE = pe.as<double>(); a.partD = pd.as<float>(); a.max_slices = max_slices;
+    if (plane <= (size_t)1 << 20) {  // small frames only: scratch for the grid.z split of the disparity range
+        a.max_slices = 8;
+        ASW_TRY(slice_scratch(ctx, a.max_slices, plane, &a.partE, &a.partD));
     }
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
+    ASW_TRY(agg_begin(ctx));
     ASW_TRY(launch_bilateral(ctx->stream, a));
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
-    ctx->timing.aggregate_launches = 1;
-    return ASW_OK;
+    return agg_end(ctx, 1);
+}
+
+static int run_bilateral_classic(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_volume)
+{
+    return run_bilateral(ctx, f, mp, keep_volume, false);
+}
+
+static int run_direct8(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_volume)
+{
+    return run_bilateral(ctx, f, mp, keep_volume, true);
 }
 
 
@@ -279,29 +342,20 @@ int run_ncc_cost(asw_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int H, int 
 static int run_ncc(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_volume)
 {
     if (f->channels != 3) return ASW_ERR_UNSUPPORTED_LAYOUT;
-    if (mp.disparity_type != ASW_DISPARITY_LEFT && mp.disparity_type != ASW_DISPARITY_RIGHT) return ASW_ERR_BAD_ARGUMENT;
+    ASW_TRY(check_direction(mp.disparity_type));
     if (mp.win % 2 == 0) return ASW_ERR_EVEN_WINDOW;
     const int H = f->rows, W = f->cols;
-    const size_t plane = (size_t)H * W;
-    ASW_TRY(f->disp.ensure(plane * 4));
-    f->vol_floats = 0;
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
-    if (mp.disparity_type == ASW_DISPARITY_RIGHT) {
-        ASW_HIP_TRY(hipMemsetAsync(f->disp.p, 0, plane * 4, ctx->stream));
+    const bool right = mp.disparity_type == ASW_DISPARITY_RIGHT;
+    // LEFT, kept: the raw (un-normalised) costs of all numD offsets, for inspection
+    ASW_TRY(ensure_outputs(f, mp.numD, keep_volume && !right));
+    ASW_TRY(agg_begin(ctx));
+    if (right) {
+        ASW_HIP_TRY(hipMemsetAsync(f->disp.p, 0, (size_t)H * W * 4, ctx->stream));
         if (keep_volume) return ASW_ERR_UNSUPPORTED_LAYOUT;
-    } else {
-        float* vol = nullptr;
-        if (keep_volume) {  // raw (un-normalised) costs of all numD offsets, for inspection
-            ASW_TRY(f->vol.ensure(plane * mp.numD * 4));
-            f->vol_floats = plane * mp.numD;
-            vol = f->vol.as<float>();
-        }
-        ASW_TRY(run_ncc_cost(ctx, f->L.as<uint8_t>(), f->R.as<uint8_t>(), H, W, mp.disparity_type, mp.win, mp.minD, mp.numD, vol,
-                             f->disp.as<float>(), mp.numD - 1));
-    }
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
-    ctx->timing.aggregate_launches = 1;
-    return ASW_OK;
+    } else
+        ASW_TRY(run_ncc_cost(ctx, f->L.as<uint8_t>(), f->R.as<uint8_t>(), H, W, mp.disparity_type, mp.win, mp.minD, mp.numD,
+                             keep_volume ? f->vol.as<float>() : nullptr, f->disp.as<float>(), mp.numD - 1));
+    return agg_end(ctx, 1);
 }
 
 enum GuidedKind { GUIDED_SAD6 = 0 /* GuidedF */, GUIDED_SIM3 = 1 /* GuidedF_2 */, GUIDED_NCC = 2 /* GuidedF_3 */ };
@@ -315,7 +369,7 @@ static int run_guided(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_v
     if (f->channels != 3) return ASW_ERR_UNSUPPORTED_LAYOUT;
     // GuidedF_2: RIGHT / gray branches of computeSimilarity throw in the reference (App. B-7).
     if (variant2 && mp.disparity_type != ASW_DISPARITY_LEFT) return ASW_ERR_UNSUPPORTED_LAYOUT;
-    if (mp.disparity_type != ASW_DISPARITY_LEFT && mp.disparity_type != ASW_DISPARITY_RIGHT) return ASW_ERR_BAD_ARGUMENT;
+    ASW_TRY(check_direction(mp.disparity_type));
     const bool right = mp.disparity_type == ASW_DISPARITY_RIGHT;
     if (!variant2 && mp.win % 2 == 0) return ASW_ERR_EVEN_WINDOW;  // getCostSAD_d, M.cpp:2458-2462; computeNCC, M.cpp:939-942
     if (mp.win < 1 || mp.win > 128) return ASW_ERR_BAD_ARGUMENT;
@@ -344,9 +398,7 @@ static int run_guided(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_v
     ASW_TRY(ab.ensure(ab_floats * 4));
     ASW_TRY(pxa.ensure((plane + 4) * 4));  // + slack: the q pass reads the guide words of a lane's two columns as one pair, the last one may start at column W-1
     ASW_TRY(pxb.ensure((plane + 4) * 4));
-    ASW_TRY(f->vol.ensure(plane * n * 4));  // q volume: always needed for the WTA pass
-    ASW_TRY(f->disp.ensure(plane * 4));
-    f->vol_floats = keep_volume ? plane * n : 0;
+    ASW_TRY(ensure_outputs(f, n, keep_volume, true));  // q volume: always needed for the WTA pass
     const uint8_t* dL = f->L.as<uint8_t>();
     const uint8_t* dR = f->R.as<uint8_t>();
 
@@ -376,16 +428,11 @@ static int run_guided(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_v
                                         psc.as<float2>()));  // M.cpp:2990 (+ the min/max of M.cpp:2775, fused)
         ASW_TRY(launch_u8_scale(ctx->stream, dL, plane * 3, ord.as<uint32_t>() + 2 * n, gsc.as<float2>()));
     } else {
-        DevBuf& gl = ctx->buf("grayL");
-        DevBuf& gr = ctx->buf("grayR");
+        const uint8_t *gl, *gr;
         DevBuf& colmm = ctx->buf("g_colmm");
-        ASW_TRY(gl.ensure(plane));
-        ASW_TRY(gr.ensure(plane));
         ASW_TRY(colmm.ensure((size_t)2 * W * sizeof(int)));
-        ASW_TRY(launch_bgr2gray(ctx->stream, dL, H, W, gl.as<uint8_t>(), ctx->gray_bits));
-        ASW_TRY(launch_bgr2gray(ctx->stream, dR, H, W, gr.as<uint8_t>(), ctx->gray_bits));
-        ASW_TRY(launch_cost_sad(ctx->stream, gl.as<uint8_t>(), gr.as<uint8_t>(), H, W, mp.disparity_type, mp.win, mp.minD, n,
-                                raw.as<float>()));  // M.cpp:2884-2889
+        ASW_TRY(gray_pair(ctx, dL, dR, 3, H, W, &gl, &gr));
+        ASW_TRY(launch_cost_sad(ctx->stream, gl, gr, H, W, mp.disparity_type, mp.win, mp.minD, n, raw.as<float>()));  // M.cpp:2884-2889
         ASW_TRY(launch_guide_scales_lr(ctx->stream, right ? dR : dL, right ? dL : dR, H, W, mp.minD, n, mp.disparity_type,
                                        ord.as<uint32_t>() + 2 * n, colmm.as<int>(), gsc.as<float2>()));
     }
@@ -398,13 +445,15 @@ static int run_guided(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_v
     a.stats = stats.as<float>(); a.rep_scratch = repb.as<int>(); a.ab = ab.as<float>(); a.q = f->vol.as<float>();
     a.ab_floats = ab_floats; a.fused = fused ? 1 : 0;
     a.tune = &ctx->tune;
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
+    ASW_TRY(agg_begin(ctx));
     ASW_TRY(launch_guided(ctx->stream, a));
     ASW_TRY(launch_wta(ctx->stream, f->vol.as<float>(), n, H, W, mp.minD, f->disp.as<float>()));  // M.cpp:3032-3048
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
-    ctx->timing.aggregate_launches = plain3 ? (fused ? 3 : 4) : 5;  // statistics, [a/b, q | fused walk], WTA
-    return ASW_OK;
+    return agg_end(ctx, plain3 ? (fused ? 3 : 4) : 5);  // statistics, [a/b, q | fused walk], WTA
 }
+
+static int run_guided_sad6(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_volume) { return run_guided(ctx, f, mp, keep_volume, GUIDED_SAD6); }
+static int run_guided_sim3(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_volume) { return run_guided(ctx, f, mp, keep_volume, GUIDED_SIM3); }
+static int run_guided_ncc(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_volume) { return run_guided(ctx, f, mp, keep_volume, GUIDED_NCC); }
 
 // ------------------------------------------------------------------------------------------
 // geodesic ASW: computeAdaptiveWeight_geodesic (M.cpp:1436-1534)
@@ -413,10 +462,10 @@ static int run_geodesic(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep
 {
     if (mp.win % 2 == 0) return ASW_ERR_EVEN_WINDOW;  // M.cpp:1440-1443
     if (f->channels != 3) return ASW_ERR_UNSUPPORTED_LAYOUT;  // at<Vec3b>
-    if (mp.disparity_type != ASW_DISPARITY_LEFT && mp.disparity_type != ASW_DISPARITY_RIGHT) return ASW_ERR_BAD_ARGUMENT;
+    ASW_TRY(check_direction(mp.disparity_type));
     const int flip = mp.disparity_type == ASW_DISPARITY_RIGHT ? 1 : 0;  // M.cpp:1498-1520 == LEFT on the mirrored problem
     if (mp.win < 1 || mp.win > 35) return ASW_ERR_BAD_ARGUMENT;
-    const int H = f->rows, W = f->cols, nD = mp.numD + 1;  // inclusive range, M.cpp:1447,1467
+    const int H = f->rows, W = f->cols, nD = method_info(ASW_ALG_ADAPTIVE_WEIGHT_GEODESIC)->planes(mp.numD);
     const size_t plane = (size_t)H * W, cells = (size_t)mp.win * mp.win;
     DevBuf& pl = ctx->buf("bgrxL");
     DevBuf& pr = ctx->buf("bgrxR");
@@ -426,43 +475,29 @@ static int run_geodesic(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep
     ASW_TRY(pr.ensure(plane * 4));
     ASW_TRY(wl.ensure(plane * cells * 2));
     ASW_TRY(wr.ensure(plane * cells * 2));
-    ASW_TRY(f->disp.ensure(plane * 4));
-    f->vol_floats = 0;
-    if (keep_volume) {
-        ASW_TRY(f->vol.ensure(plane * nD * 4));
-        f->vol_floats = plane * nD;
-    }
+    ASW_TRY(ensure_outputs(f, nD, keep_volume));
     ASW_TRY(launch_pack_bgrx(ctx->stream, f->L.as<uint8_t>(), H, W, pl.as<uint32_t>()));
     ASW_TRY(launch_pack_bgrx(ctx->stream, f->R.as<uint8_t>(), H, W, pr.as<uint32_t>()));
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
+    ASW_TRY(agg_begin(ctx));
     ASW_TRY(launch_geodesic_weights_u16(ctx->stream, pl.as<uint32_t>(), H, W, mp.win, 3, wl.as<uint16_t>()));  // M.cpp:1464
     ASW_TRY(launch_geodesic_weights_u16(ctx->stream, pr.as<uint32_t>(), H, W, mp.win, 3, wr.as<uint16_t>()));  // M.cpp:1465
     double* partE = nullptr;
     float* partD = nullptr;
-    if (plane <= (size_t)1 << 20) {  // small frames only: scratch for the grid.z split of the disparity range
-        DevBuf& pe = ctx->buf("bil_partE");
-        DevBuf& pd = ctx->buf("bil_partD");
-        ASW_TRY(pe.ensure((size_t)8 * plane * sizeof(double)));
-        ASW_TRY(pd.ensure((size_t)8 * plane * sizeof(float)));
-        partE = pe.as<double>(); partD = pd.as<float>();
-    }
+    if (plane <= (size_t)1 << 20)  // small frames only: scratch for the grid.z split of the disparity range
+        ASW_TRY(slice_scratch(ctx, 8, plane, &partE, &partD));
+    // fixed image (the one the disparity map belongs to) / other image
+    const uint32_t* pf = flip ? pr.as<uint32_t>() : pl.as<uint32_t>();
+    const uint32_t* po = flip ? pl.as<uint32_t>() : pr.as<uint32_t>();
+    const uint16_t* wf = flip ? wr.as<uint16_t>() : wl.as<uint16_t>();
+    const uint16_t* wo = flip ? wl.as<uint16_t>() : wr.as<uint16_t>();
+    float* vol = keep_volume ? f->vol.as<float>() : nullptr;
     // Long candidate ranges of the 15x15 case (either direction) run as passes of the xq kernel (128 / 64 candidates each) plus
     // k_asw_geodesic for what is left (< 64 candidates); every pass leaves its winners in one slice, merged at the end with
     // the reference's strict '<' in ascending d.  ASW_GEODESIC_XQ=0 forces the one-kernel path.
     if (mp.win == 15 && nD >= geodesic_xq_pass_candidates(4) && W >= 64 && mp.minD >= 0 && ctx->tune.geodesic_xq != 0) {
-        // fixed image (the one the disparity map belongs to) / other image
-        const uint32_t* pf = flip ? pr.as<uint32_t>() : pl.as<uint32_t>();
-        const uint32_t* po = flip ? pl.as<uint32_t>() : pr.as<uint32_t>();
-        const uint16_t* wf = flip ? wr.as<uint16_t>() : wl.as<uint16_t>();
-        const uint16_t* wo = flip ? wl.as<uint16_t>() : wr.as<uint16_t>();
-        const int nslices_max = nD / 64 + 2;
-        DevBuf& pe = ctx->buf("bil_partE");
-        DevBuf& pd = ctx->buf("bil_partD");
-        ASW_TRY(pe.ensure((size_t)nslices_max * plane * sizeof(double)));
-        ASW_TRY(pd.ensure((size_t)nslices_max * plane * sizeof(float)));
-        double* sE = pe.as<double>();
-        float* sD = pd.as<float>();
-        float* vol = keep_volume ? f->vol.as<float>() : nullptr;
+        double* sE;
+        float* sD;
+        ASW_TRY(slice_scratch(ctx, nD / 64 + 2, plane, &sE, &sD));
         ASW_HIP_TRY(hipEventRecord(ctx->aux_ev[0], ctx->stream));  // fork: border tiles and the tail run beside the passes
         ASW_HIP_TRY(hipStreamWaitEvent(ctx->aux[0], ctx->aux_ev[0], 0));
         ASW_HIP_TRY(hipStreamWaitEvent(ctx->aux[1], ctx->aux_ev[0], 0));
@@ -488,17 +523,9 @@ static int run_geodesic(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep
         ASW_HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->aux_ev[1], 0));  // join
         ASW_HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->aux_ev[2], 0));
         ASW_TRY(launch_merge_slices(ctx->stream, sE, sD, ns, plane, f->disp.as<float>()));
-    } else if (!flip)
-        ASW_TRY(launch_asw_geodesic(ctx->stream, pl.as<uint32_t>(), pr.as<uint32_t>(), wl.as<uint16_t>(), wr.as<uint16_t>(), H, W,
-                                    mp.win, mp.minD, nD, 0, keep_volume ? f->vol.as<float>() : nullptr, f->disp.as<float>(),
-                                    partE, partD));
-    else
-        ASW_TRY(launch_asw_geodesic(ctx->stream, pr.as<uint32_t>(), pl.as<uint32_t>(), wr.as<uint16_t>(), wl.as<uint16_t>(), H, W,
-                                    mp.win, mp.minD, nD, 1, keep_volume ? f->vol.as<float>() : nullptr, f->disp.as<float>(),
-                                    partE, partD));
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
-    ctx->timing.aggregate_launches = 3;
-    return ASW_OK;
+    } else
+        ASW_TRY(launch_asw_geodesic(ctx->stream, pf, po, wf, wo, H, W, mp.win, mp.minD, nD, flip, vol, f->disp.as<float>(), partE, partD));
+    return agg_end(ctx, 3);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -556,51 +583,42 @@ static int run_wmedian(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_
     ASW_TRY(raw.ensure(plane * n * 4));
     ASW_TRY(wl.ensure(plane * cells * 4));
     ASW_TRY(wr.ensure((size_t)H * Wb * cells * 4));
-    ASW_TRY(f->vol.ensure(plane * n * 4));
-    ASW_TRY(f->disp.ensure(plane * 4));
-    f->vol_floats = keep_volume ? plane * n : 0;
+    ASW_TRY(ensure_outputs(f, n, keep_volume, true));  // the medians: always needed for the WTA pass
     const uint8_t* dL = f->L.as<uint8_t>();
     const uint8_t* dR = f->R.as<uint8_t>();
     ASW_TRY(build_similarity_volume(ctx, dL, dR, H, W, mp.minD, n, 0.4, 10, 50, raw.as<float>()));  // M.cpp:3250
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
+    ASW_TRY(agg_begin(ctx));
     ASW_TRY(launch_wm_weights(ctx->stream, dL, H, W, 0, mp.win, ctx->wm_lut2.as<float>(), ctx->wm_wd.as<float>(), wl.as<float>()));
     ASW_TRY(launch_wm_weights(ctx->stream, dR, H, W, max_off, mp.win, ctx->wm_lut2.as<float>(), nullptr, wr.as<float>()));
     // 15x15 (the reference's call site): the neighbourhood of an 8x8 pixel block is sorted once per slice and every pixel walks
-    // it (k_wmedian_tile.hip); every other window up to 37x37 likewise (below); 1x1 and 39x39 .. 45x45 sort per pixel (k_wmedian.hip).  Slices go in chunks that keep the sorted lists
-    // (3 KB per block and slice) below 2 GiB.  ASW_WMEDIAN_TILE=0 forces the per-pixel sort (A/B measurements, tests).
-    if (mp.win == 15 && ctx->tune.wmedian_tile != 0) {
-        const size_t per_slice = wmedian_tile_list_slots(H, W, 1);
+    // it (k_wmedian_tile.hip), 3 KB of list per block and slice; 3x3 .. 13x13, 17x17 .. 37x37: the same scheme with the window a
+    // run-time parameter (k_wmedian_tile_gen.hip), 1.5 .. 12 KB; 1x1 and 39x39 .. 45x45 sort per pixel (k_wmedian.hip).  Slices go in
+    // chunks that keep the sorted lists below 2 GiB.  ASW_WMEDIAN_TILE=0 forces the per-pixel sort (A/B measurements, tests).
+    const bool tile15 = mp.win == 15;
+    if ((tile15 || wmedian_tile_gen_supported(mp.win)) && ctx->tune.wmedian_tile != 0) {
+        size_t per_slice = wmedian_tile_list_slots(H, W, 1);
+        if (!tile15) per_slice = per_slice / 512 * (size_t)wmedian_tile_gen_slots(mp.win);
         int chunk = (int)std::min<size_t>((size_t)n, std::max<size_t>(8, (((size_t)2 << 30) / 6 / per_slice) / 8 * 8));
         if (ctx->tune.wmedian_tile_chunk > 0) chunk = std::max(1, std::min(n, ctx->tune.wmedian_tile_chunk));  // tests: odd chunkings
         DevBuf& lc = ctx->buf("wmListC");
         DevBuf& lp = ctx->buf("wmListP");
         ASW_TRY(lc.ensure(per_slice * chunk * 4));
         ASW_TRY(lp.ensure(per_slice * chunk * 2));
-        for (int d0 = 0; d0 < n; d0 += chunk)
-            ASW_TRY(launch_wmedian_tile(ctx->stream, raw.as<float>(), wl.as<float>(), wr.as<float>(), H, W, n, max_off, d0,
-                                        std::min(chunk, n - d0), lc.as<uint32_t>(), lp.as<uint16_t>(), f->vol.as<float>(),
-                                        ctx->tune.wmedian_tile_split));
-    } else if (wmedian_tile_gen_supported(mp.win) && ctx->tune.wmedian_tile != 0) {
-        // 3x3 .. 13x13, 17x17 .. 37x37: the same scheme with the window a run-time parameter (k_wmedian_tile_gen.hip), 1.5 .. 12 KB of list per
-        // block and slice
-        const size_t per_slice = wmedian_tile_list_slots(H, W, 1) / 512 * (size_t)wmedian_tile_gen_slots(mp.win);
-        int chunk = (int)std::min<size_t>((size_t)n, std::max<size_t>(8, (((size_t)2 << 30) / 6 / per_slice) / 8 * 8));
-        if (ctx->tune.wmedian_tile_chunk > 0) chunk = std::max(1, std::min(n, ctx->tune.wmedian_tile_chunk));
-        DevBuf& lc = ctx->buf("wmListC");
-        DevBuf& lp = ctx->buf("wmListP");
-        ASW_TRY(lc.ensure(per_slice * chunk * 4));
-        ASW_TRY(lp.ensure(per_slice * chunk * 2));
-        for (int d0 = 0; d0 < n; d0 += chunk)
-            ASW_TRY(launch_wmedian_tile_gen(ctx->stream, raw.as<float>(), wl.as<float>(), wr.as<float>(), H, W, mp.win, n, max_off, d0,
-                                            std::min(chunk, n - d0), lc.as<uint32_t>(), lp.as<uint16_t>(), f->vol.as<float>(),
-                                            ctx->tune.wmedian_gen_rows));
+        for (int d0 = 0; d0 < n; d0 += chunk) {
+            const int dn = std::min(chunk, n - d0);
+            if (tile15)
+                ASW_TRY(launch_wmedian_tile(ctx->stream, raw.as<float>(), wl.as<float>(), wr.as<float>(), H, W, n, max_off, d0, dn,
+                                            lc.as<uint32_t>(), lp.as<uint16_t>(), f->vol.as<float>(), ctx->tune.wmedian_tile_split));
+            else
+                ASW_TRY(launch_wmedian_tile_gen(ctx->stream, raw.as<float>(), wl.as<float>(), wr.as<float>(), H, W, mp.win, n, max_off,
+                                                d0, dn, lc.as<uint32_t>(), lp.as<uint16_t>(), f->vol.as<float>(),
+                                                ctx->tune.wmedian_gen_rows));
+        }
     } else
         ASW_TRY(launch_wmedian(ctx->stream, raw.as<float>(), wl.as<float>(), wr.as<float>(), H, W, mp.win, n, max_off,
                                f->vol.as<float>()));
     ASW_TRY(launch_wta(ctx->stream, f->vol.as<float>(), n, H, W, mp.minD, f->disp.as<float>()));  // M.cpp:3365-3381
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
-    ctx->timing.aggregate_launches = 4;
-    return ASW_OK;
+    return agg_end(ctx, 4);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -610,7 +628,7 @@ static int run_blo1(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_vol
 {
     if (mp.win % 2 == 0) return ASW_ERR_EVEN_WINDOW;  // getCostSAD_d -> Mat(), M.cpp:2458-2462
     if (f->channels != 3 && f->channels != 1) return ASW_ERR_UNSUPPORTED_LAYOUT;
-    if (mp.disparity_type != ASW_DISPARITY_LEFT && mp.disparity_type != ASW_DISPARITY_RIGHT) return ASW_ERR_BAD_ARGUMENT;
+    ASW_TRY(check_direction(mp.disparity_type));
     // the reference indexes setsJB_ks_ds_x[key][offset] with the ABSOLUTE offset (M.cpp:2659): out of range unless 0
     if (mp.minD != 0) return ASW_ERR_BAD_ARGUMENT;
     if (mp.win < 1 || mp.win > 64) return ASW_ERR_BAD_ARGUMENT;
@@ -619,33 +637,16 @@ static int run_blo1(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_vol
     const int H = f->rows, W = f->cols, n = mp.numD;
     const size_t plane = (size_t)H * W;
     // keys 0, step, 2*step, ..., 255 (M.cpp:2551-2560) are implied by `step` in the kernel
-    DevBuf& gl = ctx->buf("grayL");
-    DevBuf& gr = ctx->buf("grayR");
+    const uint8_t *gl, *gr;
     DevBuf& raw = ctx->buf("g_raw");
-    ASW_TRY(gl.ensure(plane));
-    ASW_TRY(gr.ensure(plane));
     ASW_TRY(raw.ensure(plane * n * 4));
-    ASW_TRY(f->disp.ensure(plane * 4));
-    f->vol_floats = 0;
-    if (keep_volume) {
-        ASW_TRY(f->vol.ensure(plane * n * 4));
-        f->vol_floats = plane * n;
-    }
-    if (f->channels == 3) {  // M.cpp:2514-2521
-        ASW_TRY(launch_bgr2gray(ctx->stream, f->L.as<uint8_t>(), H, W, gl.as<uint8_t>(), ctx->gray_bits));
-        ASW_TRY(launch_bgr2gray(ctx->stream, f->R.as<uint8_t>(), H, W, gr.as<uint8_t>(), ctx->gray_bits));
-    } else {
-        ASW_HIP_TRY(hipMemcpyAsync(gl.p, f->L.p, plane, hipMemcpyDeviceToDevice, ctx->stream));
-        ASW_HIP_TRY(hipMemcpyAsync(gr.p, f->R.p, plane, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    ASW_TRY(launch_cost_sad(ctx->stream, gl.as<uint8_t>(), gr.as<uint8_t>(), H, W, mp.disparity_type, mp.win, mp.minD, n,
-                            raw.as<float>()));  // M.cpp:2529-2547
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
-    ASW_TRY(launch_blo1(ctx->stream, gl.as<uint8_t>(), gr.as<uint8_t>(), raw.as<float>(), step, H, W, mp.disparity_type, mp.win, n,
+    ASW_TRY(ensure_outputs(f, n, keep_volume));
+    ASW_TRY(gray_pair(ctx, f->L.as<uint8_t>(), f->R.as<uint8_t>(), f->channels, H, W, &gl, &gr));  // M.cpp:2514-2521
+    ASW_TRY(launch_cost_sad(ctx->stream, gl, gr, H, W, mp.disparity_type, mp.win, mp.minD, n, raw.as<float>()));  // M.cpp:2529-2547
+    ASW_TRY(agg_begin(ctx));
+    ASW_TRY(launch_blo1(ctx->stream, gl, gr, raw.as<float>(), step, H, W, mp.disparity_type, mp.win, n,
                         keep_volume ? f->vol.as<float>() : nullptr, f->disp.as<float>()));
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
-    ctx->timing.aggregate_launches = 1;
-    return ASW_OK;
+    return agg_end(ctx, 1);
 }
 
 // computeAdaptiveWeight_bilateralGrid, M.cpp:2253-2430.  DISPARITY_LEFT only: the RIGHT branches read column `width` of the
@@ -654,42 +655,25 @@ static int run_bilgrid(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_
 {
     if (f->channels != 3 && f->channels != 1) return ASW_ERR_UNSUPPORTED_LAYOUT;
     if (mp.disparity_type != ASW_DISPARITY_LEFT) return ASW_ERR_UNSUPPORTED_LAYOUT;
-    const int H = f->rows, W = f->cols, n = mp.numD + 1;  // offsets minD .. minD+numD inclusive
+    const int H = f->rows, W = f->cols, n = method_info(ASW_ALG_ADAPTIVE_WEIGHT_BILATERAL_GRID)->planes(mp.numD);
     int nx, ny, nz;
     ASW_TRY(bilgrid_dims(H, W, mp.grid_rate_s, mp.grid_rate_r, &nx, &ny, &nz));
     const size_t plane = (size_t)H * W;
     const size_t cells = (size_t)(nx + 1) * (ny + 1) * (nz + 1) * (nz + 1);
     if (cells > ((size_t)1 << 33)) return ASW_ERR_ALLOC;  // 8 G cells = 96 GB of grid
-    DevBuf& gl = ctx->buf("grayL");
-    DevBuf& gr = ctx->buf("grayR");
+    const uint8_t *gl, *gr;
     DevBuf& gF = ctx->buf("grid_sum");
     DevBuf& gS = ctx->buf("grid_count");
     DevBuf& best = ctx->buf("grid_best");
-    ASW_TRY(gl.ensure(plane));
-    ASW_TRY(gr.ensure(plane));
     ASW_TRY(gF.ensure(cells * 8));
     ASW_TRY(gS.ensure(cells * 4));
     ASW_TRY(best.ensure(plane * 8));
-    ASW_TRY(f->disp.ensure(plane * 4));
-    f->vol_floats = 0;
-    if (keep_volume) {
-        ASW_TRY(f->vol.ensure(plane * n * 4));
-        f->vol_floats = plane * n;
-    }
-    if (f->channels == 3) {  // M.cpp:2271-2278
-        ASW_TRY(launch_bgr2gray(ctx->stream, f->L.as<uint8_t>(), H, W, gl.as<uint8_t>(), ctx->gray_bits));
-        ASW_TRY(launch_bgr2gray(ctx->stream, f->R.as<uint8_t>(), H, W, gr.as<uint8_t>(), ctx->gray_bits));
-    } else {
-        ASW_HIP_TRY(hipMemcpyAsync(gl.p, f->L.p, plane, hipMemcpyDeviceToDevice, ctx->stream));
-        ASW_HIP_TRY(hipMemcpyAsync(gr.p, f->R.p, plane, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
-    ASW_TRY(launch_bilgrid(ctx->stream, gl.as<uint8_t>(), gr.as<uint8_t>(), H, W, mp.grid_rate_s, mp.grid_rate_r, mp.minD, mp.numD,
-                           gF.as<double>(), gS.as<int>(), best.as<double>(), keep_volume ? f->vol.as<float>() : nullptr,
-                           f->disp.as<float>()));
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
-    ctx->timing.aggregate_launches = 1;
-    return ASW_OK;
+    ASW_TRY(ensure_outputs(f, n, keep_volume));
+    ASW_TRY(gray_pair(ctx, f->L.as<uint8_t>(), f->R.as<uint8_t>(), f->channels, H, W, &gl, &gr));  // M.cpp:2271-2278
+    ASW_TRY(agg_begin(ctx));
+    ASW_TRY(launch_bilgrid(ctx->stream, gl, gr, H, W, mp.grid_rate_s, mp.grid_rate_r, mp.minD, mp.numD, gF.as<double>(), gS.as<int>(),
+                           best.as<double>(), keep_volume ? f->vol.as<float>() : nullptr, f->disp.as<float>()));
+    return agg_end(ctx, 1);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -735,7 +719,7 @@ int sgbm_prepare(asw_ctx* ctx, const SgbmParams& p, int H, int W, int cn, bool w
 // getDisparity_SGBM: CV_Error for numDisparity % 16 != 0 or an even window (-> ASW_ERR_UNSUPPORTED_METHOD, the status of a method
 // the library does not serve); the images as they are (cn 1 or 3); StereoSGBM::create(minD, numD, w) with the settings below;
 // compute() -> convertTo(CV_8U, 1/16).  disparityType is ignored: both directions give the left-view map.  No volume is kept.
-static int run_sgbm(asw_ctx* ctx, Frame* f, const MatchParams& mp)
+static int run_sgbm(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool /* keep_volume: there is none to keep */)
 {
     if (mp.numD % 16 != 0 || mp.win % 2 == 0) return ASW_ERR_UNSUPPORTED_METHOD;
     const int cn = f->channels, w = mp.win > 0 ? mp.win : 3;
@@ -750,11 +734,9 @@ static int run_sgbm(asw_ctx* ctx, Frame* f, const MatchParams& mp)
     a.L = f->L.as<uint8_t>(); a.R = f->R.as<uint8_t>();
     a.vol = nullptr;
     a.ev_agg0 = ctx->ev[2]; a.ev_agg1 = ctx->ev[3];
-    const size_t plane = (size_t)f->rows * f->cols;
-    ASW_TRY(f->disp.ensure(plane * 4));
-    f->vol_floats = 0;
+    ASW_TRY(ensure_outputs(f, 0, false));
     ASW_TRY(launch_sgbm(ctx->stream, a));
-    ASW_TRY(launch_disp16_to_u8f(ctx->stream, a.disp16, plane, f->disp.as<float>()));
+    ASW_TRY(launch_disp16_to_u8f(ctx->stream, a.disp16, (size_t)f->rows * f->cols, f->disp.as<float>()));
     ctx->timing.aggregate_launches = 2;
     return ASW_OK;
 }
@@ -799,7 +781,7 @@ static int run_cross(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_vo
     if (mp.win % 2 == 0) return ASW_ERR_EVEN_WINDOW;
     if (mp.win < 1 || mp.win > 35) return ASW_ERR_BAD_ARGUMENT;
     if (f->channels != 3 && f->channels != 1) return ASW_ERR_UNSUPPORTED_LAYOUT;  // what asw_cost_ad takes
-    if (mp.disparity_type != ASW_DISPARITY_LEFT && mp.disparity_type != ASW_DISPARITY_RIGHT) return ASW_ERR_BAD_ARGUMENT;
+    ASW_TRY(check_direction(mp.disparity_type));
     if (mp.cross_tau < 0 || mp.cross_tau > 255 || mp.cross_trunc < 1 || mp.cross_trunc > 255) return ASW_ERR_BAD_ARGUMENT;
     const int H = f->rows, W = f->cols, n = mp.numD;
     // the sums the kernel keeps are local to a tile (a row prefix < 255 * 99, a column prefix < 255 * 35 * 66): no frame can take them
@@ -813,37 +795,56 @@ static int run_cross(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_vo
     ASW_TRY(raw.ensure(plane * n));
     ASW_TRY(arms.ensure(plane * sizeof(uint32_t)));
     ASW_TRY(cnt.ensure(plane * sizeof(uint16_t)));
-    ASW_TRY(f->disp.ensure(plane * 4));
-    f->vol_floats = 0;
-    if (keep_volume) {
-        ASW_TRY(f->vol.ensure(plane * n * 4));
-        f->vol_floats = plane * n;
-    }
+    ASW_TRY(ensure_outputs(f, n, keep_volume));
     const uint8_t* dL = f->L.as<uint8_t>();
     const uint8_t* dR = f->R.as<uint8_t>();
     ASW_TRY(launch_cost_ad(ctx->stream, dL, dR, H, W, f->channels, mp.disparity_type, mp.minD, n, 0, 0, raw.as<uint8_t>()));
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
+    ASW_TRY(agg_begin(ctx));
     ASW_TRY(launch_cross_arms(ctx->stream, mp.disparity_type == ASW_DISPARITY_RIGHT ? dR : dL, H, W, f->channels, mp.win, mp.cross_tau,
                               arms.as<uint32_t>(), cnt.as<uint16_t>()));
     ASW_TRY(launch_cross_aggregate(ctx->stream, raw.as<uint8_t>(), arms.as<uint32_t>(), cnt.as<uint16_t>(), H, W, mp.win, mp.cross_trunc,
                                    mp.minD, n, keep_volume ? f->vol.as<float>() : nullptr, f->disp.as<float>()));
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
-    ctx->timing.aggregate_launches = 3;  // arms, region sizes, aggregation + WTA
-    return ASW_OK;
+    return agg_end(ctx, 3);  // arms, region sizes, aggregation + WTA
+}
+
+// ------------------------------------------------------------------------------------------
+// the method table: one row per value of the selector's enum (M.cpp:49-87), in the enum's order.  A new method is a row here, its
+// runner above and its enum value in asw_mi355x.h.
+// ------------------------------------------------------------------------------------------
+static const MethodInfo k_methods[] = {
+    // algorithm, extra planes, runner, no volume, ignores disparity_type, no sub-pixel, packed parameters
+    {ASW_ALG_BM, 0, nullptr, true, true, false, false},     // served by asw_stereo_bm / asw_get_disparity_bm only
+    {ASW_ALG_SGBM, 0, run_sgbm, true, true, false, false},  // asw_sgbm has the volume S
+    {ASW_ALG_ADAPTIVE_WEIGHT, 1, run_bilateral_classic, false, false, false, false},  // offset <= max_offset, M.cpp:1021,1074
+    {ASW_ALG_ADAPTIVE_WEIGHT_8DIRECT, 1, run_direct8, false, false, false, false},    // M.cpp:1171
+    {ASW_ALG_ADAPTIVE_WEIGHT_GEODESIC, 1, run_geodesic, false, false, false, false},  // M.cpp:1447,1467
+    {ASW_ALG_ADAPTIVE_WEIGHT_BILATERAL_GRID, 1, run_bilgrid, false, false, false, false},  // M.cpp:2256,2280
+    {ASW_ALG_ADAPTIVE_WEIGHT_BLO1, 0, run_blo1, false, false, false, false},
+    {ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER, 0, run_guided_sad6, false, false, false, false},
+    {ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER_2, 0, run_guided_sim3, false, false, false, false},
+    {ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER_3, 0, run_guided_ncc, false, false, false, false},
+    {ASW_ALG_ADAPTIVE_WEIGHT_MEDIAN, 0, run_wmedian, false, false, false, false},
+    // computeNCC's disparity overload has its own candidate range and no selector volume in the RIGHT view
+    {ASW_ALG_NCC, 0, run_ncc, false, false, true, false},
+    {ASW_ALG_ADAPTIVE_WEIGHT_CROSS, 0, run_cross, false, false, false, true},
+};
+
+const MethodInfo* method_info(int method)
+{
+    const int n = (int)(sizeof(k_methods) / sizeof(k_methods[0]));
+    return method >= 0 && method < n && k_methods[method].algorithm == method ? &k_methods[method] : nullptr;
 }
 
 // Sub-pixel flags of a caller's disparity_type -> mp.subpixel, mp.disparity_type without them.  A value
 // without a flag bit passes through as it is: the methods refuse what they refused before, with the statuses they had.
-static int decode_subpixel(int algorithm, MatchParams& mp)
+static int decode_subpixel(const MethodInfo* m, MatchParams& mp)
 {
     const int flags = ASW_DISPARITY_SUBPIXEL_PARABOLA | ASW_DISPARITY_SUBPIXEL_EQUIANGULAR;
     mp.subpixel = 0;
-    // SGBM ignores disparity_type altogether; BM is not served whatever it holds
-    if (algorithm == ASW_ALG_SGBM || algorithm == ASW_ALG_BM || !(mp.disparity_type & flags)) return ASW_OK;
+    if ((m && m->ignores_disparity_type) || !(mp.disparity_type & flags)) return ASW_OK;
     if ((mp.disparity_type & flags) == flags) return ASW_ERR_BAD_ARGUMENT;
     if (mp.disparity_type & ~(flags | ASW_DISPARITY_RIGHT)) return ASW_ERR_BAD_ARGUMENT;
-    // computeNCC's disparity overload has its own candidate range and no selector volume in the RIGHT view
-    if (algorithm == ASW_ALG_NCC) return ASW_ERR_UNSUPPORTED_METHOD;
+    if (m && m->no_subpixel) return ASW_ERR_UNSUPPORTED_METHOD;
     mp.subpixel = mp.disparity_type & flags;
     mp.disparity_type &= ~flags;
     return ASW_OK;
@@ -855,30 +856,16 @@ int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp_in, 
     MatchParams mp = mp_in;
     if (mp.numD <= 0 || mp.minD < 0) return ASW_ERR_BAD_ARGUMENT;
     ASW_TRY(decode_algorithm(algorithm, &algorithm, &mp.cross_tau, &mp.cross_trunc));  // asw_alg_cross() values -> 12 + parameters
-    ASW_TRY(decode_subpixel(algorithm, mp));
+    const MethodInfo* m = method_info(algorithm);
+    ASW_TRY(decode_subpixel(m, mp));
     // the sub-pixel kernel reads the aggregated volume: the methods that can skip it (bilateral / direct8, geodesic, BLO1, the
     // bilateral grid) are asked for it; what the CALLER keeps is decided below
     const bool want_volume = keep_volume || mp.subpixel != 0;
     ASW_HIP_TRY(hipSetDevice(ctx->device));
     ASW_HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
-    int rc;
-    switch (algorithm) {  // M.cpp:49-87
-    case ASW_ALG_ADAPTIVE_WEIGHT: rc = run_bilateral(ctx, f, mp, want_volume); break;
-    case ASW_ALG_ADAPTIVE_WEIGHT_8DIRECT: rc = run_bilateral(ctx, f, mp, want_volume, true); break;
-    case ASW_ALG_ADAPTIVE_WEIGHT_GEODESIC: rc = run_geodesic(ctx, f, mp, want_volume); break;
-    case ASW_ALG_ADAPTIVE_WEIGHT_BILATERAL_GRID: rc = run_bilgrid(ctx, f, mp, want_volume); break;
-    case ASW_ALG_ADAPTIVE_WEIGHT_BLO1: rc = run_blo1(ctx, f, mp, want_volume); break;
-    case ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER: rc = run_guided(ctx, f, mp, want_volume, GUIDED_SAD6); break;
-    case ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER_2: rc = run_guided(ctx, f, mp, want_volume, GUIDED_SIM3); break;
-    case ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER_3: rc = run_guided(ctx, f, mp, want_volume, GUIDED_NCC); break;
-    case ASW_ALG_NCC: rc = run_ncc(ctx, f, mp, want_volume); break;
-    case ASW_ALG_ADAPTIVE_WEIGHT_MEDIAN: rc = run_wmedian(ctx, f, mp, want_volume); break;
-    case ASW_ALG_SGBM: rc = run_sgbm(ctx, f, mp); break;
-    case ASW_ALG_ADAPTIVE_WEIGHT_CROSS: rc = run_cross(ctx, f, mp, want_volume); break;
-    default: rc = ASW_ERR_UNSUPPORTED_METHOD; break;
-    }
+    int rc = m && m->run ? m->run(ctx, f, mp, want_volume) : ASW_ERR_UNSUPPORTED_METHOD;
     if (rc == ASW_OK && mp.subpixel)  // after the aggregation events: counts in total_ms and cost_ms, not in aggregate_ms
-        rc = launch_subpixel(ctx->stream, mp.subpixel, f->vol.as<float>(), asw_volume_planes(algorithm, mp.numD), f->rows, f->cols,
+        rc = launch_subpixel(ctx->stream, mp.subpixel, f->vol.as<float>(), m->planes(mp.numD), f->rows, f->cols,
                              mp.minD, f->disp.as<float>());
     if (rc != ASW_OK) {
         f->invalidate_results();
@@ -886,18 +873,10 @@ int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp_in, 
     }
     const size_t kept_floats = keep_volume ? f->vol_floats : 0;  // a volume asked for by the sub-pixel step alone is not the caller's
     f->vol_floats = 0;  // restored together with has_disp once nothing can fail any more
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
-    if (!sync) {  // pipelined callers (batch scheduler) order and wait on the stream themselves
-        f->has_disp = true; f->disp_rows = f->rows; f->disp_cols = f->cols; f->vol_floats = kept_floats;
-        return ASW_OK;
-    }
-    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    float t = 0;
-    ASW_HIP_TRY(hipEventElapsedTime(&t, ctx->ev[0], ctx->ev[1]));
-    ctx->timing.total_ms = t;
-    ASW_HIP_TRY(hipEventElapsedTime(&t, ctx->ev[2], ctx->ev[3]));
-    ctx->timing.aggregate_ms = t;
-    ctx->timing.cost_ms = ctx->timing.total_ms - ctx->timing.aggregate_ms;
+    if (sync)
+        ASW_TRY(timed_finish(ctx));
+    else  // pipelined callers (batch scheduler) order and wait on the stream themselves
+        ASW_HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
     f->has_disp = true; f->disp_rows = f->rows; f->disp_cols = f->cols; f->vol_floats = kept_floats;
     return ASW_OK;
 }
@@ -908,9 +887,7 @@ extern "C" int asw_match_resident(asw_ctx* ctx, int slot, int disparity_type, in
     if (!ctx) return ASW_ERR_BAD_ARGUMENT;
     Frame* f = frame_slot(ctx, slot, false);
     if (!f || !f->valid) return ASW_ERR_NO_FRAME;
-    MatchParams mp;
-    mp.disparity_type = disparity_type; mp.win = win_size; mp.minD = min_disparity; mp.numD = num_disparity;
-    return run_method(ctx, f, algorithm, mp, keep_volume != 0);
+    return run_method(ctx, f, algorithm, match_params(disparity_type, win_size, min_disparity, num_disparity), keep_volume != 0);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -978,7 +955,8 @@ int match_refined(asw_ctx* ctx, Frame* f, int algorithm, int win_size, int min_d
                   int refine_win, double gamma_c, double gamma_s, int* n_rejected, int* n_unfillable)
 {
     f->invalidate_results();
-    if (algorithm == ASW_ALG_SGBM || algorithm == ASW_ALG_BM) return ASW_ERR_UNSUPPORTED_METHOD;  // they carry their own disp12MaxDiff
+    const MethodInfo* m = method_info(algorithm);
+    if (m && m->no_volume) return ASW_ERR_UNSUPPORTED_METHOD;  // SGBM / BM carry their own disp12MaxDiff
     if (num_disparity <= 0 || min_disparity < 0) return ASW_ERR_BAD_ARGUMENT;  // as a plain match (run_method)
     int plain;  // unused: a bad asw_alg_cross() value is refused here with its own status, as a plain match refuses it
     ASW_TRY(decode_algorithm(algorithm, &plain, nullptr, nullptr));
@@ -987,8 +965,7 @@ int match_refined(asw_ctx* ctx, Frame* f, int algorithm, int win_size, int min_d
     rp.gamma_c = gamma_c; rp.gamma_s = gamma_s;
     if (rp.n == 0) return ASW_ERR_UNSUPPORTED_METHOD;
     ASW_TRY(check_refine_params(rp, f->rows, f->cols, f->channels));
-    MatchParams mp;
-    mp.win = win_size; mp.minD = min_disparity; mp.numD = num_disparity;
+    MatchParams mp = match_params(ASW_DISPARITY_RIGHT, win_size, min_disparity, num_disparity);
     DevBuf* side[2] = {&ctx->buf("refine_left"), &ctx->buf("refine_right")};
     asw_timing sum = {0, 0, 0, 0};
     for (int dt = 1; dt >= 0; dt--) {  // RIGHT first: a method whose right branch is not served is refused before any work
@@ -1046,9 +1023,7 @@ int asw_internal_enqueue_match(asw_ctx* ctx, int slot, int disparity_type, int a
 {
     Frame* f = frame_slot(ctx, slot, false);
     if (!f || !f->valid) return ASW_ERR_NO_FRAME;
-    MatchParams mp;
-    mp.disparity_type = disparity_type; mp.win = win_size; mp.minD = min_disparity; mp.numD = num_disparity;
-    return run_method(ctx, f, algorithm, mp, false, false);
+    return run_method(ctx, f, algorithm, match_params(disparity_type, win_size, min_disparity, num_disparity), false, false);
 }
 
 int asw_internal_check_pair(const asw_image* l, const asw_image* r, const asw_image* d)

@@ -11,17 +11,16 @@
 //                   each computed pixel, and the SAD volume only when the caller asks for it
 //   k_bm_lrkey      step 6, first pass: min of (cost, x) per target column x2 (packed 64-bit atomicMin: the first x wins a tie)
 //   k_bm_finish     step 6, second pass, and FILTERED outside the valid region
-//   k_disp16_to_u8  getDisparity_BM's convertTo(CV_8U, 1/16)
+// getDisparity_BM's convertTo(CV_8U, 1/16) is k_sgbm.hip's k_disp16_to_u8 (launch_disp16_to_u8).
 #include <limits.h>
 
 #include <algorithm>
 
 #include "asw_internal.h"
+#include "asw_device.h"
 #include "asw_host.h"
 
 namespace {
-
-inline unsigned blocks(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 
 // x-Sobel of rows y-1, y, y+1 (BORDER_REFLECT_101), clamp(v, -cap, cap) + cap; columns 0 and W-1 and, with an odd H, the whole
 // last row hold cap (prefilterXSobel works on row pairs).  blockIdx.y: 0 left, 1 right.
@@ -43,13 +42,6 @@ __global__ __launch_bounds__(256) void k_bm_prefilter(const uint8_t* __restrict_
         v = min(max(s, -cap), cap) + cap;
     }
     out[blockIdx.y * plane + i] = (uint8_t)v;
-}
-
-__device__ __forceinline__ int bm_wave_min(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-    return v;
 }
 
 // Horizontal window sums of one row along a tile: the window of column xb + t slides one column per step.  BmRow keeps, per
@@ -154,7 +146,7 @@ __global__ __launch_bounds__(64) void k_bm_match(const uint8_t* __restrict__ pf,
             }
             const int tsum = __builtin_amdgcn_readlane(tex, t) + a.st;
             if (lane == t) tex = tsum - b.st;
-            m = bm_wave_min(m);
+            m = wave_min(m);
             int mind = -1;  // the smallest k with the minimal SAD: chunk-major, then the lowest lane
 #pragma unroll
             for (int c = 0; c < NPL; c++) {
@@ -237,20 +229,6 @@ __global__ __launch_bounds__(256) void k_bm_finish(const short* __restrict__ raw
     out[i] = (short)v;
 }
 
-__global__ __launch_bounds__(256) void k_bm_fill_s16(short* __restrict__ out, size_t n, short v)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = v;
-}
-
-// convertTo(CV_8U, 1/16): round half to even, saturate
-__global__ __launch_bounds__(256) void k_disp16_to_u8(const short* __restrict__ in, size_t n, uint8_t* __restrict__ out)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    out[i] = (uint8_t)fminf(fmaxf(rintf((float)in[i] * 0.0625f), 0.0f), 255.0f);
-}
-
 template <int NPL>
 int launch_match(hipStream_t s, const BmLaunch& a, const uint8_t* pf, short* raw, int* cost)
 {
@@ -289,8 +267,7 @@ int launch_bm(hipStream_t s, const BmLaunch& a)
     const int y0 = h, y1 = H - h, x0 = lofs + h, x1 = W - h;
     if (a.vol) ASW_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)a.vol, 0x7fc00000, plane * D, s));  // NaN where nothing is computed
     if (y1 <= y0 || x1 <= x0) {  // empty valid region: the whole map is FILTERED (this library's definition)
-        hipLaunchKernelGGL(k_bm_fill_s16, dim3(blocks(plane, 256)), dim3(256), 0, s, a.disp16, plane, (short)FILTERED);
-        ASW_HIP_TRY(hipGetLastError());
+        ASW_TRY(launch_fill_s16(s, a.disp16, plane, (short)FILTERED));
         if (a.ev_agg0) ASW_HIP_TRY(hipEventRecord(a.ev_agg0, s));
         if (a.ev_agg1) ASW_HIP_TRY(hipEventRecord(a.ev_agg1, s));
         return ASW_OK;
@@ -305,13 +282,7 @@ int launch_bm(hipStream_t s, const BmLaunch& a)
     hipLaunchKernelGGL(k_bm_prefilter, dim3(blocks(plane, 256), 2), dim3(256), 0, s, a.L, a.R, H, W, a.cap, pf);
     ASW_HIP_TRY(hipGetLastError());
     if (a.ev_agg0) ASW_HIP_TRY(hipEventRecord(a.ev_agg0, s));
-    const int npl = (D + 63) / 64;
-    if (npl <= 1) ASW_TRY((launch_match<1>(s, a, pf, raw, cost)));
-    else if (npl <= 2) ASW_TRY((launch_match<2>(s, a, pf, raw, cost)));
-    else if (npl <= 4) ASW_TRY((launch_match<4>(s, a, pf, raw, cost)));
-    else if (npl <= 8) ASW_TRY((launch_match<8>(s, a, pf, raw, cost)));
-    else if (npl <= 16) ASW_TRY((launch_match<16>(s, a, pf, raw, cost)));
-    else return ASW_ERR_BAD_ARGUMENT;
+    ASW_TRY(dispatch_npl(D, [&](auto npl) { return launch_match<decltype(npl)::value>(s, a, pf, raw, cost); }));
     if (a.ev_agg1) ASW_HIP_TRY(hipEventRecord(a.ev_agg1, s));
     const int minX1 = minD + D;
     if (a.M >= 0 && minX1 < W) {
@@ -326,12 +297,5 @@ int launch_bm(hipStream_t s, const BmLaunch& a)
     ASW_HIP_TRY(hipGetLastError());
     if (a.speckle_range >= 0 && a.speckle_window > 0)
         ASW_TRY(launch_filter_speckles(s, a.disp16, H, W, FILTERED, a.speckle_window, a.speckle_range, spk));
-    return ASW_OK;
-}
-
-int launch_disp16_to_u8(hipStream_t s, const short* disp16, size_t n, uint8_t* out)
-{
-    hipLaunchKernelGGL(k_disp16_to_u8, dim3(blocks(n, 256)), dim3(256), 0, s, disp16, n, out);
-    ASW_HIP_TRY(hipGetLastError());
     return ASW_OK;
 }

@@ -11,8 +11,9 @@
 //   k_sgbm_line       asw_sgbm_paths only: bottom->top and the four diagonal paths, one wavefront per column / (anti-)diagonal
 //   k_sgbm_row        left->right and right->left paths, winner, uniqueness, subpixel, disp2 keys: one wavefront per row
 //   k_sgbm_lr         the left-right rule of step 6 -> int16 map
-//   k_median3_s16     step 7;  k_spk_*: step 8 (union-find over the whole frame);  k_disp16_to_u8f: step 9
+//   k_median3_s16     step 7;  k_spk_*: step 8 (union-find over the whole frame);  k_disp16_to_u8<float>: step 9
 #include "asw_internal.h"
+#include "asw_device.h"
 #include "asw_host.h"
 
 namespace {
@@ -87,13 +88,6 @@ __global__ __launch_bounds__(256) void k_sgbm_hcost(const int4* __restrict__ pf,
         out[(size_t)xi * D] = sum;
         sum += pix(xi + h + 1) - pix(xi - h);
     }
-}
-
-__device__ __forceinline__ int wave_min(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-    return v;
 }
 
 // One path step over the candidates of a wavefront (d = k * 64 + lane): Lr holds L(p - r, d) on entry and L(p, d) on exit, m the
@@ -501,20 +495,20 @@ __global__ __launch_bounds__(256) void k_spk_apply(short* __restrict__ img, size
     if (r >= 0 && size[r] <= max_size) img[i] = (short)new_val;
 }
 
-// convertTo(CV_8U, 1/16): round half to even, saturate -- as f32 for the selector's CV_32F result
-__global__ __launch_bounds__(256) void k_disp16_to_u8f(const short* __restrict__ in, size_t n, float* __restrict__ out)
+// convertTo(CV_8U, 1/16): round half to even, saturate -- T = float for the selector's CV_32F result, uint8_t for getDisparity_BM
+template <typename T>
+__global__ __launch_bounds__(256) void k_disp16_to_u8(const short* __restrict__ in, size_t n, T* __restrict__ out)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    out[i] = fminf(fmaxf(rintf((float)in[i] * 0.0625f), 0.0f), 255.0f);
+    out[i] = (T)fminf(fmaxf(rintf((float)in[i] * 0.0625f), 0.0f), 255.0f);
 }
 
-inline unsigned blocks(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
-
+// the path kernels of one frame; hb, C, T, disp_raw, key: regions of a.scratch as launch_sgbm carves them
 template <int NPL>
-int launch_paths(hipStream_t s, const int* hb, int H, int W, int minD, int D, int h, int P1, int P2, int U, int keep_S, int paths,
-                 int* C, int* T, int* disp_raw, unsigned long long* key)
+int launch_paths(hipStream_t s, const SgbmLaunch& a, const int* hb, int* C, int* T, int* disp_raw, unsigned long long* key)
 {
+    const int H = a.H, W = a.W, minD = a.minD, D = a.D, h = a.w / 2, P1 = a.P1, P2 = a.P2, paths = a.paths;
     const int Wv = W - (minD + D);
     hipLaunchKernelGGL(k_sgbm_top<NPL>, dim3(Wv), dim3(64), 2 * D * sizeof(int), s, hb, H, Wv, D, h, P1, P2, C, T);
     ASW_HIP_TRY(hipGetLastError());
@@ -528,8 +522,8 @@ int launch_paths(hipStream_t s, const int* hb, int H, int W, int minD, int D, in
                            P2, geom, dirs[geom]);
         ASW_HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_sgbm_row<NPL>, dim3(H), dim3(64), 4 * D * sizeof(int), s, C, T, H, W, minD, D, P1, P2, U, keep_S, disp_raw,
-                       key);
+    hipLaunchKernelGGL(k_sgbm_row<NPL>, dim3(H), dim3(64), 4 * D * sizeof(int), s, C, T, H, W, minD, D, P1, P2, a.U, a.vol != nullptr,
+                       disp_raw, key);
     ASW_HIP_TRY(hipGetLastError());
     return ASW_OK;
 }
@@ -550,8 +544,7 @@ int launch_sgbm(hipStream_t s, const SgbmLaunch& a)
     const size_t plane = (size_t)H * W;
     const int INVALID = 16 * (minD - 1);
     if (W <= minD + D) {  // no valid column: every pixel INVALID, nothing to filter
-        hipLaunchKernelGGL(k_fill_s16, dim3(blocks(plane, 256)), dim3(256), 0, s, a.disp16, plane, (short)INVALID);
-        ASW_HIP_TRY(hipGetLastError());
+        ASW_TRY(launch_fill_s16(s, a.disp16, plane, (short)INVALID));
         if (a.vol) ASW_HIP_TRY(hipMemsetAsync(a.vol, 0, plane * D * sizeof(float), s));
         if (a.ev_agg0) ASW_HIP_TRY(hipEventRecord(a.ev_agg0, s));
         if (a.ev_agg1) ASW_HIP_TRY(hipEventRecord(a.ev_agg1, s));
@@ -574,14 +567,8 @@ int launch_sgbm(hipStream_t s, const SgbmLaunch& a)
     hipLaunchKernelGGL(k_sgbm_hcost, dim3(blocks((size_t)H * D, 256)), dim3(256), 0, s, pf, H, W, a.cn, minD, D, a.w / 2, hb);
     ASW_HIP_TRY(hipGetLastError());
     ASW_HIP_TRY(hipMemsetAsync(key, 0xff, plane * 8, s));
-    const int npl = (D + 63) / 64;
     if (a.ev_agg0) ASW_HIP_TRY(hipEventRecord(a.ev_agg0, s));
-    if (npl <= 1) ASW_TRY(launch_paths<1>(s, hb, H, W, minD, D, a.w / 2, a.P1, a.P2, a.U, a.vol != nullptr, a.paths, C, T, disp_raw, key));
-    else if (npl <= 2) ASW_TRY(launch_paths<2>(s, hb, H, W, minD, D, a.w / 2, a.P1, a.P2, a.U, a.vol != nullptr, a.paths, C, T, disp_raw, key));
-    else if (npl <= 4) ASW_TRY(launch_paths<4>(s, hb, H, W, minD, D, a.w / 2, a.P1, a.P2, a.U, a.vol != nullptr, a.paths, C, T, disp_raw, key));
-    else if (npl <= 8) ASW_TRY(launch_paths<8>(s, hb, H, W, minD, D, a.w / 2, a.P1, a.P2, a.U, a.vol != nullptr, a.paths, C, T, disp_raw, key));
-    else if (npl <= 16) ASW_TRY(launch_paths<16>(s, hb, H, W, minD, D, a.w / 2, a.P1, a.P2, a.U, a.vol != nullptr, a.paths, C, T, disp_raw, key));
-    else return ASW_ERR_BAD_ARGUMENT;
+    ASW_TRY(dispatch_npl(D, [&](auto npl) { return launch_paths<decltype(npl)::value>(s, a, hb, C, T, disp_raw, key); }));
     if (a.ev_agg1) ASW_HIP_TRY(hipEventRecord(a.ev_agg1, s));
     if (a.vol) {
         hipLaunchKernelGGL(k_sgbm_volume, dim3(blocks(plane * D, 256)), dim3(256), 0, s, T, H, W, minD, D, a.vol);
@@ -616,9 +603,20 @@ int launch_filter_speckles(hipStream_t s, short* img, int H, int W, int new_val,
     return ASW_OK;
 }
 
-int launch_disp16_to_u8f(hipStream_t s, const short* disp16, size_t n, float* out)
+int launch_fill_s16(hipStream_t s, short* out, size_t n, short v)
 {
-    hipLaunchKernelGGL(k_disp16_to_u8f, dim3(blocks(n, 256)), dim3(256), 0, s, disp16, n, out);
+    hipLaunchKernelGGL(k_fill_s16, dim3(blocks(n, 256)), dim3(256), 0, s, out, n, v);
     ASW_HIP_TRY(hipGetLastError());
     return ASW_OK;
 }
+
+template <typename T>
+static int launch_disp16_convert(hipStream_t s, const short* disp16, size_t n, T* out)
+{
+    hipLaunchKernelGGL(k_disp16_to_u8<T>, dim3(blocks(n, 256)), dim3(256), 0, s, disp16, n, out);
+    ASW_HIP_TRY(hipGetLastError());
+    return ASW_OK;
+}
+
+int launch_disp16_to_u8f(hipStream_t s, const short* disp16, size_t n, float* out) { return launch_disp16_convert(s, disp16, n, out); }
+int launch_disp16_to_u8(hipStream_t s, const short* disp16, size_t n, uint8_t* out) { return launch_disp16_convert(s, disp16, n, out); }
