@@ -30,6 +30,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "asw_device.h"
 #include "asw_internal.h"
 
 namespace {
@@ -65,12 +66,6 @@ struct Layout {
     {
     }
 };
-
-// 32-bit byte offset from a uniform base: global_load with an SGPR base, no 64-bit address arithmetic per lane
-__device__ __forceinline__ float lut_at(const float* __restrict__ lut, unsigned idx)
-{
-    return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(lut) + (idx << 2));
-}
 
 template <int DC>
 __device__ __forceinline__ void load_cost(const uint8_t* cell, uint32_t (&cw)[(DC + 3) / 4])
@@ -226,12 +221,8 @@ __device__ __forceinline__ void process_chunk(const BilParams& p, const uint8_t*
             sWL[t * (TH * TW) + tid] = wlv[t];
         }
         if (doB) *dstB = wb;
-        // The hardware orders them; the COMPILER must be told that other lanes read these words (to one thread its store and the
-        // loads of its neighbours' slots never alias, so it may delay or sink the store: k_guided.hip ran into exactly that).
-        // Wavefront-scope fences cost no instruction.
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        // other lanes read these words
+        wave_lds_sync();
         if (g0 + G < p.ntaps) gather(g0 + G);  // in flight while this group is accumulated
         // rolled on purpose: one tap's operands (1 + 4 + DC registers) live at a time keeps the kernel at
         // <= 128 VGPRs, i.e. 4 waves per SIMD, which hides the LDS latency better than deeper unrolling did
@@ -252,9 +243,7 @@ __device__ __forceinline__ void process_chunk(const BilParams& p, const uint8_t*
             }
         }
         // the next group's stores stay behind this group's loads
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
     }
 
     const int x = x0 + tx, y = y0 + ty;

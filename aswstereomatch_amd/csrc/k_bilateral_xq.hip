@@ -51,6 +51,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "asw_device.h"
 #include "asw_internal.h"
 
 namespace {
@@ -131,11 +132,6 @@ __device__ __forceinline__ double cost_sample(uint32_t gl, uint32_t gr, uint32_t
 {
     const uint32_t c = __builtin_amdgcn_sad_u16(gl, gr, 0u);  // the high halves are zero: |gl - gr|
     return __builtin_bit_cast(double, (uint64_t)c | ((uint64_t)hi0 << 32));
-}
-
-__device__ __forceinline__ float lut_at(const float* __restrict__ lut, unsigned idx)
-{
-    return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(lut) + (idx << 2));
 }
 
 // packed cell table in LDS: (dxw + 8) | (dyw + 8) << 4 | class << 8

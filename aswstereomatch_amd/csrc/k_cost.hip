@@ -84,14 +84,10 @@ __device__ __forceinline__ float2 minmax_scale(double smin, double smax)
 
 __device__ __forceinline__ void block_minmax_commit(uint32_t lo, uint32_t hi, uint32_t* out2)
 {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = min(lo, (uint32_t)__shfl_xor((int)lo, o));
-        hi = max(hi, (uint32_t)__shfl_xor((int)hi, o));
-    }
+    const MinMax<uint32_t> r = wave_minmax(lo, hi);
     if ((threadIdx.x & 63) == 0) {
-        atomicMin(out2, lo);
-        atomicMax(out2 + 1, hi);
+        atomicMin(out2, r.lo);
+        atomicMax(out2 + 1, r.hi);
     }
 }
 
@@ -214,7 +210,7 @@ __global__ __launch_bounds__(256) void k_scales_from_parts(const uint32_t* __res
     }
     __shared__ uint32_t s_lo[4], s_hi[4];
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
+    for (int o = 32; o > 0; o >>= 1) {  // wave_minmax, inline: through the call the registers of the LDS stores below come out renumbered
         lo = min(lo, (uint32_t)__shfl_xor((int)lo, o));
         hi = max(hi, (uint32_t)__shfl_xor((int)hi, o));
     }
@@ -328,13 +324,9 @@ __global__ __launch_bounds__(64) void k_guide_scales_lr(const uint32_t* __restri
         lo = min(lo, colmmR[2 * c]);
         hi = max(hi, colmmR[2 * c + 1]);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = min(lo, __shfl_xor(lo, o));
-        hi = max(hi, __shfl_xor(hi, o));
-    }
+    const MinMax<int> r = wave_minmax(lo, hi);
     if (threadIdx.x == 0) {
-        double mn = fmin((double)ord2f(ordL[0]), (double)lo), mx = fmax((double)ord2f(ordL[1]), (double)hi);
+        double mn = fmin((double)ord2f(ordL[0]), (double)r.lo), mx = fmax((double)ord2f(ordL[1]), (double)r.hi);
         scales[k] = minmax_scale(mn, mx);
     }
 }

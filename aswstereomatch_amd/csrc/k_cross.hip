@@ -80,8 +80,7 @@ __global__ __launch_bounds__(256) void k_cross_aggregate(const uint8_t* __restri
     int* B = lds + (size_t)DC * RH * SA;
     const int tid = threadIdx.x, tx = tid & 63, ty = tid >> 6;
     // every XCD takes a contiguous run of tiles: neighbouring tiles share their halo lines of the cost volume in one L2
-    const int nwg = gridDim.x * gridDim.y, lin = blockIdx.x + gridDim.x * blockIdx.y;
-    const int xcd = lin & 7, vid = xcd * (nwg >> 3) + min(xcd, nwg & 7) + (lin >> 3);
+    const int vid = xcd_contiguous(gridDim.x * gridDim.y, blockIdx.x + gridDim.x * blockIdx.y);
     const int x0 = (vid % (int)gridDim.x) * TW, y0 = (vid / (int)gridDim.x) * TH;
     const int x = x0 + tx;
     const size_t plane = (size_t)H * W;

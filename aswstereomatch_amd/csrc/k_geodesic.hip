@@ -33,8 +33,6 @@ __global__ __launch_bounds__(256) void k_pack_bgrx(const uint8_t* __restrict__ b
     if (i < n) out[i] = (uint32_t)bgr[3 * i] | ((uint32_t)bgr[3 * i + 1] << 8) | ((uint32_t)bgr[3 * i + 2] << 16);
 }
 
-__device__ __forceinline__ uint32_t cdist(uint32_t a, uint32_t b) { return __builtin_amdgcn_sad_u8(a, b, 0u); }
-
 // One thread = one pixel.  WIN is the (odd) window size; planes: [WIN*WIN][H][W] (u16 or f32).
 // The backward sweep can only reach the cells above the centre and those left of it in its own row: every cell below the centre row
 // (and right of the centre in it) still holds FLT_MAX when the forward sweep starts.  So the backward sweep runs rows h+1 .. 1
@@ -373,11 +371,10 @@ __global__ __launch_bounds__(256) void k_asw_geodesic_few(const uint32_t* __rest
     constexpr int h = WIN / 2, TR = TH + 2 * h, LW = TW + 2 * h;
     __shared__ uint32_t sF[TR * LW], sO[TR * LW];
     const int tid = threadIdx.x, tx = tid & 63, ty = tid >> 6;
-    // every XCD takes a contiguous run of tiles (see k_asw_geodesic_xq): a tile row is 128 bytes of a u16 weight plane at an
+    // every XCD takes a contiguous run of tiles: a tile row is 128 bytes of a u16 weight plane at an
     // arbitrary alignment, i.e. two 128-byte lines, each shared with a neighbour -- dealt round-robin, the neighbours sat on
     // other XCDs and every line came from HBM twice (0.82 GB fetched for 0.42 GB of tables)
-    const int nwg = gridDim.x * gridDim.y, lin = blockIdx.x + gridDim.x * blockIdx.y;
-    const int xcd = lin & 7, vid = xcd * (nwg >> 3) + min(xcd, nwg & 7) + (lin >> 3);
+    const int vid = xcd_contiguous(gridDim.x * gridDim.y, blockIdx.x + gridDim.x * blockIdx.y);
     const int x0 = (vid % (int)gridDim.x) * TW, y0 = (vid / (int)gridDim.x) * TH;
     const int x = x0 + tx, y = y0 + ty, xc = min(x, W - 1), yc = min(y, H - 1);
     const size_t plane = (size_t)H * W;

@@ -59,6 +59,58 @@ __device__ __forceinline__ void guide_unpack(uint32_t u, float2 sc, float* I)
     I[2] = (float)((u >> 16) & 0xffu) * sc.x + sc.y;
 }
 
+// Horizontal pass over a strip of PAIR sums (k_box_walk's PAIRS, the pair kernels): per plane the strip holds {V[2l] + V[2l+1],
+// V[2l]} at lane l's two slots, and with T = the HP - 1 pair sums of lanes l+1 .. l+HP-1 the lane's two windows of 2 HP + 1
+// columns are (pair[l] + T) + V[2(l+HP)] and (V[2l+1] + T) + pair[l+HP].  b: the lane's own slot in plane 0, STRIDE doubles per
+// plane; v0 / v1: the lane's own two column sums; m0 / m1: the NPL box means of its two columns.
+// All LDS reads of a group of planes are issued before the first addition (the scheduler, left alone, orders them plane by
+// plane to save registers: ~16 exposed LDS round trips per step, and at two wavefronts per SIMD nobody hides them -- one
+// wavefront alone spent two thirds of a step waiting).
+template <int NPL, int HP, int STRIDE>
+__device__ __forceinline__ void pair_row_means(const double* b, const double (&v0)[NPL], const double (&v1)[NPL], double scale,
+                                               float (&m0)[NPL], float (&m1)[NPL])
+{
+    constexpr int GRP = 2;  // planes whose reads are in flight together (16 registers each; all four: spills)
+#pragma unroll
+    for (int p0 = 0; p0 < NPL; p0 += GRP) {
+        double bb[GRP][2 * HP + 2];
+#pragma unroll
+        for (int g = 0; g < GRP; g++)
+            if (p0 + g < NPL) {
+                const double* bp = b + (p0 + g) * STRIDE;
+#pragma unroll
+                for (int i = 2; i < 2 * HP + 2; i++)
+                    if (!(i & 1) || i == 2 * HP + 1) bb[g][i] = bp[i];  // pair sums of lanes l+1 .. l+HP, V[even] of l+HP
+            }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int g = 0; g < GRP; g++)
+            if (p0 + g < NPL) {
+                const int p = p0 + g;
+                double t = bb[g][2];
+#pragma unroll
+                for (int i = 2; i < HP; i++) t = t + bb[g][2 * i];
+                const double s0 = ((v0[p] + v1[p]) + t) + bb[g][2 * HP + 1];
+                const double s1 = (v1[p] + t) + bb[g][2 * HP];
+                m0[p] = (float)(s0 * scale);
+                m1[p] = (float)(s1 * scale);
+            }
+    }
+}
+
+// Workgroup wj = blockIdx.x >> 3 of XCD blockIdx.x & 7 -> region (strip xw, band by) of the pair kernels: as in k_box_walk,
+// every XCD takes a contiguous run of regions and runs through all n slices of a region (wj % n) before the next.
+// false: nothing to do for the whole workgroup.
+__device__ __forceinline__ bool pair_region(int wj, int n, int nxw, int nby, int& xw, int& by)
+{
+    const int nreg = nxw * nby, rpx = (nreg + 7) >> 3;
+    const int reg = (blockIdx.x & 7) * rpx + wj / n;
+    if (wj / n >= rpx || reg >= nreg) return false;
+    xw = reg % nxw;
+    by = reg / nxw;
+    return true;
+}
+
 // Every wavefront owns a strip of 128 input columns (two adjacent ones per lane, 128-(k-1) output columns)
 // of a band of rows and walks down the band on its own:
 //   * vertical running sums in f64 registers (add the entering row, subtract the leaving one -- ColumnSum's
@@ -297,25 +349,17 @@ __global__ __launch_bounds__(BW) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
                         for (int c = 0; c < CPL; c++) hs[(n * NP + p) * (SW + 2) + c0 + c] = vs[c][n][p];
                     }
                 }
-            // Same-wavefront LDS traffic is ordered in hardware: the reads below see the writes above without a workgroup
-            // barrier.  The COMPILER must be told that other lanes read these words: to a single thread its own store
-            // (offset c0) and its loads (offsets c0+1 ..) never alias, and LLVM promotes the stored value to a register and
-            // sinks the store out of the row loop (seen with the straight-line walk: every row after the first was wrong).
-            // Wavefront-scope fences cost no instruction.
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            // the reads below (offsets c0+1 ..) are of other lanes' stores (offset c0)
+            wave_lds_sync();
             if (any_out) {
                 const int y = y0 + s - (k - 1);
 #pragma unroll
                 for (int n = 0; n < ND; n++) {
                     float m[CPL][NP];
                     if constexpr (PAIRS && (RING || WPE <= 3)) {  // (register targets of 4 wavefronts per SIMD have no room for it)
-                        // All LDS reads of a group of planes are issued before the first addition (the scheduler, left alone,
-                        // orders them plane by plane to save registers: ~16 exposed LDS round trips per step, and at two
-                        // wavefronts per SIMD nobody hides them -- one wavefront alone spent two thirds of a step waiting).
+                        // pair_row_means, inline: through the call the scalar code around the walk is scheduled differently
                         constexpr int HP = (KT - 1) / 2;
-                        constexpr int GRP = 2;  // planes whose reads are in flight together (16 registers each; all four: spills)
+                        constexpr int GRP = 2;
 #pragma unroll
                         for (int p0 = 0; p0 < NP; p0 += GRP) {
                             double bb[GRP][2 * HP + 2];
@@ -398,9 +442,7 @@ __global__ __launch_bounds__(BW) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
                 }
             }
             // the next row's stores stay behind this row's loads
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
         }
     };
     using T = std::true_type;
@@ -1204,10 +1246,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     float* xch = reinterpret_cast<float*>(pbase + 2 * NPL * (SW + 2) * 8);
     const int H = a.H, W = a.W;
     const int wj = blockIdx.x >> 3;
-    const int nreg = a.nxw * a.nby, rpx = (nreg + 7) >> 3;
-    const int reg = (blockIdx.x & 7) * rpx + wj / a.n;
-    if (wj / a.n >= rpx || reg >= nreg) return;  // whole workgroup
-    const int xw = reg % a.nxw, by = reg / a.nxw;
+    int xw, by;
+    if (!pair_region(wj, a.n, a.nxw, a.nby, xw, by)) return;  // whole workgroup
     const int kz = wj % a.n + pr;
     const bool live = kz < a.n;                   // a pair without a slice still keeps the workgroup's barriers
     const int kzc = min(kz, a.n - 1);
@@ -1259,40 +1299,11 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             hs[p * (SW + 2) + c0] = vs[0][p] + vs[1][p];
             hs[p * (SW + 2) + c0 + 1] = vs[0][p];
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
 #pragma unroll
         for (int p = 0; p < NPL; p++) { m[0][p] = 0.0f; m[1][p] = 0.0f; }
-        if (reader) {
-            constexpr int GRP = 2;  // planes whose LDS reads are in flight together
-#pragma unroll
-            for (int p0 = 0; p0 < NPL; p0 += GRP) {
-                double bb[GRP][2 * HP + 2];
-#pragma unroll
-                for (int g = 0; g < GRP; g++) {
-                    const double* b = hs + (p0 + g) * (SW + 2) + c0;
-#pragma unroll
-                    for (int i = 2; i < 2 * HP + 2; i++)
-                        if (!(i & 1) || i == 2 * HP + 1) bb[g][i] = b[i];
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int g = 0; g < GRP; g++) {
-                    const int p = p0 + g;
-                    double t = bb[g][2];
-#pragma unroll
-                    for (int i = 2; i < HP; i++) t = t + bb[g][2 * i];
-                    const double s0 = ((vs[0][p] + vs[1][p]) + t) + bb[g][2 * HP + 1];
-                    const double s1 = (vs[1][p] + t) + bb[g][2 * HP];
-                    m[0][p] = (float)(s0 * scale);
-                    m[1][p] = (float)(s1 * scale);
-                }
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (reader) pair_row_means<NPL, HP, SW + 2>(hs + c0, vs[0], vs[1], scale, m[0], m[1]);
+        wave_lds_sync();
     };
 
     // one iteration: A computes input row `it` (and, from it = K-1 on, hands a/b row it-(K-1) to B through slot it & 1); barrier;
@@ -1455,10 +1466,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     float* xch = reinterpret_cast<float*>(smem + 2 * NPL * (SW + 2) * 8);             // [2][SW]: partial dot products, double-buffered
     const int H = a.H, W = a.W;
     const int wj = blockIdx.x >> 3;
-    const int nreg = a.nxw * a.nby, rpx = (nreg + 7) >> 3;
-    const int reg = (blockIdx.x & 7) * rpx + wj / a.n;
-    if (wj / a.n >= rpx || reg >= nreg) return;  // whole workgroup
-    const int xw = reg % a.nxw, by = reg / a.nxw;
+    int xw, by;
+    if (!pair_region(wj, a.n, a.nxw, a.nby, xw, by)) return;  // whole workgroup
     const int kz = wj % a.n;
     const int xo0 = xw * XO, c0 = 2 * lane;
     const int y0 = by * a.band, y1 = min(H, y0 + a.band);
@@ -1545,41 +1554,12 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 hs[p * (SW + 2) + c0] = vs[0][p] + vs[1][p];
                 hs[p * (SW + 2) + c0 + 1] = vs[0][p];
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
             float m[2][NPL];
 #pragma unroll
             for (int p = 0; p < NPL; p++) { m[0][p] = 0.0f; m[1][p] = 0.0f; }
-            if (reader) {
-                constexpr int GRP = 2;
-#pragma unroll
-                for (int p0 = 0; p0 < NPL; p0 += GRP) {
-                    double bb[GRP][2 * HP + 2];
-#pragma unroll
-                    for (int g = 0; g < GRP; g++) {
-                        const double* b = hs + (p0 + g) * (SW + 2) + c0;
-#pragma unroll
-                        for (int i = 2; i < 2 * HP + 2; i++)
-                            if (!(i & 1) || i == 2 * HP + 1) bb[g][i] = b[i];
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int g = 0; g < GRP; g++) {
-                        const int p = p0 + g;
-                        double t = bb[g][2];
-#pragma unroll
-                        for (int i = 2; i < HP; i++) t = t + bb[g][2 * i];
-                        const double s0 = ((vs[0][p] + vs[1][p]) + t) + bb[g][2 * HP + 1];
-                        const double s1 = (vs[1][p] + t) + bb[g][2 * HP];
-                        m[0][p] = (float)(s0 * scale);
-                        m[1][p] = (float)(s1 * scale);
-                    }
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            if (reader) pair_row_means<NPL, HP, SW + 2>(hs + c0, vs[0], vs[1], scale, m[0], m[1]);
+            wave_lds_sync();
             float* xs = xch + (s & 1) * SW;
             const float2 sc[2] = {gcol0.sc, gcol1.sc};
             float I[2][3];
@@ -1682,7 +1662,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     double* hs = reinterpret_cast<double*>(smem) + (size_t)role * NPL * (SW + 2);
     float* xch = reinterpret_cast<float*>(smem + 2 * NPL * (SW + 2) * 8);  // [2][SW] partial dot products
     const int H = a.H, W = a.W;
-    const int wj = blockIdx.x >> 3;
+    const int wj = blockIdx.x >> 3;  // pair_region, inline: through the call this kernel's registers come out renumbered
     const int nreg = a.nxw * a.nby, rpx = (nreg + 7) >> 3;
     const int reg = (blockIdx.x & 7) * rpx + wj / a.n;
     if (wj / a.n >= rpx || reg >= nreg) return;  // whole workgroup
@@ -1813,13 +1793,11 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                 hs[p * (SW + 2) + c0] = vs[0][p] + vs[1][p];
                 hs[p * (SW + 2) + c0 + 1] = vs[0][p];
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
             float m[2][NPL];
 #pragma unroll
             for (int p = 0; p < NPL; p++) { m[0][p] = 0.0f; m[1][p] = 0.0f; }
-            if (reader) {
+            if (reader) {  // pair_row_means, inline: a call here spills (the kernel sits on its 168-register ceiling)
                 constexpr int GRP = 2;
 #pragma unroll
                 for (int p0 = 0; p0 < NPL; p0 += GRP) {
@@ -1845,9 +1823,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                     }
                 }
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
             // a_c = cov_c / den_c of this word (M.cpp:2796-2846), the partial dot product in the reference's order
             float o[2][4], dotp[2];
 #pragma unroll
@@ -1890,13 +1866,9 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                 v4f* tr = reinterpret_cast<v4f*>(hs);
                 tr[c0] = v4f{o[0][0], o[0][1], o[0][2], o[0][3]};
                 tr[c0 + 1] = v4f{o[1][0], o[1][1], o[1][2], o[1][3]};
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_sync();
                 const v4f w0 = tr[lane], w1 = tr[64 + lane];
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_sync();
                 float* dst = abo_row0 + (size_t)y * W * 4;
                 if (xo0 + lane < W) __builtin_nontemporal_store(w0, reinterpret_cast<v4f*>(dst + 4 * lane));
                 if (64 + lane < XO && xo0 + 64 + lane < W) __builtin_nontemporal_store(w1, reinterpret_cast<v4f*>(dst + 4 * (64 + lane)));

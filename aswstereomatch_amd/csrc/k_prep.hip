@@ -146,14 +146,10 @@ __global__ __launch_bounds__(256) void k_disp_to_u8(const float* __restrict__ di
         lo = min(lo, v);
         hi = max(hi, v);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lo = min(lo, __shfl_xor(lo, o));
-        hi = max(hi, __shfl_xor(hi, o));
-    }
+    const MinMax<int> r = wave_minmax(lo, hi);
     if ((threadIdx.x & 63) == 0) {
-        atomicMin(mm, lo);
-        atomicMax(mm + 1, hi);
+        atomicMin(mm, r.lo);
+        atomicMax(mm + 1, r.hi);
     }
 }
 

@@ -52,8 +52,7 @@ __global__ __launch_bounds__(256) void k_wm_sort_regions(const float* __restrict
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     // every XCD takes a contiguous run of (slice group, block) pairs: neighbouring blocks' regions overlap (22 of 8 columns /
     // rows) and share 128-byte lines of the cost plane, which then come from HBM once
-    const int nwg = gridDim.x * gridDim.y, lin = blockIdx.x + gridDim.x * blockIdx.y;
-    const int xcd = lin & 7, vid = xcd * (nwg >> 3) + min(xcd, nwg & 7) + (lin >> 3);
+    const int vid = xcd_contiguous(gridDim.x * gridDim.y, blockIdx.x + gridDim.x * blockIdx.y);
     const int dd = (vid / (int)gridDim.x) * 4 + wv;
     if (dd >= d_count) return;  // whole wavefront
     const int blk = vid % (int)gridDim.x, by = blk / nbx, bx = blk - by * nbx;
@@ -93,40 +92,6 @@ __global__ __launch_bounds__(256) void k_wm_sort_regions(const float* __restrict
 }
 
 // ---- 2. every pixel of the block walks the sorted region -------------------------------------------------------------------
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ double dpp_f64(double v)  // lanes without a source (row edge, masked rows) read 0
-{
-    const long long b = __double_as_longlong(v);
-    int lo, hi;
-    if constexpr (ROWMASK == 0xf) {  // shifts inside a row: bound_ctrl supplies the zeros, no 'old' operand to initialise
-        lo = __builtin_amdgcn_mov_dpp((int)(uint32_t)b, CTRL, 0xf, 0xf, true);
-        hi = __builtin_amdgcn_mov_dpp((int)(uint32_t)((unsigned long long)b >> 32), CTRL, 0xf, 0xf, true);
-    } else {                         // row broadcasts into some rows only: the other rows keep old = 0
-        lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)b, CTRL, ROWMASK, 0xf, false);
-        hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)((unsigned long long)b >> 32), CTRL, ROWMASK, 0xf, false);
-    }
-    return __longlong_as_double((long long)(((unsigned long long)(uint32_t)hi << 32) | (uint32_t)lo));
-}
-
-__device__ __forceinline__ double wave_inclusive_scan(double v)
-{
-    v += dpp_f64<0x111, 0xf>(v);  // row_shr:1
-    v += dpp_f64<0x112, 0xf>(v);  // row_shr:2
-    v += dpp_f64<0x114, 0xf>(v);  // row_shr:4
-    v += dpp_f64<0x118, 0xf>(v);  // row_shr:8   -> inclusive inside each row of 16
-    v += dpp_f64<0x142, 0xa>(v);  // row_bcast:15 into rows 1 and 3
-    v += dpp_f64<0x143, 0xc>(v);  // row_bcast:31 into rows 2 and 3
-    return v;
-}
-
-__device__ __forceinline__ double readlane_f64(double v, int l)
-{
-    const long long b = __double_as_longlong(v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, l);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((unsigned long long)b >> 32), l);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
 // a[r] of lane l for wave-uniform r and l: a branch tree on the scalar unit and two v_readlane, instead of a chain of
 // v_cndmask (each with its s_cmp / s_cselect) over all N registers
 template <int N>
@@ -141,17 +106,6 @@ __device__ __forceinline__ uint32_t pick_reg(const uint32_t (&a)[N], int r, int 
     if (r < 6) return r == 4 ? ASW_RL(4) : ASW_RL(5);
     return r == 6 ? ASW_RL(6) : ASW_RL(7);
 #undef ASW_RL
-}
-
-__device__ __forceinline__ int wave_inclusive_scan(int v)
-{
-    v += __builtin_amdgcn_mov_dpp(v, 0x111, 0xf, 0xf, true);
-    v += __builtin_amdgcn_mov_dpp(v, 0x112, 0xf, 0xf, true);
-    v += __builtin_amdgcn_mov_dpp(v, 0x114, 0xf, 0xf, true);
-    v += __builtin_amdgcn_mov_dpp(v, 0x118, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
-    return v;
 }
 
 // grid blocks * NSPLIT (one dimension, see the mapping below), 512 threads: wavefront w takes the slices d_begin + w, w + 8, ... and, for each, the 64 / NSPLIT pixels
@@ -184,8 +138,7 @@ __global__ __launch_bounds__(64 * PICK_WAVES) void k_wm_pick(const float* __rest
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     // one-dimensional grid of (block, part) pairs; every XCD takes a contiguous run of them, so the parts of a block -- which
     // read the same sorted lists -- run on one XCD at about the same time and the lists come from HBM once, not once per part
-    const int nwg = gridDim.x, lin = blockIdx.x;
-    const int xcd = lin & 7, vid = xcd * (nwg >> 3) + min(xcd, nwg & 7) + (lin >> 3);
+    const int vid = xcd_contiguous(gridDim.x, blockIdx.x);
     const int blk = vid / NSPLIT, part = vid - blk * NSPLIT;
     const int by = blk / nbx, bx = blk - by * nbx;
     const int x0 = bx * BW, y0 = by * BH;
@@ -243,18 +196,14 @@ __global__ __launch_bounds__(64 * PICK_WAVES) void k_wm_pick(const float* __rest
                 if (keep[r]) cb[o] = ((uint32_t)(lane * KPL + r) << 16) | (uint32_t)pos[r];
                 o += keep[r] ? 1 : 0;
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
 #pragma unroll
             for (int i = 0; i < KE; i++) {
                 const uint32_t e = cb[lane * KE + i];
                 epos[i] = 4 * (int)(e & 0xffffu);  // four times the position: the byte offset into the layout needs no shift per pixel
                 eslot[i] = e >> 16;
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
             for (int i = lane; i < 64 * KE; i += 64) wrp[i] = -0.0f;  // the borrowed part of the layout: "not a member" again
         } else {
 #pragma unroll
@@ -287,10 +236,8 @@ __global__ __launch_bounds__(64 * PICK_WAVES) void k_wm_pick(const float* __rest
             for (int k = 0; k < 4; k++)
                 if (lane + 64 * k < NC) *reinterpret_cast<float*>(wq + coff[k]) = wl_row[lane + 64 * k] * nxt[k];
             if (todo) fetch(p_begin + __builtin_ctzll(todo));  // the next pixel's row: in flight under this pixel's arithmetic
-            // LDS operations of a wavefront execute in order; the compiler is told that other lanes read these words
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            // other lanes gather from these words
+            wave_lds_sync();
 
             const int base4 = 4 * ((p >> 3) * PS + (p & 7) - HW);
             const char* wqe = wq + 4 * ROW0 - base4;  // COMPACT: wave-uniform, so a gather address is one addition
@@ -310,9 +257,7 @@ __global__ __launch_bounds__(64 * PICK_WAVES) void k_wm_pick(const float* __rest
                 mb = (mb << 1) | (__float_as_uint(w) != 0x80000000u ? 1u : 0u);
             }
             // the next pixel's weights overwrite the layout: behind this pixel's gathers
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
             const double incl = wave_inclusive_scan(run);
             const double half = readlane_f64(incl, 63) * 0.5;  // cv::sum(weight_img_win)[0] / 2, M.cpp:3284
             // first entry whose prefix (exclusive prefix of the lane + local prefix) exceeds half: compared as
@@ -325,20 +270,8 @@ __global__ __launch_bounds__(64 * PICK_WAVES) void k_wm_pick(const float* __rest
             const unsigned long long ball = __ballot(first < KE);
             float res = 0.0f;
             if (ball) {  // wave-uniform
-                const int fl = __ffsll((long long)ball) - 1;
-                const int fr = __builtin_amdgcn_readlane(first, fl);
-                const uint32_t bits = (uint32_t)__builtin_amdgcn_readlane((int)mb, fl);
-                const uint32_t before = bits >> (KE - fr);  // members among entries 0 .. fr-1 of that lane, entry fr-1 at bit 0
-                int pl = fl, pr = fr;  // the crossing element itself if nothing precedes it (M.cpp:3293-3296)
-                if (before) {
-                    pr = fr - 1 - __builtin_ctz(before);
-                } else {
-                    const unsigned long long lower = __ballot(mb != 0u) & ((1ull << fl) - 1ull);
-                    if (lower) {
-                        pl = 63 - __builtin_clzll(lower);
-                        pr = KE - 1 - __builtin_ctz((uint32_t)__builtin_amdgcn_readlane((int)mb, pl));  // its last member
-                    }
-                }
+                int pl, pr;
+                last_member_before<KE, false>(ball, first, mb, pl, pr);
                 if constexpr (COMPACT) {  // (pl, pr) addresses the compacted list: back to the slot that holds the cost
                     const int slot = (int)pick_reg(eslot, pr, pl);
                     pl = slot >> 3;

@@ -38,8 +38,7 @@ __global__ __launch_bounds__(256) void k_wmg_sort(const float* __restrict__ cost
     constexpr int SLOTS = 64 * KPL;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     // every XCD takes a contiguous run of (slice group, block) pairs: neighbouring regions overlap and share lines of the cost plane
-    const int nwg = gridDim.x * gridDim.y, lin = blockIdx.x + gridDim.x * blockIdx.y;
-    const int xcd = lin & 7, vid = xcd * (nwg >> 3) + min(xcd, nwg & 7) + (lin >> 3);
+    const int vid = xcd_contiguous(gridDim.x * gridDim.y, blockIdx.x + gridDim.x * blockIdx.y);
     const int dd = (vid / (int)gridDim.x) * 4 + wv;
     if (dd >= d_count) return;  // whole wavefront
     const int hw = win / 2, RW = BW + win - 1, nreg = RW * (BH + win - 1);
@@ -88,40 +87,6 @@ __global__ __launch_bounds__(256) void k_wmg_sort(const float* __restrict__ cost
 }
 
 // ---- 2. every pixel of a part walks the sorted region ----------------------------------------------------------------------
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ double dpp_f64(double v)  // lanes without a source (row edge, masked rows) read 0
-{
-    const long long b = __double_as_longlong(v);
-    int lo, hi;
-    if constexpr (ROWMASK == 0xf) {
-        lo = __builtin_amdgcn_mov_dpp((int)(uint32_t)b, CTRL, 0xf, 0xf, true);
-        hi = __builtin_amdgcn_mov_dpp((int)(uint32_t)((unsigned long long)b >> 32), CTRL, 0xf, 0xf, true);
-    } else {
-        lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)b, CTRL, ROWMASK, 0xf, false);
-        hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)((unsigned long long)b >> 32), CTRL, ROWMASK, 0xf, false);
-    }
-    return __longlong_as_double((long long)(((unsigned long long)(uint32_t)hi << 32) | (uint32_t)lo));
-}
-
-__device__ __forceinline__ double wave_inclusive_scan(double v)
-{
-    v += dpp_f64<0x111, 0xf>(v);  // row_shr:1
-    v += dpp_f64<0x112, 0xf>(v);  // row_shr:2
-    v += dpp_f64<0x114, 0xf>(v);  // row_shr:4
-    v += dpp_f64<0x118, 0xf>(v);  // row_shr:8   -> inclusive inside each row of 16
-    v += dpp_f64<0x142, 0xa>(v);  // row_bcast:15 into rows 1 and 3
-    v += dpp_f64<0x143, 0xc>(v);  // row_bcast:31 into rows 2 and 3
-    return v;
-}
-
-__device__ __forceinline__ double readlane_f64(double v, int l)
-{
-    const long long b = __double_as_longlong(v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, l);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((unsigned long long)b >> 32), l);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
 // grid: nblocks * nparts workgroups of NW wavefronts (one dimension; the parts of a block are consecutive in an XCD's order).
 // A part = rpp rows of the 8x8 block; wavefront w takes the slices d_begin + w, w + NW, ... of the chunk.
 // LDS (dynamic): float sWL[8 * rpp][wls] | float sWR[NW][wls] | u16 sT[win * 64 + 1]   (wls = win^2 + 1 rounded up to 4, slot
@@ -141,8 +106,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE, 8)
     uint16_t* sT = reinterpret_cast<uint16_t*>(sWR + (size_t)NW * wls);
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     // every XCD takes a contiguous run of (block, part) pairs: the parts of a block read the same lists at about the same time
-    const int nwg = gridDim.x, lin = blockIdx.x;
-    const int xcd = lin & 7, vid = xcd * (nwg >> 3) + min(xcd, nwg & 7) + (lin >> 3);
+    const int vid = xcd_contiguous(gridDim.x, blockIdx.x);
     const int blk = vid / nparts, part = vid - blk * nparts;
     const int by = blk / nbx, bx = blk - by * nbx;
     const int x0 = bx * BW, y0 = by * BH;
@@ -212,10 +176,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE, 8)
             for (int k = 0; k < NCI; k++)
                 if (lane + 64 * k < NC) wrp[lane + 64 * k] = wl_row[lane + 64 * k] * nxt[k];
             if (todo) fetch(p_begin + __builtin_ctzll(todo));  // the next pixel's row: in flight under this pixel's arithmetic
-            // LDS operations of a wavefront execute in order; the compiler must know that other lanes read these words
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            // other lanes gather from these words
+            wave_lds_sync();
 
             const char* wq = reinterpret_cast<const char*>(wrp);
             const int base2 = 2 * ((p >> 3) * 64 + (p & 7) - (BW - 1));
@@ -240,27 +202,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(WPE, 8)
             const unsigned long long ball = __ballot(first < KPL);
             int slot = -1;
             if (ball) {  // wave-uniform
-                const int fl = __ffsll((long long)ball) - 1;
-                const int fr = __builtin_amdgcn_readlane(first, fl);
-                const uint32_t bits = (uint32_t)__builtin_amdgcn_readlane((int)mb, fl);
-                const uint32_t before = fr ? bits >> (KPL - fr) : 0u;  // members among entries 0 .. fr-1 of that lane, entry fr-1 at bit 0
-                int pl = fl, pr = fr;  // the crossing element itself if nothing precedes it (M.cpp:3293-3296)
-                if (before) {
-                    pr = fr - 1 - __builtin_ctz(before);
-                } else {
-                    const unsigned long long lower = __ballot(mb != 0u) & ((1ull << fl) - 1ull);
-                    if (lower) {
-                        pl = 63 - __builtin_clzll(lower);
-                        pr = KPL - 1 - __builtin_ctz((uint32_t)__builtin_amdgcn_readlane((int)mb, pl));  // its last member
-                    }
-                }
+                int pl, pr;
+                last_member_before<KPL, true>(ball, first, mb, pl, pr);
                 slot = pl * KPL + pr;
             }
             if (lane == q) my_slot = slot;
             // the next pixel's weights overwrite this wavefront's row: behind this pixel's gathers
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
         }
         // results of the whole part at once: the cost of slot my_slot (no crossing at all -- an all-zero total -- gives 0)
         if (lane < npart && ((vmask >> lane) & 1ull)) {

@@ -1,4 +1,5 @@
-// Stable in-wavefront sorting network shared by the weighted-median kernels (k_wmedian.hip, k_wmedian_tile.hip).
+// Stable in-wavefront sorting network shared by the weighted-median kernels (k_wmedian.hip, k_wmedian_tile.hip,
+// k_wmedian_tile_gen.hip), and the tile kernels' selection of the median in a sorted list.
 // Keys carry their own tie-break (window / region index in the low bits), so a plain bitonic network sorts stably.
 #pragma once
 #include <stdint.h>
@@ -119,5 +120,31 @@ __device__ __forceinline__ void bitonic_sort(T (&key)[KPL], const LaneMasks& lm)
     merge_sorted_halves<K>(key, lm);
 }
 
+// The weighted median in a list held in sorted order, N entries per lane (entry = lane * N + r).  `first`: this lane's first
+// entry whose prefix sum exceeds half of the total (N: none), `ball` = __ballot(first < N), not 0; `mb`: member flags of this
+// lane's entries, entry r at bit N - 1 - r.  The result (lane pl, entry pr) is the last MEMBER before the crossing element, or
+// the crossing element itself if nothing precedes it (M.cpp:3293-3301).  Wave-uniform.
+// GUARD: test for fr == 0 in front of the shift by N - fr.  Needed where N can be 32 (a shift by 32 is undefined); below that
+// the shift by N is defined and leaves nothing of the N flags, and the 15x15 pickers keep their code without the test.
+template <int N, bool GUARD>
+__device__ __forceinline__ void last_member_before(unsigned long long ball, int first, uint32_t mb, int& pl, int& pr)
+{
+    static_assert(GUARD || N < 32, "");
+    const int fl = __ffsll((long long)ball) - 1;
+    const int fr = __builtin_amdgcn_readlane(first, fl);
+    const uint32_t bits = (uint32_t)__builtin_amdgcn_readlane((int)mb, fl);
+    const uint32_t before = (!GUARD || fr) ? bits >> (N - fr) : 0u;  // members among entries 0 .. fr-1 of that lane, entry fr-1 at bit 0
+    pl = fl;
+    pr = fr;
+    if (before) {
+        pr = fr - 1 - __builtin_ctz(before);
+    } else {
+        const unsigned long long lower = __ballot(mb != 0u) & ((1ull << fl) - 1ull);
+        if (lower) {
+            pl = 63 - __builtin_clzll(lower);
+            pr = N - 1 - __builtin_ctz((uint32_t)__builtin_amdgcn_readlane((int)mb, pl));  // its last member
+        }
+    }
+}
 
 }  // namespace wmnet
