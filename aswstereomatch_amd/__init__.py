@@ -32,6 +32,7 @@ __all__ = [
     "SGBM_PATH_LR", "SGBM_PATH_RL", "SGBM_PATH_TB", "SGBM_PATH_BT", "SGBM_PATH_TLBR", "SGBM_PATH_TRBL", "SGBM_PATH_BRTL",
     "SGBM_PATH_BLTR", "SGBM_PATHS_3WAY", "SGBM_PATHS_HH4", "SGBM_PATHS_SGBM", "SGBM_PATHS_HH",
     "cross_algorithm", "computeAdaptiveWeight_cross",
+    "adcensus_algorithm", "computeCensus", "computeADCensus", "computeAdaptiveWeight_adcensus",
     "AswError",
 ]
 
@@ -82,6 +83,21 @@ def cross_algorithm(tau=20, trunc=20):
     tau, trunc = int(tau), int(trunc)
     bad = 0x01000000 if (tau < 0 or tau > 255 or trunc < 1 or trunc > 255) else 0
     return _ALG_CROSS_PARAMS | bad | ((trunc & 0xFF) << 16) | ((tau & 0xFF) << 8) | int(StereoMatchingAlgorithms.ADAPTIVE_WEIGHT_CROSS)
+
+
+_ALG_ADCENSUS_PARAMS = 0x20000000  # ASW_ALG_ADCENSUS_PARAMS
+_COST_CENSUS_PARAMS = 0x40000000  # ASW_COST_CENSUS_PARAMS: asw_cost_tad's threshold carrying the census cost builders, as the header's inline asw_cost_census / asw_cost_adcensus form it
+
+
+def adcensus_algorithm(tau=20, lambda_ad=10, lambda_census=30):
+    """asw_alg_adcensus of asw_mi355x.h: the value of `algorithmType` that runs AD-Census matching -- entry
+    12's cross-based aggregation over the census + AD cost -- with colour threshold tau (0..255) and the table constants lambda_ad
+    (1..31) and lambda_census (1..255) in every call that takes an algorithm; an argument out of range gives a value the library
+    refuses with ERR_BAD_ARGUMENT (lambda_ad field 0)."""
+    tau, lambda_ad, lambda_census = int(tau), int(lambda_ad), int(lambda_census)
+    bad = tau < 0 or tau > 255 or lambda_ad < 1 or lambda_ad > 31 or lambda_census < 1 or lambda_census > 255
+    return (_ALG_ADCENSUS_PARAMS | ((0 if bad else lambda_ad) << 24) | ((lambda_census & 0xFF) << 16) | ((tau & 0xFF) << 8) |
+            int(StereoMatchingAlgorithms.ADAPTIVE_WEIGHT_CROSS))
 
 
 PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL = 0, 1  # StereoBM::PREFILTER_*; asw_stereo_bm serves XSOBEL
@@ -285,6 +301,17 @@ class Context:
         return self._aggregate("asw_aggregate_cross", _A.ADAPTIVE_WEIGHT_CROSS, numDisparity, leftImg, rightImg, (), return_cost_volume,
                                fn=call)
 
+    def computeAdaptiveWeight_adcensus(self, leftImg, rightImg, dispType=DISPARITY_LEFT, tau=20, lambda_ad=10, lambda_census=30,
+                                       winSize=15, minDisparity=0, numDisparity=64, return_cost_volume=False):
+        """AD-Census matching (asw_aggregate_adcensus; not in the reference): the census + AD cost of
+        computeADCensus summed over every pixel's cross-shaped region, exact integers and one f32 division; 1- or 3-channel pairs."""
+        alg = adcensus_algorithm(tau, lambda_ad, lambda_census)
+
+        def call(h, l, r, d, *args):
+            return self._lib.asw_stereo_match(h, l, r, d, int(dispType), alg, winSize, minDisparity, numDisparity, *args)
+        return self._aggregate("asw_aggregate_adcensus", _A.ADAPTIVE_WEIGHT_CROSS, numDisparity, leftImg, rightImg, (),
+                               return_cost_volume, fn=call)
+
     # ---- semi-global block matching (DESIGN.md section 4.8) ----
     def getDisparity_SGBM(self, srcLeft, srcRight, winSize=15, minDisparity=0, numDisparity=64):
         """getDisparity_SGBM (M.h:94, aswMethods.cpp:158-194): StereoSGBM with the reference's settings -> uint8 map
@@ -385,6 +412,21 @@ class Context:
         a = np.asarray(leftImg)
         return self._cost(self._lib.asw_cost_ad, "asw_cost_ad", leftImg, rightImg, np.uint8, a.shape[:2], numDisparity,
                           (int(dispType), minDisparity, numDisparity))
+
+    def computeCensus(self, leftImg, rightImg, dispType=DISPARITY_LEFT, minDisparity=0, numDisparity=30):
+        """asw_cost_census: the Hamming distance (0..62) of the 9 x 7 census codes of the gray pair, uint8 planes like computeAD's."""
+        a = np.asarray(leftImg)
+        return self._cost(self._lib.asw_cost_tad, "asw_cost_census", leftImg, rightImg, np.uint8, a.shape[:2], numDisparity,
+                          (int(dispType), _COST_CENSUS_PARAMS, minDisparity, numDisparity))
+
+    def computeADCensus(self, leftImg, rightImg, dispType=DISPARITY_LEFT, lambda_ad=10, lambda_census=30, minDisparity=0,
+                        numDisparity=30):
+        """asw_cost_adcensus: TA[AD] + TC[Hamming] (0..254), the raw cost of AD-Census matching; both lambdas in 1..255."""
+        a = np.asarray(leftImg)
+        la, lc = int(lambda_ad), int(lambda_census)
+        bad = 0x10000 if (la < 1 or la > 255 or lc < 1 or lc > 255) else 0
+        return self._cost(self._lib.asw_cost_tad, "asw_cost_adcensus", leftImg, rightImg, np.uint8, a.shape[:2], numDisparity,
+                          (int(dispType), _COST_CENSUS_PARAMS | bad | ((la & 0xFF) << 8) | (lc & 0xFF), minDisparity, numDisparity))
 
     def computeTAD(self, leftImg, rightImg, dispType=DISPARITY_LEFT, threshold_T=30, minDisparity=0, numDisparity=30):
         a = np.asarray(leftImg)
@@ -663,6 +705,9 @@ computeAdaptiveWeight_GuidedF_2 = _bind("computeAdaptiveWeight_GuidedF_2")
 computeAdaptiveWeight_WeightedMedian = _bind("computeAdaptiveWeight_WeightedMedian")
 computeAdaptiveWeight_BLO1 = _bind("computeAdaptiveWeight_BLO1")
 computeAdaptiveWeight_cross = _bind("computeAdaptiveWeight_cross")
+computeCensus = _bind("computeCensus")
+computeADCensus = _bind("computeADCensus")
+computeAdaptiveWeight_adcensus = _bind("computeAdaptiveWeight_adcensus")
 winnerTakeAll = _bind("winnerTakeAll")
 getDisparity_SGBM = _bind("getDisparity_SGBM")
 sgbm = _bind("sgbm")

@@ -37,23 +37,28 @@ int match_host(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_
     return ASW_OK;
 }
 
-int decode_algorithm(int algorithm, int* method, int* tau, int* trunc)
+int decode_algorithm(int algorithm, int* method, MatchParams* mp)
 {
     *method = algorithm;
-    if (!(algorithm & ASW_ALG_CROSS_PARAMS)) return ASW_OK;
+    if (!(algorithm & (ASW_ALG_CROSS_PARAMS | ASW_ALG_ADCENSUS_PARAMS))) return ASW_OK;
     const MethodInfo* m = method_info(algorithm & 0xFF);
     if (!m || !m->packed_params) return ASW_ERR_UNSUPPORTED_METHOD;
-    const int t = (algorithm >> 16) & 0xFF;
-    if (t == 0 || (algorithm & 0x3F000000) || algorithm < 0) return ASW_ERR_BAD_ARGUMENT;  // bits 24..29 and 31 stay clear
+    const int tau = (algorithm >> 8) & 0xFF, f16 = (algorithm >> 16) & 0xFF;
+    if (algorithm & ASW_ALG_CROSS_PARAMS) {  // asw_alg_cross(): bits 16..23 = trunc, bits 24..29 and 31 stay clear
+        if (f16 == 0 || (algorithm & 0x3F000000) || algorithm < 0) return ASW_ERR_BAD_ARGUMENT;
+        if (mp) { mp->cross_tau = tau; mp->cross_trunc = f16; }
+    } else {  // asw_alg_adcensus(): bits 16..23 = lambda_census, bits 24..28 = lambda_ad, bit 31 stays clear
+        const int lambda_ad = (algorithm >> 24) & 0x1F;
+        if (f16 == 0 || lambda_ad == 0 || algorithm < 0) return ASW_ERR_BAD_ARGUMENT;
+        if (mp) { mp->cross_cost = 1; mp->cross_tau = tau; mp->cross_trunc = 255; mp->lambda_ad = lambda_ad; mp->lambda_census = f16; }
+    }
     *method = m->algorithm;
-    if (tau) *tau = (algorithm >> 8) & 0xFF;
-    if (trunc) *trunc = t;
     return ASW_OK;
 }
 
 extern "C" int asw_volume_planes(int algorithm, int num_disparity)
 {
-    if (decode_algorithm(algorithm, &algorithm, nullptr, nullptr) != ASW_OK) return 0;
+    if (decode_algorithm(algorithm, &algorithm, nullptr) != ASW_OK) return 0;
     const MethodInfo* m = method_info(algorithm);
     return m ? m->planes(num_disparity) : 0;
 }
@@ -130,9 +135,34 @@ extern "C" int asw_cost_ad(asw_ctx* ctx, const asw_image* left, const asw_image*
     return cost_ad_common(ctx, left, right, cost, disparity_type, 0, 0, min_disparity, num_disparity);
 }
 
+// asw_cost_census (lambda_ad = 0: the Hamming distance alone) and asw_cost_adcensus, the header's inline forms over asw_cost_tad
+static int cost_census_common(asw_ctx* ctx, const asw_image* left, const asw_image* right, uint8_t* cost, int disparity_type,
+                              int lambda_ad, int lambda_census, int minD, int numD)
+{
+    if (!ctx || !cost) return ASW_ERR_BAD_ARGUMENT;
+    ASW_TRY(check_pair(left, right));
+    if (numD <= 0 || minD < 0) return ASW_ERR_BAD_ARGUMENT;
+    if (left->channels != 1 && left->channels != 3) return ASW_ERR_UNSUPPORTED_LAYOUT;
+    if (disparity_type != ASW_DISPARITY_LEFT && disparity_type != ASW_DISPARITY_RIGHT) return ASW_ERR_BAD_ARGUMENT;
+    ASW_HIP_TRY(hipSetDevice(ctx->device));
+    const int H = left->rows, W = left->cols;
+    const uint8_t *dl, *dr;
+    DevBuf& dc = ctx->buf("cost_u8");
+    ASW_TRY(upload_stage_pair(ctx, left, right, &dl, &dr));
+    const size_t bytes = (size_t)numD * H * W;
+    ASW_TRY(dc.ensure(bytes));
+    ASW_TRY(build_census_cost(ctx, dl, dr, H, W, left->channels, disparity_type, minD, numD, lambda_ad, lambda_census, dc.as<uint8_t>()));
+    return download_sync(ctx, cost, dc.p, bytes);
+}
+
 extern "C" int asw_cost_tad(asw_ctx* ctx, const asw_image* left, const asw_image* right, uint8_t* cost,
                             int disparity_type, int threshold_t, int min_disparity, int num_disparity)
 {
+    if (threshold_t >= ASW_COST_CENSUS_PARAMS) {  // asw_cost_census / asw_cost_adcensus: bits 8..15 = lambda_ad, 0..7 = lambda_census
+        const int la = (threshold_t >> 8) & 0xFF, lc = threshold_t & 0xFF;
+        if ((threshold_t & 0x3FFF0000) || (la == 0) != (lc == 0)) return ASW_ERR_BAD_ARGUMENT;
+        return cost_census_common(ctx, left, right, cost, disparity_type, la, lc, min_disparity, num_disparity);
+    }
     return cost_ad_common(ctx, left, right, cost, disparity_type, 1, threshold_t, min_disparity, num_disparity);
 }
 

@@ -121,5 +121,14 @@ __device__ __forceinline__ float lut_at(const float* __restrict__ lut, unsigned 
     return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(lut) + (idx << 2));
 }
 
+// u8 MatExpr (c0+c1+c2)/3 == round((min(255,c0+c1)+c2)/3): no exact .5 can occur, so the
+// integer form floor((s+1)/3) is identical to OpenCV's float addWeighted + cvRound (App. A-4;
+// tests/test_oracle_kat.py::test_ad_float_formula_equals_integer_rule).  The AD value of k_cost_ad and k_cost_census.
+__device__ __forceinline__ uint32_t mean3_u8(int c0, int c1, int c2)
+{
+    int t = min(255, c0 + c1);
+    return (uint32_t)((t + c2 + 1) / 3);
+}
+
 // colour distance of two packed BGRX pixels: |db| + |dg| + |dr| in one v_sad_u8
 __device__ __forceinline__ uint32_t cdist(uint32_t a, uint32_t b) { return __builtin_amdgcn_sad_u8(a, b, 0u); }

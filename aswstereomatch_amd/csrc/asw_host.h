@@ -38,6 +38,8 @@ struct MatchParams {
     double blo_rate_r = 0.015;          // M.cpp:70
     double grid_rate_s = 10, grid_rate_r = 10;  // M.cpp:67
     int cross_tau = 20, cross_trunc = 20;       // ASW_ALG_ADAPTIVE_WEIGHT_CROSS; an encoded selector value replaces them
+    int cross_cost = 0;                         // the cost entry 12 aggregates: 0 = truncated AD, 1 = AD-Census (asw_alg_adcensus())
+    int lambda_ad = 10, lambda_census = 30;     // AD-Census: the two table constants
 };
 inline MatchParams match_params(int disparity_type, int win, int minD, int numD)
 {
@@ -56,15 +58,20 @@ struct MethodInfo {
     bool no_volume;               // no selector volume (0 planes), hence no sub-pixel step and no refinement either
     bool ignores_disparity_type;  // whatever disparity_type holds, sub-pixel flags included, is not looked at
     bool no_subpixel;             // a sub-pixel flag is refused with ASW_ERR_UNSUPPORTED_METHOD
-    bool packed_params;           // the selector value may carry the method's parameters (ASW_ALG_CROSS_PARAMS, asw_alg_cross())
+    bool packed_params;           // the selector value may carry the method's parameters (asw_alg_cross(), asw_alg_adcensus())
     int planes(int numD) const { return no_volume ? 0 : numD + extra_planes; }
 };
 const MethodInfo* method_info(int method);  // the row of a plain (decoded) selector value; null for a value outside the table
 
-// The selector's `algorithm` as a caller passes it -> the plain enum value in *method and, for an asw_alg_cross() value, its
-// parameters in *tau / *trunc (left alone otherwise; either may be null).  ASW_ERR_UNSUPPORTED_METHOD / ASW_ERR_BAD_ARGUMENT for the
-// encodings asw_mi355x.h refuses; a value without ASW_ALG_CROSS_PARAMS passes through as it is.
-int decode_algorithm(int algorithm, int* method, int* tau, int* trunc);
+// The selector's `algorithm` as a caller passes it -> the plain enum value in *method and, for an asw_alg_cross() or
+// asw_alg_adcensus() value, its parameters in mp's cross_* / lambda_* fields (left alone otherwise; mp may be null).
+// ASW_ERR_UNSUPPORTED_METHOD / ASW_ERR_BAD_ARGUMENT for the encodings asw_mi355x.h refuses; a value with neither
+// ASW_ALG_CROSS_PARAMS nor ASW_ALG_ADCENSUS_PARAMS passes through as it is.
+int decode_algorithm(int algorithm, int* method, MatchParams* mp);
+// AD-Census cost of a device pair into cost u8 [numD][H][W]: gray pair, two census transforms, then the
+// Hamming distance alone (lambda_ad = 0) or TA[AD] + TC[Hamming] with the tables of the two lambdas (each 1..255)
+int build_census_cost(asw_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int H, int W, int channels, int disparity_type, int minD,
+                      int numD, int lambda_ad, int lambda_census, uint8_t* cost);
 
 int check_u8_image(const asw_image* im);
 int check_pair(const asw_image* L, const asw_image* R);

@@ -98,6 +98,7 @@ struct asw_ctx {
     std::map<std::string, DevBuf> scratch;  // named grow-only scratch buffers
     BilateralTables bil;
     RefineTables refine;
+    int census_lambda_ad = 0, census_lambda_census = 0;  // what buf("census_tables") holds (asw_methods.hip: ensure_census_tables)
     // weighted-median tables: exp() LUT of the colour weight per rateR, space kernel per (win, rateS)
     DevBuf wm_lut2, wm_wd;
     double wm_rate_r = -1, wm_rate_s = -1;
@@ -294,9 +295,18 @@ int launch_bilgrid(hipStream_t s, const uint8_t* gl, const uint8_t* gr, int H, i
 // ---- cross-based support regions (k_cross.hip), DESIGN.md section 4.12 ----
 // arms [H][W]: left | right << 8 | up << 16 | down << 24 of the view image (C = 1 or 3 channels), cnt [H][W]: the region size N
 int launch_cross_arms(hipStream_t s, const uint8_t* img, int H, int W, int C, int win, int tau, uint32_t* arms, uint16_t* cnt);
-// cost: the u8 AD volume [numD][H][W] of launch_cost_ad; vol (optional) [numD][H][W]; disp [H][W]: WTA, strict '<' in ascending d
+// cost: a u8 cost volume [numD][H][W]; vol (optional) [numD][H][W]; disp [H][W]: WTA, strict '<' in ascending d
 int launch_cross_aggregate(hipStream_t s, const uint8_t* cost, const uint32_t* arms, const uint16_t* cnt, int H, int W, int win,
                            int trunc, int minD, int numD, float* vol, float* disp);
+
+// ---- census cost (k_census.hip), DESIGN.md section 4.13 ----
+// gray [H][W] -> code [H][W]: the 62-bit census code of the 9 x 7 window, borders clamped; H <= 16 * 65535
+int launch_census_transform(hipStream_t s, const uint8_t* gray, int H, int W, uint2* code);
+// cost u8 [numD][H][W].  tables == nullptr: the Hamming distance of the two codes (0..62; L, R and C are not looked at);
+// else tables = TA[256] | TC[64] (u8, each entry <= 127) and the cost is TA[AD of launch_cost_ad for L, R, C] + TC[Hamming].
+// The staged rows must fit 160 KB of LDS, else ASW_ERR_BAD_ARGUMENT: W <= 10240 (Hamming), 9084 (C = 1), 7432 (C = 3).
+int launch_cost_census(hipStream_t s, const uint8_t* L, const uint8_t* R, const uint2* codeL, const uint2* codeR, int H, int W, int C,
+                       int disp_type, int minD, int numD, const uint8_t* tables, uint8_t* cost);
 
 // ---- hooks for the batch scheduler (batch.hip) ----
 int asw_internal_stage_slot(asw_ctx* ctx, int slot, int rows, int cols, int channels, Frame** out);

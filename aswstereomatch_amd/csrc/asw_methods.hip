@@ -774,6 +774,43 @@ int bm_prepare(asw_ctx* ctx, const BmParams& p, int H, int W, BmLaunch* out)
 }
 
 // ------------------------------------------------------------------------------------------
+// AD-Census cost (Mei et al. 2011): DESIGN.md section 4.13; not in the reference
+// ------------------------------------------------------------------------------------------
+// TA[v] = floor(127 (1 - exp(-v / lambda_ad)) + 0.5), v = 0..255, and TC[h] the same with lambda_census, h = 0..62, in
+// buf("census_tables") as TA[256] | TC[64]
+static int ensure_census_tables(asw_ctx* ctx, int lambda_ad, int lambda_census)
+{
+    DevBuf& t = ctx->buf("census_tables");
+    if (t.p && ctx->census_lambda_ad == lambda_ad && ctx->census_lambda_census == lambda_census) return ASW_OK;
+    ctx->census_lambda_ad = 0;
+    uint8_t tab[320] = {0};
+    for (int v = 0; v < 256; v++) tab[v] = (uint8_t)floor(127.0 * (1.0 - exp(-(double)v / lambda_ad)) + 0.5);
+    for (int h = 0; h < 63; h++) tab[256 + h] = (uint8_t)floor(127.0 * (1.0 - exp(-(double)h / lambda_census)) + 0.5);
+    ASW_TRY(t.ensure(sizeof(tab)));
+    ASW_HIP_TRY(hipMemcpyAsync(t.p, tab, sizeof(tab), hipMemcpyHostToDevice, ctx->stream));
+    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));  // the host array dies at return
+    ctx->census_lambda_ad = lambda_ad; ctx->census_lambda_census = lambda_census;
+    return ASW_OK;
+}
+
+int build_census_cost(asw_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int H, int W, int channels, int disparity_type, int minD,
+                      int numD, int lambda_ad, int lambda_census, uint8_t* cost)
+{
+    const size_t plane = (size_t)H * W;
+    DevBuf& cl = ctx->buf("censusL");
+    DevBuf& cr = ctx->buf("censusR");
+    ASW_TRY(cl.ensure(plane * sizeof(uint2)));
+    ASW_TRY(cr.ensure(plane * sizeof(uint2)));
+    if (lambda_ad > 0) ASW_TRY(ensure_census_tables(ctx, lambda_ad, lambda_census));
+    const uint8_t *gl, *gr;
+    ASW_TRY(gray_pair(ctx, dL, dR, channels, H, W, &gl, &gr));
+    ASW_TRY(launch_census_transform(ctx->stream, gl, H, W, cl.as<uint2>()));
+    ASW_TRY(launch_census_transform(ctx->stream, gr, H, W, cr.as<uint2>()));
+    return launch_cost_census(ctx->stream, dL, dR, cl.as<uint2>(), cr.as<uint2>(), H, W, channels, disparity_type, minD, numD,
+                              lambda_ad > 0 ? ctx->buf("census_tables").as<uint8_t>() : nullptr, cost);
+}
+
+// ------------------------------------------------------------------------------------------
 // cross-based support regions (Zhang, Lu, Lafruit 2009): DESIGN.md section 4.12; not in the reference
 // ------------------------------------------------------------------------------------------
 static int run_cross(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_volume)
@@ -789,7 +826,7 @@ static int run_cross(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_vo
     if ((size_t)H * W >= ((size_t)1 << 31)) return ASW_ERR_BAD_ARGUMENT;
     if (H > 4 * 65535) return ASW_ERR_BAD_ARGUMENT;  // the arm kernels put four rows on a workgroup of grid.y
     const size_t plane = (size_t)H * W;
-    DevBuf& raw = ctx->buf("cross_cost");   // u8 AD volume: a quarter of the f32 volume
+    DevBuf& raw = ctx->buf("cross_cost");   // u8 cost volume (AD, or AD-Census): a quarter of the f32 volume
     DevBuf& arms = ctx->buf("cross_arms");
     DevBuf& cnt = ctx->buf("cross_count");
     ASW_TRY(raw.ensure(plane * n));
@@ -798,7 +835,11 @@ static int run_cross(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_vo
     ASW_TRY(ensure_outputs(f, n, keep_volume));
     const uint8_t* dL = f->L.as<uint8_t>();
     const uint8_t* dR = f->R.as<uint8_t>();
-    ASW_TRY(launch_cost_ad(ctx->stream, dL, dR, H, W, f->channels, mp.disparity_type, mp.minD, n, 0, 0, raw.as<uint8_t>()));
+    if (mp.cross_cost == 1)
+        ASW_TRY(build_census_cost(ctx, dL, dR, H, W, f->channels, mp.disparity_type, mp.minD, n, mp.lambda_ad, mp.lambda_census,
+                                  raw.as<uint8_t>()));
+    else
+        ASW_TRY(launch_cost_ad(ctx->stream, dL, dR, H, W, f->channels, mp.disparity_type, mp.minD, n, 0, 0, raw.as<uint8_t>()));
     ASW_TRY(agg_begin(ctx));
     ASW_TRY(launch_cross_arms(ctx->stream, mp.disparity_type == ASW_DISPARITY_RIGHT ? dR : dL, H, W, f->channels, mp.win, mp.cross_tau,
                               arms.as<uint32_t>(), cnt.as<uint16_t>()));
@@ -855,7 +896,7 @@ int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp_in, 
     f->invalidate_results();  // whatever the slot's disparity / volume were, they are not this call's
     MatchParams mp = mp_in;
     if (mp.numD <= 0 || mp.minD < 0) return ASW_ERR_BAD_ARGUMENT;
-    ASW_TRY(decode_algorithm(algorithm, &algorithm, &mp.cross_tau, &mp.cross_trunc));  // asw_alg_cross() values -> 12 + parameters
+    ASW_TRY(decode_algorithm(algorithm, &algorithm, &mp));  // asw_alg_cross() / asw_alg_adcensus() values -> 12 + parameters
     const MethodInfo* m = method_info(algorithm);
     ASW_TRY(decode_subpixel(m, mp));
     // the sub-pixel kernel reads the aggregated volume: the methods that can skip it (bilateral / direct8, geodesic, BLO1, the
@@ -958,8 +999,8 @@ int match_refined(asw_ctx* ctx, Frame* f, int algorithm, int win_size, int min_d
     const MethodInfo* m = method_info(algorithm);
     if (m && m->no_volume) return ASW_ERR_UNSUPPORTED_METHOD;  // SGBM / BM carry their own disp12MaxDiff
     if (num_disparity <= 0 || min_disparity < 0) return ASW_ERR_BAD_ARGUMENT;  // as a plain match (run_method)
-    int plain;  // unused: a bad asw_alg_cross() value is refused here with its own status, as a plain match refuses it
-    ASW_TRY(decode_algorithm(algorithm, &plain, nullptr, nullptr));
+    int plain;  // unused: a bad asw_alg_cross() / asw_alg_adcensus() value is refused here with its own status, as a plain match refuses it
+    ASW_TRY(decode_algorithm(algorithm, &plain, nullptr));
     RefineParams rp;
     rp.minD = min_disparity; rp.n = asw_volume_planes(algorithm, num_disparity); rp.max_diff = max_diff; rp.win = refine_win;
     rp.gamma_c = gamma_c; rp.gamma_s = gamma_s;

@@ -35,15 +35,6 @@ __global__ void k_bgr2gray(const uint8_t* __restrict__ bgr, int n, uint8_t* __re
     }
 }
 
-// u8 MatExpr (c0+c1+c2)/3 == round((min(255,c0+c1)+c2)/3): no exact .5 can occur, so the
-// integer form floor((s+1)/3) is identical to OpenCV's float addWeighted + cvRound (App. A-4;
-// tests/test_oracle_kat.py::test_ad_float_formula_equals_integer_rule).
-__device__ __forceinline__ uint32_t mean3_u8(int c0, int c1, int c2)
-{
-    int t = min(255, c0 + c1);
-    return (uint32_t)((t + c2 + 1) / 3);
-}
-
 // computeAD / computeTAD / computeSD (M.cpp:208-292, 304-401, 670-759).  One block per (row, d-slab); the two image
 // rows are staged in LDS once and every disparity plane of the slab is produced from them.
 // Each thread owns 4 consecutive pixels -> one dword store per plane (256 B per wave-instruction).

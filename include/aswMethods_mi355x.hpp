@@ -385,6 +385,18 @@ inline AswMat computeAdaptiveWeight_cross(AswMat leftImg, AswMat rightImg, Dispa
     }, "computeAdaptiveWeight_cross");
 }
 
+// Not in the reference: AD-Census matching (asw_aggregate_adcensus) -- the census + AD cost under the cross-based
+// aggregation -> the f32 map; empty Mat for an even window
+inline AswMat computeAdaptiveWeight_adcensus(AswMat leftImg, AswMat rightImg, DisparityType dispType = DISPARITY_LEFT, int tau = 20,
+                                             int lambda_ad = 10, int lambda_census = 30, int winSize = 15, int minDisparity = 0,
+                                             int numDisparity = 64)
+{
+    return asw::detail::aggregate(leftImg, rightImg, [&](asw_ctx* c, asw_image* l, asw_image* r, asw_image* o) {
+        return asw_aggregate_adcensus(c, l, r, o, (int)dispType, tau, lambda_ad, lambda_census, winSize, minDisparity, numDisparity, nullptr,
+                                      0);
+    }, "computeAdaptiveWeight_adcensus");
+}
+
 // Not in the reference: the cross-check that consumes a DISPARITY_LEFT and a DISPARITY_RIGHT map (asw_lr_check)
 inline AswMat leftRightCheck(AswMat dispLeft, AswMat dispRight, float maxDiff = 1.0f, float invalidValue = -1.0f, int* nInvalid = nullptr)
 {

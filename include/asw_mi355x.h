@@ -103,6 +103,31 @@ static inline int asw_alg_cross(int tau, int trunc)
     return ASW_ALG_CROSS_PARAMS | bad | ((trunc & 0xFF) << 16) | ((tau & 0xFF) << 8) | ASW_ALG_ADAPTIVE_WEIGHT_CROSS;
 }
 
+/* ---- AD-Census matching (Mei et al. 2011; census of Zabih & Woodfill 1994; not in the reference) ----
+ * Selector entry 12 with another raw cost: everything said above holds with e replaced by the AD-Census cost and trunc = 255
+ * (a no-op on it).  A = the view image, B = the other one, s = -1 (LEFT) / +1 (RIGHT), off = min_d + plane index, all integer:
+ *   gray: a 3-channel image through the context's cvtColor(BGR2GRAY) (asw_set_gray_bits), a 1-channel image as it is;
+ *   census code of a gray pixel G(y,x): 62 bits, one per (dy, dx), dy in -3..3, dx in -4..4, (0,0) excluded, set exactly when
+ *     G(clamp(y+dy), clamp(x+dx)) < G(y,x) (clamped at the image border; a flat neighbourhood gives 0);
+ *   ham(y,x,off) = popcount(codeA(y,x) ^ codeB(y, reflect(x + s off))), 0..62, reflect the BORDER_REFLECT rule of asw_cost_ad;
+ *   ad(y,x,off) = the u8 value asw_cost_ad gives for the same pair, direction and plane;
+ *   e = TA[ad] + TC[ham] (0..254), TA[v] = floor(127 (1 - exp(-v / lambda_ad)) + 0.5), TC[h] the same with lambda_census (double).
+ * asw_alg_adcensus(tau, lambda_ad, lambda_census) forms the value of `algorithm`: bits 0-7 = 12, bits 8-15 = tau (0..255), bits 16-23 =
+ * lambda_census (1..255), bits 24-28 = lambda_ad (1..31), bit 29 set (ASW_ALG_ADCENSUS_PARAMS), bits 30 and 31 clear; an argument out of
+ * range gives lambda_ad field 0.  A value with bit 30 set is an asw_alg_cross() value whatever bit 29 holds; otherwise, with bit 29
+ * set, a low byte other than 12 gives ASW_ERR_UNSUPPORTED_METHOD and bit 31, lambda_ad field 0 or lambda_census field 0
+ * ASW_ERR_BAD_ARGUMENT.  asw_volume_planes is num_disparity for every valid value and 0 for the invalid ones.  Defaults everywhere:
+ * tau 20, lambda_ad 10, lambda_census 30.  The cost kernel stages a row pair in LDS: cols <= 7432 (3 channels) / 9084 (1 channel),
+ * else ASW_ERR_BAD_ARGUMENT.  asw_get_timing: the gray, census and cost kernels count in cost_ms; aggregate_ms / aggregate_launches are
+ * those of entry 12.  asw_aggregate_adcensus (inline, after asw_stereo_match below) is the per-method form. */
+enum { ASW_ALG_ADCENSUS_PARAMS = 0x20000000 };
+static inline int asw_alg_adcensus(int tau, int lambda_ad, int lambda_census)
+{
+    const int bad = tau < 0 || tau > 255 || lambda_ad < 1 || lambda_ad > 31 || lambda_census < 1 || lambda_census > 255;
+    return ASW_ALG_ADCENSUS_PARAMS | ((bad ? 0 : lambda_ad) << 24) | ((lambda_census & 0xFF) << 16) | ((tau & 0xFF) << 8) |
+           ASW_ALG_ADAPTIVE_WEIGHT_CROSS;
+}
+
 /* cv::Mat depth codes */
 enum { ASW_8U = 0, ASW_16S = 3, ASW_32F = 5 };
 
@@ -162,6 +187,15 @@ static inline int asw_aggregate_cross(asw_ctx* ctx, const asw_image* left, const
 {
     return asw_stereo_match(ctx, left, right, disp, disparity_type, asw_alg_cross(tau, trunc), win_size, min_disparity, num_disparity,
                             cost_volume_out, cost_volume_floats);
+}
+
+/* AD-Census matching with explicit parameters (above): asw_stereo_match with algorithm = asw_alg_adcensus(tau, lambda_ad, lambda_census). */
+static inline int asw_aggregate_adcensus(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp, int disparity_type,
+                                         int tau, int lambda_ad, int lambda_census, int win_size, int min_disparity, int num_disparity,
+                                         float* cost_volume_out, size_t cost_volume_floats)
+{
+    return asw_stereo_match(ctx, left, right, disp, disparity_type, asw_alg_adcensus(tau, lambda_ad, lambda_census), win_size,
+                            min_disparity, num_disparity, cost_volume_out, cost_volume_floats);
 }
 
 /* Planes of the cost volume `algorithm` produces for num_disparity candidates (what cost_volume_out must hold);
@@ -244,6 +278,25 @@ int asw_cost_ad(asw_ctx* ctx, const asw_image* left, const asw_image* right, uin
 /* computeTAD, M.cpp:304-401: 0/255 mask of AD > threshold_T */
 int asw_cost_tad(asw_ctx* ctx, const asw_image* left, const asw_image* right, uint8_t* cost,
                  int disparity_type, int threshold_t, int min_disparity, int num_disparity);
+/* Census cost and AD-Census cost (not in the reference; "AD-Census matching" above), inline over asw_cost_tad so that the library's
+ * exported set does not grow: a threshold_t from ASW_COST_CENSUS_PARAMS (bit 30) up, which as a TAD threshold could only give an
+ * all-zero mask, selects them: bits 8-15 = lambda_ad, bits 0-7 = lambda_census, both 0 (Hamming alone) or both 1..255, bits 16-29
+ * clear, else ASW_ERR_BAD_ARGUMENT.  Arguments and statuses otherwise as asw_cost_ad; cost u8 [num_d][rows][cols].
+ * asw_cost_census: the Hamming distance ham (0..62) of the census codes of the gray pair; cols <= 10240.
+ * asw_cost_adcensus: e = TA[ad] + TC[ham] (0..254); both lambdas in 1..255; cols <= 7432 (3 channels) / 9084 (1 channel). */
+enum { ASW_COST_CENSUS_PARAMS = 0x40000000 };
+static inline int asw_cost_census(asw_ctx* ctx, const asw_image* left, const asw_image* right, uint8_t* cost, int disparity_type,
+                                  int min_disparity, int num_disparity)
+{
+    return asw_cost_tad(ctx, left, right, cost, disparity_type, ASW_COST_CENSUS_PARAMS, min_disparity, num_disparity);
+}
+static inline int asw_cost_adcensus(asw_ctx* ctx, const asw_image* left, const asw_image* right, uint8_t* cost, int disparity_type,
+                                    int lambda_ad, int lambda_census, int min_disparity, int num_disparity)
+{
+    const int bad = (lambda_ad < 1 || lambda_ad > 255 || lambda_census < 1 || lambda_census > 255) ? 0x10000 : 0;
+    return asw_cost_tad(ctx, left, right, cost, disparity_type,
+                        ASW_COST_CENSUS_PARAMS | bad | ((lambda_ad & 0xFF) << 8) | (lambda_census & 0xFF), min_disparity, num_disparity);
+}
 /* computeSD, M.h:117-118, M.cpp:670-759: the AD value squared by a u8 Mat::mul, i.e. min(255, ad*ad) */
 int asw_cost_sd(asw_ctx* ctx, const asw_image* left, const asw_image* right, uint8_t* cost,
                 int disparity_type, int min_disparity, int num_disparity);

@@ -20,6 +20,11 @@ The leg cross is the cross-based support-region method (selector entry 12) again
 without the kept volume; its cases come from cross_ref.random_case and a mismatch prints the tag cross_ref.build_case rebuilds.
 
     python tools/fuzz_parity.py --seconds 120 --seed 1 --only cross
+
+The leg adcensus is AD-Census matching (asw_alg_adcensus: the census + AD cost under entry 12's aggregation) against
+tests/adcensus_ref.py in the same way; its cases are the cross cases plus random lambdas (adcensus_ref.random_case / build_case).
+
+    python tools/fuzz_parity.py --seconds 120 --seed 1 --only adcensus
 """
 import argparse
 import os
@@ -34,12 +39,14 @@ from aswstereomatch_amd.synth import make_pair  # noqa: E402
 from oracle import asw_oracle as O  # noqa: E402
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+import adcensus_ref as ac  # noqa: E402
 import cross_ref as cr  # noqa: E402
 import matcher_cases as mc  # noqa: E402
 
 A = asw.StereoMatchingAlgorithms
 # checked against the CPU oracle (oracle/); the legs (mc.FAMILIES) are checked against the restatements under tests/
-LEGS = tuple(mc.FAMILIES) + ("cross",)
+LEGS = tuple(mc.FAMILIES) + ("cross", "adcensus")
+REF_LEGS = {"cross": cr, "adcensus": ac}  # legs whose module has random_case / gpu_result of its own
 ORACLE_METHODS = ["classic", "direct8", "geodesic", "guided", "guided2", "guided3", "wmedian", "blo1", "ncc", "ncc_cost",
                   "ad_tad", "similarity", "sad", "geodist", "gfilter", "prep", "bilgrid", "lrcheck", "resident", "batch"]
 
@@ -83,7 +90,7 @@ def main():
     while time.time() - t0 < args.seconds:
         if rng_mc.random() < leg_share:  # the integer kernels: inputs and every parameter come from tests/matcher_cases.py
             method = legs[int(rng_mc.integers(0, len(legs)))]
-            case = cr.random_case(rng_mc, n) if method == "cross" else mc.random_case(rng_mc, method, n)
+            case = REF_LEGS[method].random_case(rng_mc, n) if method in REF_LEGS else mc.random_case(rng_mc, method, n)
             tag = (method,) + case["tag"]
         else:
             H = int(rng.integers(1, args.max_h))
@@ -145,8 +152,8 @@ def main():
         if args.trace:
             print("case", n, tag, flush=True)
         try:
-            if method == "cross":
-                (v, d, d2), (vw, dw) = cr.gpu_result(ctx, case)
+            if method in REF_LEGS:
+                (v, d, d2), (vw, dw) = REF_LEGS[method].gpu_result(ctx, case)
                 ok = np.array_equal(v, vw) and np.array_equal(d, dw) and np.array_equal(d2, dw)
             elif method in mc.FAMILIES:
                 ok = mc.same(*mc.gpu_result(ctx, case))
