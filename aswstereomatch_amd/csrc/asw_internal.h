@@ -117,6 +117,8 @@ struct asw_ctx {
 int launch_bgr2gray(hipStream_t s, const uint8_t* bgr, int H, int W, uint8_t* gray, int bits);
 // cvtColor(COLOR_RGB2GRAY) applied to BGR data, as computeNCC does (M.cpp:835,840): the R and B coefficients swap
 int launch_rgb2gray(hipStream_t s, const uint8_t* bgr, int H, int W, uint8_t* gray, int bits);
+// cost u8 [numD][H][W].  The staged row pair (2 W C bytes) must fit 160 KB of LDS, else ASW_ERR_BAD_ARGUMENT: W <= 27306 (C = 3),
+// 81920 (C = 1)
 int launch_cost_ad(hipStream_t s, const uint8_t* L, const uint8_t* R, int H, int W, int C, int disp_type, int minD,
                    int numD, int do_thresh /* 0: AD, 1: TAD mask, 2: SD */, int threshold, uint8_t* cost);
 int launch_wta(hipStream_t s, const float* vol, int n, int H, int W, int minD, float* disp);

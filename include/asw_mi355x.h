@@ -272,7 +272,9 @@ int asw_aggregate_wmedian(asw_ctx* ctx, const asw_image* left, const asw_image* 
                           int num_disparity, float* cost_volume_out, size_t cost_volume_floats);
 
 /* ---- cost builders (M.h:101-113, 156) : outputs are dense d-major volumes ---- */
-/* computeAD, M.cpp:208-292: cost u8 [num_d][rows][cols]; 1- or 3-channel 8U input */
+/* computeAD, M.cpp:208-292: cost u8 [num_d][rows][cols]; 1- or 3-channel 8U input.  asw_cost_ad, asw_cost_tad and asw_cost_sd stage a
+ * row pair in LDS (2 * cols * channels bytes of 160 KB): cols <= 27306 (3 channels) / 81920 (1 channel), else ASW_ERR_BAD_ARGUMENT;
+ * the same holds for selector entry 12, whose raw cost this is. */
 int asw_cost_ad(asw_ctx* ctx, const asw_image* left, const asw_image* right, uint8_t* cost,
                 int disparity_type, int min_disparity, int num_disparity);
 /* computeTAD, M.cpp:304-401: 0/255 mask of AD > threshold_T */
