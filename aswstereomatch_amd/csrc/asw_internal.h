@@ -143,6 +143,8 @@ struct BilateralLaunch {
     int c_begin = 0;  // > 0: only candidates [c_begin, nD)
     int resume = 0;   // 1: the running minimum starts from partE / partD ([H][W]) instead of DBL_MAX
     int out_slice = -1;  // >= 0: write this launch's winners to slice out_slice of partE / partD (merged later) instead of disp
+    int col_lo = 0, col_hi = -1;  // image columns [col_lo, col_hi) to compute (col_hi < 0: W): only the tiles that overlap them are
+                                  // launched and nothing is stored outside them (not with the grid.z split of small frames)
 };
 // xq form of the classic kernel (k_bilateral_xq.hip): candidates [0, bilateral_xq_candidates()) of a DISPARITY_LEFT, win = 15
 // problem with at least that many candidates; writes the running minimum to bestE / bestD for the tail launch, or -- when
@@ -153,10 +155,16 @@ int bilateral_xq_candidates(int nwave);  // nwave = 8 / 4 wavefronts per workgro
 constexpr int XQ_LUT_SCALE_LOG2 = 60;
 bool bilateral_xq_lut_ok(const float* lut, size_t n);
 int launch_bilateral_xq(hipStream_t s, hipStream_t s_border, int nwave, const uint8_t* gL, const uint8_t* gR, int H, int W, int minD,
-                        const int4* cells, const float* lut, float* vol, double* bestE, float* bestD, float* disp, bool right = false);
+                        const int4* cells, const float* lut, float* vol, double* bestE, float* bestD, float* disp, bool right = false,
+                        bool last = false);
+// image columns [*lo, *hi) that the interior tiles of the xq launch cover (empty: no interior tile)
+void bilateral_xq_interior_columns(int W, bool right, int* lo, int* hi);
 int launch_bilateral(hipStream_t s, const BilateralLaunch& a);
 // winners of per-slice partial WTAs (candidate range split over grid.z for small frames) -> disparity, strict '<' in ascending d
 int launch_merge_slices(hipStream_t s, const double* partE, const float* partD, int nz, size_t plane, float* disp);
+// the same over the image columns [col_lo, col_hi) only
+int launch_merge_slices_cols(hipStream_t s, const double* partE, const float* partD, int nz, int H, int W, int col_lo, int col_hi,
+                             float* disp);
 int bilateral_lds_row_stride(int win);  // LW of the kernel's sample tile (taps[].x is expressed in it)
 
 // ---- cost kernels (k_cost.hip) ----

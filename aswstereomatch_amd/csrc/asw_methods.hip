@@ -235,23 +235,33 @@ static int run_bilateral(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool kee
         ASW_TRY(slice_scratch(ctx, a.max_slices, plane, &a.partE, &a.partD));
         a.c_begin = bilateral_xq_candidates(xq_waves);
         const bool tail = nD > a.c_begin;  // numDisparity = 127 / 63 ends exactly at the xq kernel's 128 / 64 candidates
+        // One candidate more than the xq kernel's block -- the reference's inclusive range at numDisparity 128 / 64: the interior
+        // tiles finish it themselves (LASTC) and write the disparity; the one-kernel launch for that candidate, its
+        // slice and the merge shrink to the columns of the border tiles.  The launch count stays 4.
+        int ic_lo = 0, ic_hi = 0;
+        bilateral_xq_interior_columns(W, flip != 0, &ic_lo, &ic_hi);
+        const bool last = nD == a.c_begin + 1 && ic_lo < ic_hi;
+        const int bc_lo = flip ? 0 : ic_hi, bc_hi = flip ? ic_lo : W;  // the border tiles' columns (never empty)
         ASW_TRY(agg_begin(ctx));
         // fork: border tiles and the tail are independent of the interior launch (they write other pixels / another slice of the
         // per-slice winners); on side streams they overlap it instead of adding two latency-bound 0.5 ms launches to the frame
         ASW_HIP_TRY(hipEventRecord(ctx->aux_ev[0], ctx->stream));
         ASW_HIP_TRY(hipStreamWaitEvent(ctx->aux[0], ctx->aux_ev[0], 0));
         ASW_TRY(launch_bilateral_xq(ctx->stream, ctx->aux[0], xq_waves, a.gL, a.gR, H, W, mp.minD, ctx->bil.cells.as<int4>(), ctx->bil.lut_xq.as<float>(), a.vol,
-                                    a.partE, a.partD, tail ? nullptr : a.disp, flip != 0));
+                                    a.partE, a.partD, tail && !last ? nullptr : a.disp, flip != 0, last));
         ASW_HIP_TRY(hipEventRecord(ctx->aux_ev[1], ctx->aux[0]));
         if (tail) {
             ASW_HIP_TRY(hipStreamWaitEvent(ctx->aux[1], ctx->aux_ev[0], 0));
             a.out_slice = 1;  // candidates [128 | 64, nD) -> slice 1; the xq launches fill slice 0
+            if (last) { a.col_lo = bc_lo; a.col_hi = bc_hi; }
             ASW_TRY(launch_bilateral(ctx->aux[1], a));
             ASW_HIP_TRY(hipEventRecord(ctx->aux_ev[2], ctx->aux[1]));
             ASW_HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->aux_ev[2], 0));
         }
         ASW_HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->aux_ev[1], 0));  // join
-        if (tail) ASW_TRY(launch_merge_slices(ctx->stream, a.partE, a.partD, 2, plane, a.disp));  // strict '<', ascending d
+        // strict '<', ascending d
+        if (tail && last) ASW_TRY(launch_merge_slices_cols(ctx->stream, a.partE, a.partD, 2, H, W, bc_lo, bc_hi, a.disp));
+        else if (tail) ASW_TRY(launch_merge_slices(ctx->stream, a.partE, a.partD, 2, plane, a.disp));
         return agg_end(ctx, tail ? 4 : 2);
     }
     if (plane <= (size_t)1 << 20) {  // small frames only: scratch for the grid.z split of the disparity range

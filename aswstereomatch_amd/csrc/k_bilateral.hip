@@ -46,6 +46,8 @@ struct BilParams {
     int c_begin;     // first candidate of this launch; > 0: the tail of a range whose head k_asw_bilateral_xq does
     int resume;      // 1: the running minimum is resumed from partE / partD ([H][W], grid.z == 1)
     int out_slice;   // >= 0 (grid.z == 1): winners go to slice out_slice of partE / partD (merged later) instead of disp
+    int tile0;       // first tile column of the launch: only the tiles that overlap the column window are launched
+    int x_lo, x_hi;  // column window [x_lo, x_hi) in the kernel's (mirrored when flip) coordinates: nothing is stored outside it
 };
 
 constexpr __host__ __device__ int round_up(int v, int a) { return (v + a - 1) / a * a; }
@@ -101,7 +103,7 @@ __device__ __forceinline__ void process_chunk(const BilParams& p, const uint8_t*
     float* sWL = reinterpret_cast<float*>(smem + lay.offWL);
     constexpr int SWR = TW + DC - 1;
     const int tid = threadIdx.x, tx = tid & 63, ty = tid >> 6;
-    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
+    const int x0 = (p.tile0 + blockIdx.x) * TW, y0 = blockIdx.y * TH;
     const int H = p.H, W = p.W, h = lay.h, LW = lay.LW, LWp = lay.LWp, RWp = lay.RWp, TR = lay.TR;
     const int RW = TW + 2 * h + DC - 1;
     const int d0 = p.minD + c0;
@@ -247,7 +249,7 @@ __device__ __forceinline__ void process_chunk(const BilParams& p, const uint8_t*
     }
 
     const int x = x0 + tx, y = y0 + ty;
-    if (x < W && y < H) {
+    if (x >= p.x_lo && x < p.x_hi && y < H) {
 #pragma unroll
         for (int dd = 0; dd < DC; dd++) {
             double E = num[dd] / den[dd];  // M.cpp:1111
@@ -269,7 +271,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     extern __shared__ __align__(16) unsigned char smem[];
     const Layout lay(HH > 0 ? HH : p.h, G);
     const int tid = threadIdx.x;
-    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
+    const int x0 = (p.tile0 + blockIdx.x) * TW, y0 = blockIdx.y * TH;
     const int H = p.H, W = p.W, h = lay.h;
 
     // left gray tile with replicate-clamped coordinates, staged once
@@ -300,7 +302,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     if (cEnd - c0 >= 1) { process_chunk<1, G>(p, gR, taps, lut, vol, lay, smem, c0, bestE, bestD); c0 += 1; }
 
     const int x = x0 + (tid & 63), y = y0 + (tid >> 6);
-    if (x < W && y < H) {
+    if (x >= p.x_lo && x < p.x_hi && y < H) {
         const size_t o = (size_t)y * W + (p.flip ? W - 1 - x : x);
         if (gridDim.z == 1 && p.out_slice < 0) {
             disp[o] = bestD;
@@ -327,6 +329,22 @@ __global__ __launch_bounds__(256) void k_merge_slices(const double* __restrict__
     disp[o] = bd;
 }
 
+// the same over the columns [x_lo, x_lo + wc) of every row only: grid (ceil(wc / 64), H), 64 threads
+__global__ __launch_bounds__(64) void k_merge_slices_cols(const double* __restrict__ partE, const float* __restrict__ partD, int nz,
+                                                          int H, int W, int x_lo, int wc, float* __restrict__ disp)
+{
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= wc) return;
+    const size_t plane = (size_t)H * W, o = (size_t)blockIdx.y * W + x_lo + c;
+    double best = 1.7976931348623157e308;
+    float bd = 0.0f;
+    for (int z = 0; z < nz; z++) {
+        const double e = partE[(size_t)z * plane + o];
+        if (e < best) { best = e; bd = partD[(size_t)z * plane + o]; }
+    }
+    disp[o] = bd;
+}
+
 template <int HH, int G, int WPE = 2>
 int launch_t(hipStream_t s, const BilateralLaunch& a)
 {
@@ -334,12 +352,18 @@ int launch_t(hipStream_t s, const BilateralLaunch& a)
     p.H = a.H; p.W = a.W; p.h = a.win / 2; p.minD = a.minD; p.nD = a.nD; p.ntaps = a.ntaps; p.flip = a.flip;
     p.c_begin = a.c_begin; p.resume = a.resume; p.out_slice = a.out_slice;
     if (a.c_begin < 0 || a.c_begin >= a.nD || ((a.resume || a.out_slice >= 0) && !(a.partE && a.partD))) return ASW_ERR_BAD_ARGUMENT;
+    // column window in the kernel's coordinates (mirrored when flip); W need not be a multiple of the tile width
+    const int c_lo = std::max(a.col_lo, 0), c_hi = a.col_hi < 0 ? a.W : std::min(a.col_hi, a.W);
+    if (c_lo >= c_hi) return ASW_ERR_BAD_ARGUMENT;
+    p.x_lo = a.flip ? a.W - c_hi : c_lo;
+    p.x_hi = a.flip ? a.W - c_lo : c_hi;
+    p.tile0 = p.x_lo / TW;
     const Layout lay(p.h, G);
     if (lay.total > 160 * 1024) return ASW_ERR_BAD_ARGUMENT;
     auto kern = k_asw_bilateral<HH, G, WPE>;
     if (lay.total > 64 * 1024)
         ASW_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lay.total));
-    dim3 grid((a.W + TW - 1) / TW, (a.H + TH - 1) / TH);
+    dim3 grid((p.x_hi - 1) / TW - p.tile0 + 1, (a.H + TH - 1) / TH);
     if (a.ntaps % G != 0) return ASW_ERR_BAD_ARGUMENT;  // cannot happen for odd windows
     // Small images do not fill 256 CUs with tiles alone (C2: 450x375 -> 752 tiles): split the candidate range over
     // grid.z in multiples of 16 until there are ~2048 workgroups, and merge the per-slice winners afterwards.
@@ -366,6 +390,16 @@ int bilateral_lds_row_stride(int win) { return TW + 2 * (win / 2); }
 int launch_merge_slices(hipStream_t s, const double* partE, const float* partD, int nz, size_t plane, float* disp)
 {
     hipLaunchKernelGGL(k_merge_slices, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, s, partE, partD, nz, plane, disp);
+    ASW_HIP_TRY(hipGetLastError());
+    return ASW_OK;
+}
+
+int launch_merge_slices_cols(hipStream_t s, const double* partE, const float* partD, int nz, int H, int W, int col_lo, int col_hi,
+                             float* disp)
+{
+    if (col_lo < 0 || col_hi > W || col_lo >= col_hi) return ASW_ERR_BAD_ARGUMENT;
+    const int wc = col_hi - col_lo;
+    hipLaunchKernelGGL(k_merge_slices_cols, dim3((wc + 63) / 64, H), dim3(64), 0, s, partE, partD, nz, H, W, col_lo, wc, disp);
     ASW_HIP_TRY(hipGetLastError());
     return ASW_OK;
 }

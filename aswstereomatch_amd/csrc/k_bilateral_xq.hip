@@ -37,9 +37,30 @@
 // (18 steps of 15 rows), no cost tile, gray tiles as u32 in LDS.
 // Block j = 0 holds six units with d < minD (a < b) and a block j = 32 would hold exactly six units with c = d - minD < 128
 // in the same slots (c = 128 + a - b): the j = 0 threads run those instead ("wrapped" units: second position base qrel2,
-// second right gray), so the 512 threads finish candidates [0, 128) with no idle unit.  The tail [128, nD) -- one candidate
-// at the reference's numDisparity = 128, whose range is inclusive (M.cpp:1021,1074) -- is left to k_asw_bilateral, which
-// resumes from this kernel's running minimum.
+// second right gray), so the 512 threads finish candidates [0, 128) with no idle unit.  A tail [128, nD) of more than one
+// candidate is left to k_asw_bilateral (its winners go to a second slice, k_merge_slices picks the first minimum).
+//
+// The inclusive last candidate (LASTC).  The reference's range is inclusive (M.cpp:1021,1074): numDisparity 128 / 64 are 129 /
+// 65 candidates, NFIN + 1.  Every operand of candidate NFIN is staged in the workgroup already -- the left weights of the 64
+// pixels in the ring, the right weights and grays of positions posmin + 0..63 (RIGHT: + 4 NJ) for the wrapped units -- so the
+// interior tiles' LASTC instantiation finishes it: 64 more units, one per pixel, in ONE plain wavefront, the last (UWAVE = NW -
+// 1: not on wave 0's SIMD, and the wavefront that stages a window row fewer than the others, which pays for most of the
+// unit).  Lane -> pixel 4g + a with a = (lane >> 3) & 3 (the four lanes that share a g), position index 4g + a (+ 4 NJ), unit
+// row b = a, so the right buffer of step K holds tap column K - a for it and the unit runs a columns behind like every other:
+// left weight from ring slot (K - a) mod 5, right weight from buffer K & 1, grays at tile columns 4g + K (left: the diagonal-0
+// sample of the row's own quads) and 4g + K (+ 4 NJ) (right) -- the skew cancels in both; one v_sad_u16, one f32 multiply, one
+// cvt, one fma, one add per row, taps in the same ascending order: E is bit-identical.  Lane-steps with K - a outside 0..14 add
+// +0.0 to both sums: the right weight is the all-zero class there, and the left operand is finite -- the ring slots of columns
+// -3..-1 (slots 2..4) are zeroed in the prologue, columns 15..17 find older columns, and the slot index is a non-negative
+// modulus.  Registers are the whole difficulty (wave 0 needs all 128): the LASTC kernels carry nothing that is a function of
+// the lane number through the row loops (FRESH: lane, g, qrel, the packed clamped positions are taken afresh in every step, in
+// all eight wavefronts: about 30 instructions per step each), the unit's wavefront runs with its wave number as a constant (its
+// missing staging row folds away), and the other wavefronts' row loops carry nothing of the unit's sums.  Epilogue: sE holds NFIN + 1 planes, plane NFIN goes to vol and enters the
+// WTA last with the same strict '<' (still the first minimum in ascending d), and the kernel writes disp.
+// The border tiles (EDGE; they spill at one row per body and cannot host the unit) keep the slice sequence on their own
+// columns: EDGE launch -> slice 0, k_asw_bilateral for candidate NFIN on a column window -> slice 1, k_merge_slices_cols over the
+// window.  Interior and border launches write disjoint columns of disp and vol, so the launch count stays 4 and nothing is
+// written twice.
 //
 // DISPARITY_RIGHT (M.cpp:1113-1142; RIGHT = true): the fixed image is the right one (the host passes it as gL) and the pair of
 // pixel x is the left-image position q = min(W-1, x + d).  Nothing in the blocking depends on the sign of d: unit (a,b) is
@@ -79,7 +100,7 @@ constexpr int LWP = 80;                   // u32 row stride of the left gray til
 // right weights, u32 [RWP] right gray} | u8 [KS][LW8] | u8 [KS][RW8] | u16 [NCELLCOL * KS] packed cell table.  Weights and
 // grays of a window row share one row stride per side, so that every LDS address of the row loop is one of two per-lane bases
 // (three in wave 0) plus an immediate offset: two address increments per body of three rows.
-// Epilogue (over the dead tiles): double [NFIN][PXW] E | per-part WTA partials double E[NW][PXW], float d[NW][PXW].
+// Epilogue (over the dead tiles): double [NFIN + 1][PXW] E | per-part WTA partials double E[NW][PXW], float d[NW][PXW].
 // NW = 8: 70 KB (the epilogue's), two workgroups = 16 wavefronts per CU; NW = 4: 52 KB, three workgroups = 12 wavefronts per CU.
 template <int NW>
 struct XqCfg {
@@ -104,7 +125,7 @@ struct XqCfg {
     static constexpr int OFF_R8 = OFF_L8 + KS * LW8;
     static constexpr int OFF_CELL = OFF_R8 + KS * RW8;
     static constexpr int OFF_E64 = 0;
-    static constexpr int OFF_PART = NFIN * PXW * 8;
+    static constexpr int OFF_PART = (NFIN + 1) * PXW * 8;  // plane NFIN: the last-candidate units' (LASTC)
     // the epilogue buffers reuse the dead tiles; for NW = 8 they are the larger of the two
     static constexpr int LDS_TOTAL = std::max((OFF_CELL + NCELLCOL * KS * 2 + 15) / 16 * 16, OFF_PART + NW * PXW * 12);
     static_assert(LDS_TOTAL <= (NW == 8 ? 80 : 53) * 1024, "two (NW = 8) / three (NW = 4) workgroups per CU");
@@ -211,6 +232,32 @@ __device__ __forceinline__ void stage_weights(int Kn, const float* __restrict__ 
     stage_commit<NW>(Kn, smem, wave, lane, st);
 }
 
+// LASTC kernels (FRESH) take everything that is a function of the lane number -- the lane number itself, g, qrel, the packed clamped
+// positions -- afresh in every step instead of carrying it through the row loops, in ALL wavefronts of those kernels (one register
+// file size serves every path): about a dozen instructions per step and wavefront buy the registers the unit's sums need.
+__device__ __forceinline__ int fresh_lane()
+{
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=&v"(l));
+    return l;
+}
+template <int NPOS>
+__device__ __forceinline__ uint32_t pack_positions(int lane, int pclamp_lo, int pclamp_hi)
+{
+    uint32_t ppack = 0;
+#pragma unroll
+    for (int r3 = 0; r3 < NPOS / 64; r3++) ppack |= (uint32_t)min(max(lane + 64 * r3, pclamp_lo), pclamp_hi) << (8 * r3);
+    asm volatile("" : "+v"(ppack));
+    return ppack;
+}
+// The wavefront of the last-candidate units is the last one: plain, on another SIMD than wave 0 (waves w and w + 4 share one),
+// and the one that stages a window row fewer than the others (rows w, w + NW, ... < 15), which pays for most of the unit.
+template <int NW> constexpr int UWAVE = NW - 1;
+// the sums of a lane's last-candidate unit; empty where there is none, so that the row loops of the other wavefronts carry nothing
+// of it (their steps still take the lane-derived values afresh, see FRESH above)
+template <bool ON> struct USums {};
+template <> struct USums<true> { double num = 0.0, den = 0.0; };
+
 // One step: window rows ky = 0..14 of tap column K - b for every active unit row b (BLO <= b <= BHI).
 //   EDGE = false: the workgroup's windows never clamp at the right image border: one right gray per step (two with the
 //                 wrapped units).
@@ -218,11 +265,14 @@ __device__ __forceinline__ void stage_weights(int Kn, const float* __restrict__ 
 // Units with a < b (RIGHT: b < a) take their position from qrel2 / dbase2 (== qrel / dbase except in the threads of block
 // j = 0, where they are the wrapped units of block 32).
 // WRAPW: this wavefront holds the threads of block j = 0 (wave 0).  Elsewhere qrel2 == qrel and the second loads are skipped.
-template <int NW, int K, bool EDGE, bool WRAPW, bool COMMIT, bool RIGHT>
+// LASTW: this wavefront also runs the 64 last-candidate units of the workgroup (see the header comment): lane -> pixel
+// 4g + a, a = (lane >> 3) & 3, candidate NFIN, tap column K - a.
+template <int NW, int K, bool EDGE, bool WRAPW, bool COMMIT, bool RIGHT, bool LASTW, bool FRESH>
 __device__ __forceinline__ void run_step(unsigned char* smem, int g, int qrel, int qrel2, int xabs, int dbase, int dbase2,
-                                         int W, int x0, int posmin, double (&num)[4][4], double (&den)[4][4], int wave, int lane,
-                                         const Staged<NW>& st)
+                                         int W, int x0, int posmin, double (&num)[4][4], double (&den)[4][4], USums<LASTW>& us,
+                                         int wave, int lane, const Staged<NW>& st)
 {
+    static_assert(!LASTW || (!EDGE && !WRAPW), "the last-candidate units live in a plain wavefront of an interior tile");
     XQ_CONSTS(NW)
     constexpr int BLO = K > KS - 1 ? K - (KS - 1) : 0;  // kx = K - b <= 14
     constexpr int BHI = K < 3 ? K : 3;                  // kx = K - b >= 0
@@ -249,6 +299,29 @@ __device__ __forceinline__ void run_step(unsigned char* smem, int g, int qrel, i
     lds_u8* bL = (lds_u8*)smem + OFF_LB + 16 * g;
     lds_u8* bR = (lds_u8*)smem + OFF_RB + 4 * qrel;
     lds_u8* bR2 = (lds_u8*)smem + OFF_RB + 4 * qrel2;
+    // the last-candidate unit's three addresses (see the unit in the row): left weight, right weight, right gray
+    lds_u8* uL = nullptr; lds_u8* uW = nullptr; lds_u8* uG = nullptr;
+    if constexpr (FRESH) {
+        static_assert(!EDGE, "interior tiles");
+        const int l2 = fresh_lane();
+        g = (l2 & 7) | ((l2 >> 2) & 8);
+        const int jl = 4 * wave + ((l2 >> 3) & 3);
+        qrel = RIGHT ? 4 * g + 4 * jl : 4 * g + 4 * (NJ - jl);
+        qrel2 = jl == 0 ? (RIGHT ? 4 * g + 4 * NJ : 4 * g) : qrel;
+        bL = (lds_u8*)smem + OFF_LB + 16 * g;
+        bR = (lds_u8*)smem + OFF_RB + 4 * qrel;
+        bR2 = (lds_u8*)smem + OFF_RB + 4 * qrel2;
+    }
+    if constexpr (LASTW) {
+        static_assert(FRESH, "g is this step's own");
+        const int a = (fresh_lane() >> 3) & 3;
+        // non-negative modulus: columns -3..-1 are the slots the prologue zeroed, 15..17 hold older (finite) columns
+        const int slot = a == 0 ? (K + RING) % RING : a == 1 ? (K - 1 + RING) % RING : a == 2 ? (K - 2 + RING) % RING : (K - 3 + RING) % RING;
+        uL = (lds_u8*)smem + OFF_LB + 16 * g + 4 * a + 4 * PXW * slot;
+        uW = (lds_u8*)smem + OFF_RB + 16 * g + (RIGHT ? 16 * NJ : 0) + 4 * a + 4 * (K & 1) * NPOS;
+        uG = (lds_u8*)smem + OFF_RB + 16 * g + (RIGHT ? 16 * NJ : 0);
+        asm("" : "+v"(uL), "+v"(uW), "+v"(uG));
+    }
     uint32_t hi0[7];
 #pragma unroll
     for (int i = 0; i < 7; i++) asm volatile("v_mov_b32 %0, 0" : "=v"(hi0[i]));  // seven distinct registers the compiler cannot fold
@@ -266,6 +339,8 @@ __device__ __forceinline__ void run_step(unsigned char* smem, int g, int qrel, i
                 lds_u8* rR = bR + u * 4 * RROW;
                 lds_u8* rR2 = bR2 + u * 4 * RROW;
                 double c[7];  // cost samples of the diagonals, scaled domain: |gL - gR| * 2^-1074
+                uint32_t glU = 0;  // left gray of diagonal 0 (LASTW)
+                (void)glU;
                 if constexpr (!EDGE) {
                     const uint32_t gr = *(const __attribute__((address_space(3))) uint32_t*)(rR + 4 * (RGRAY + K));  // tile column of Q + K - 7
                     uint32_t gr2 = gr;
@@ -287,6 +362,8 @@ __device__ __forceinline__ void run_step(unsigned char* smem, int g, int qrel, i
                     }
 #pragma unroll
                     for (int dl = DLO; dl <= DHI; dl++) c[dl + 3] = cost_sample(glv[K + dl - E0], (RIGHT ? dl > 0 : dl < 0) ? gr2 : gr, hi0[dl + 3]);
+                    static_assert(DLO <= 0 && DHI >= 0, "diagonal 0 is in use in every step");
+                    glU = glv[K - E0];
                 } else {
                     const int ky = ky0 + it * UR + u;
 #pragma unroll
@@ -333,6 +410,25 @@ __device__ __forceinline__ void run_step(unsigned char* smem, int g, int qrel, i
                         den[a][b] = den[a][b] + abd;                              // M.cpp:1107-1108 (x 2^120)
                     }
                 }
+                if constexpr (LASTW) {
+                    constexpr int E0 = (K + DLO) & ~3;
+                    (void)E0;
+                    typedef __attribute__((address_space(3))) const uint32_t lds_u32;
+                    // lane -> pixel 4g + a, a = (lane >> 3) & 3, candidate NFIN: position 4g + a (+ 4 NJ), unit row b = a, tap column
+                    // K - a; the grays are the tile columns 4g + K (left: the diagonal-0 sample the row has loaded anyway) and
+                    // 4g + K (+ 4 NJ) (right): the skew a cancels in both
+                    typedef __attribute__((address_space(3))) const float lds_f32;
+                    const float wlU = *(lds_f32*)(uL + u * 4 * LROW);
+                    const float wrU = *(lds_f32*)(uW + u * 4 * RROW);
+                    const uint32_t grU = *(lds_u32*)(uG + u * 4 * RROW + 4 * (RGRAY + K));
+                    // inactive lane-steps (K - a outside 0..14): wrU is the all-zero class and wlU is finite (a zeroed slot or an
+                    // older column), so ab = +0: fma(+0, c, num) = num + (+0) = num (c >= 0 is finite; num is +0 or positive, so
+                    // the sum keeps its sign) and den + (+0) = den, in the scaled domain as in the plain one
+                    const double abU = (double)(wlU * wrU);
+                    us.num = __builtin_fma(abU, cost_sample(glU, grU, hi0[3]), us.num);
+                    us.den = us.den + abU;
+                    asm volatile("" :: "v"(us.num), "v"(us.den));
+                }
                 // the fence: the row's sums are complete here (the arithmetic has no side effect the barrier alone would order)
                 // and no LDS read crosses
 #pragma unroll
@@ -348,12 +444,18 @@ __device__ __forceinline__ void run_step(unsigned char* smem, int g, int qrel, i
                 bR2 += UR * 4 * RROW;
                 asm("" : "+v"(bR2));
             }
+            if constexpr (LASTW) {
+                uL += UR * 4 * LROW;
+                uW += UR * 4 * RROW;
+                uG += UR * 4 * RROW;
+                asm("" : "+v"(uL), "+v"(uW), "+v"(uG));
+            }
         }
     };
     if constexpr (COMMIT) {
         // the gathers issued before this loop have landed after CROW rows
         rows(0, CROW / UR);
-        stage_commit<NW>(K + 1, smem, wave, lane, st);
+        stage_commit<NW>(K + 1, smem, wave, FRESH ? fresh_lane() : lane, st);
         rows(CROW, (KS - CROW) / UR);
     } else {
         rows(0, KS / UR);
@@ -361,19 +463,21 @@ __device__ __forceinline__ void run_step(unsigned char* smem, int g, int qrel, i
 }
 
 // ABL (timing experiments only, results are wrong): bit 0 = no weight staging after step 0, bit 1 = no barriers between steps
-template <int NW, bool EDGE, bool WRAPW, int ABL, bool RIGHT>
+template <int NW, bool EDGE, bool WRAPW, int ABL, bool RIGHT, bool LASTW = false, bool FRESH = false>
 __device__ __forceinline__ void run_all_steps(unsigned char* smem, const float* __restrict__ lut, int wave, int lane,
                                               uint32_t ppack, int g, int qrel, int qrel2, int xabs, int dbase, int dbase2,
-                                              int W, int x0, int posmin, double (&num)[4][4], double (&den)[4][4])
+                                              int W, int x0, int posmin, double (&num)[4][4], double (&den)[4][4], USums<LASTW>& us, int pclamp_lo = 0,
+                                              int pclamp_hi = 0)
 {
     Staged<NW> st;
 #define ASW_XQ_STEP(KK)                                                                                        \
     if (!(ABL & 1) && (KK) + 1 < NSTEP) {                                                                        \
+        if constexpr (FRESH) { lane = fresh_lane(); ppack = pack_positions<XqCfg<NW>::NPOS>(lane, pclamp_lo, pclamp_hi); }  \
         if constexpr (EDGE) stage_weights<NW>((KK) + 1, lut, smem, wave, lane, ppack);  /* border tiles: registers are scarcer there */ \
         else stage_issue<NW>((KK) + 1, lut, smem, wave, lane, ppack, st);                      \
     }                                                                                                           \
-    run_step<NW, (KK), EDGE, WRAPW, (!EDGE && !(ABL & 1) && (KK) + 1 < NSTEP), RIGHT>(smem, g, qrel, qrel2, xabs, dbase, dbase2, W, x0, posmin, \
-                                                                           num, den, wave, lane, st);          \
+    run_step<NW, (KK), EDGE, WRAPW, (!EDGE && !(ABL & 1) && (KK) + 1 < NSTEP), RIGHT, LASTW, FRESH>(smem, g, qrel, qrel2, xabs, dbase, dbase2, W, x0, \
+                                                                           posmin, num, den, us, wave, lane, st); \
     if (!(ABL & 2) || (KK) == NSTEP - 1) __syncthreads();
     ASW_XQ_STEP(0) ASW_XQ_STEP(1) ASW_XQ_STEP(2) ASW_XQ_STEP(3) ASW_XQ_STEP(4) ASW_XQ_STEP(5)
     ASW_XQ_STEP(6) ASW_XQ_STEP(7) ASW_XQ_STEP(8) ASW_XQ_STEP(9) ASW_XQ_STEP(10) ASW_XQ_STEP(11)
@@ -381,10 +485,11 @@ __device__ __forceinline__ void run_all_steps(unsigned char* smem, const float* 
 #undef ASW_XQ_STEP
 }
 
-// grid (tiles of this launch, H), 512 threads.  gL / gR: gray planes [H][W].  vol (optional): [>= NFIN][H][W].
+// grid (tiles of this launch, H), 512 threads.  gL / gR: gray planes [H][W].  vol (optional): [>= NFIN][H][W] (LASTC: NFIN + 1).
 // bestE / bestD: [H][W] running minimum over candidates [0, NFIN) (strict '<' in ascending d, M.cpp:1145-1150) for the tail
 // launch to resume from; disp (when there is no tail): the disparity itself.
-template <int NW, bool EDGE, int ABL, bool RIGHT>
+// LASTC (interior tiles only): the workgroup finishes candidates [0, NFIN]: vol has NFIN + 1 planes and disp is written.
+template <int NW, bool EDGE, int ABL, bool RIGHT, bool LASTC = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8 ? 4 : 3, NW == 8 ? 4 : 3))) void k_asw_bilateral_xq(
     XqParams p, const uint8_t* __restrict__ gL, const uint8_t* __restrict__ gR, const int4* __restrict__ cells,
     const float* __restrict__ lut, float* __restrict__ vol, double* __restrict__ bestE, float* __restrict__ bestD,
@@ -393,6 +498,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
     // static: the LDS base is then a compile-time 0 and folds into the instructions' offset fields (with the dynamic-LDS
     // symbol every address in the step loop carried its own "v_add_u32 v, <base>, v": 6 of 78 VALU instructions)
     XQ_CONSTS(NW)
+    static_assert(!(EDGE && LASTC), "the border tiles cannot host the last-candidate units");
     __shared__ __align__(16) unsigned char smem[LDS_TOTAL];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int H = p.H, W = p.W;
@@ -418,6 +524,15 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
             const int v = gR[(size_t)yy * W + xx];
             sR8[r * RW8 + c] = (uint8_t)v;
             sRd[r * Cfg::RROW + c] = (uint32_t)v;
+        }
+        if constexpr (LASTC) {
+            // ring slots 2..4 stand for tap columns -3..-1 until columns 2..4 are staged (steps 1..3): the last-candidate units
+            // of lanes with a > K read them in steps 0..2 and must find a finite weight there
+            float* sWL = reinterpret_cast<float*>(smem + OFF_LB);
+            for (int i = tid; i < KS * 3 * PXW; i += NTHR) {
+                const int r = i / (3 * PXW), c = i - r * (3 * PXW);
+                sWL[r * Cfg::LROW + 2 * PXW + c] = 0.0f;
+            }
         }
         uint16_t* sCell = reinterpret_cast<uint16_t*>(smem + OFF_CELL);
         for (int i = tid; i < NCELLCOL * KS; i += NTHR) {
@@ -447,10 +562,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
     // again: left to itself it keeps every clamped position, the bounds and more in registers of their own through all
     // steps, a dozen of the 128
     static_assert(NPOS <= 256, "a clamped position fits a byte");
-    uint32_t ppack = 0;
-#pragma unroll
-    for (int r3 = 0; r3 < NPOS / 64; r3++) ppack |= (uint32_t)min(max(lane + 64 * r3, pclamp_lo), pclamp_hi) << (8 * r3);
-    asm volatile("" : "+v"(ppack));
+    const uint32_t ppack = pack_positions<NPOS>(lane, pclamp_lo, pclamp_hi);
 
     double num[4][4], den[4][4];
 #pragma unroll
@@ -458,16 +570,21 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
 #pragma unroll
         for (int b = 0; b < 4; b++) { num[a][b] = 0.0; den[a][b] = 0.0; }
 
+    USums<LASTC> us;  // the last-candidate unit of this lane (LASTC, wave UWAVE)
+    USums<false> none;
     stage_weights<NW>(0, lut, smem, wave, lane, ppack);
     __syncthreads();
     // wave 0 holds the threads of block j = 0 (the wrapped units): its steps load the second right weights / gray; ONE branch
     // around the whole step sequence (a branch per step made the register allocator spill 488 VGPRs)
     if (EDGE || wave == 0)
-        run_all_steps<NW, EDGE, true, ABL, RIGHT>(smem, lut, wave, lane, ppack, g, qrel, qrel2, xabs, dbase, dbase2, W,
-                                                   x0, posmin, num, den);
+        run_all_steps<NW, EDGE, true, ABL, RIGHT, false, LASTC>(smem, lut, wave, lane, ppack, g, qrel, qrel2, xabs, dbase, dbase2, W,
+                                                                 x0, posmin, num, den, none, pclamp_lo, pclamp_hi);
+    else if (LASTC && wave == UWAVE<NW>)  // (the wave number as a constant: the staging rows this wavefront does not have fold away)
+        run_all_steps<NW, EDGE, false, ABL, RIGHT, LASTC, LASTC>(smem, lut, UWAVE<NW>, lane, ppack, g, qrel, qrel2, xabs, dbase, dbase2, W,
+                                                                  x0, posmin, num, den, us, pclamp_lo, pclamp_hi);
     else
-        run_all_steps<NW, EDGE, false, ABL, RIGHT>(smem, lut, wave, lane, ppack, g, qrel, qrel2, xabs, dbase, dbase2, W,
-                                                    x0, posmin, num, den);
+        run_all_steps<NW, EDGE, false, ABL, RIGHT, false, LASTC>(smem, lut, wave, lane, ppack, g, qrel, qrel2, xabs, dbase, dbase2, W,
+                                                                  x0, posmin, num, den, none, pclamp_lo, pclamp_hi);
     // (the last step ended with a barrier: the tiles are dead)
 
     // ---- E = num / den (M.cpp:1111) -> LDS [candidate][pixel]; back from the scaled domain first (both ldexp are exact)
@@ -484,6 +601,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
             const int c = RIGHT ? (b < a ? cb2 : cb) + b - a : (a < b ? cb2 : cb) + a - b;  // in [0, 128) for every unit
             sE[c * PXW + 4 * ge + a] = __builtin_ldexp(num[a][b], 954) / __builtin_ldexp(den[a][b], -120);
         }
+    if constexpr (LASTC)
+        if (wave == UWAVE<NW>) sE[NFIN * PXW + 4 * ge + ((le >> 3) & 3)] = __builtin_ldexp(us.num, 954) / __builtin_ldexp(us.den, -120);
     __syncthreads();
     // ---- WTA (strict '<' while d ascends) and volume: thread -> (pixel, 16 consecutive candidates)
     const int px = lane, part = wave;
@@ -510,7 +629,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
             const double eq = sPE[q * PXW + px];
             if (eq < e) { e = eq; d = sPD[q * PXW + px]; }
         }
-        if (disp) {
+        if constexpr (LASTC) {  // candidate NFIN enters last, with the same strict '<': still the first minimum in ascending d
+            const double eq = sE[NFIN * PXW + px];
+            if (vol) vol[((size_t)NFIN * H + y) * W + x] = (float)eq;
+            if (eq < e) { e = eq; d = (float)(p.minD + NFIN); }
+        }
+        if (LASTC || disp) {
             disp[(size_t)y * W + x] = d;
         } else {
             bestE[(size_t)y * W + x] = e;
@@ -541,8 +665,10 @@ bool bilateral_xq_lut_ok(const float* lut, size_t n)
 namespace {
 template <int NW>
 int launch_xq_t(hipStream_t s, hipStream_t s_border, const uint8_t* gL, const uint8_t* gR, int H, int W, int minD, const int4* cells,
-                const float* lut, float* vol, double* bestE, float* bestD, float* disp, bool right)
+                const float* lut, float* vol, double* bestE, float* bestD, float* disp, bool right, bool last)
 {
+    // last: the interior launch finishes candidate NFIN as well and writes disp and plane NFIN of vol for its columns; the border
+    // tiles write bestE / bestD (the caller runs candidate NFIN and the merge over their columns)
     const int ntiles = (W + PXW - 1) / PXW;
     const dim3 blk(64 * NW);
     if (right) {
@@ -551,11 +677,15 @@ int launch_xq_t(hipStream_t s, hipStream_t s_border, const uint8_t* gL, const ui
         if ((ntiles - 1) * PXW + minD > W - 1) return ASW_ERR_BAD_ARGUMENT;
         XqParams pe{H, W, minD, 0};
         hipLaunchKernelGGL((k_asw_bilateral_xq<NW, true, 0, true>), dim3(1, H), blk, 0, s_border, pe, gL, gR, cells, lut, vol,
-                           bestE, bestD, disp);
+                           bestE, bestD, last ? nullptr : disp);
         if (ntiles > 1) {
             XqParams pi{H, W, minD, 1};
-            hipLaunchKernelGGL((k_asw_bilateral_xq<NW, false, 0, true>), dim3(ntiles - 1, H), blk, 0, s, pi, gL, gR, cells, lut,
-                               vol, bestE, bestD, disp);
+            if (last)
+                hipLaunchKernelGGL((k_asw_bilateral_xq<NW, false, 0, true, true>), dim3(ntiles - 1, H), blk, 0, s, pi, gL, gR, cells,
+                                   lut, vol, bestE, bestD, disp);
+            else
+                hipLaunchKernelGGL((k_asw_bilateral_xq<NW, false, 0, true>), dim3(ntiles - 1, H), blk, 0, s, pi, gL, gR, cells, lut,
+                                   vol, bestE, bestD, disp);
         }
         ASW_HIP_TRY(hipGetLastError());
         return ASW_OK;
@@ -573,11 +703,16 @@ int launch_xq_t(hipStream_t s, hipStream_t s_border, const uint8_t* gL, const ui
     auto ke = k_asw_bilateral_xq<NW, true, 0, false>;
     if (n_int > 0) {
         XqParams p{H, W, minD, 0};
-        hipLaunchKernelGGL(ki, dim3(n_int, H), blk, 0, s, p, gL, gR, cells, lut, vol, bestE, bestD, disp);
+        if (last)
+            hipLaunchKernelGGL((k_asw_bilateral_xq<NW, false, 0, false, true>), dim3(n_int, H), blk, 0, s, p, gL, gR, cells, lut, vol,
+                               bestE, bestD, disp);
+        else
+            hipLaunchKernelGGL(ki, dim3(n_int, H), blk, 0, s, p, gL, gR, cells, lut, vol, bestE, bestD, disp);
     }
     if (ntiles > n_int) {
         XqParams p{H, W, minD, n_int};
-        hipLaunchKernelGGL(ke, dim3(ntiles - n_int, H), blk, 0, s_border, p, gL, gR, cells, lut, vol, bestE, bestD, disp);
+        hipLaunchKernelGGL(ke, dim3(ntiles - n_int, H), blk, 0, s_border, p, gL, gR, cells, lut, vol, bestE, bestD,
+                           last ? nullptr : disp);
     }
     ASW_HIP_TRY(hipGetLastError());
     return ASW_OK;
@@ -590,10 +725,25 @@ int launch_xq_t(hipStream_t s, hipStream_t s_border, const uint8_t* gL, const ui
 // disp != nullptr: the launch covers the whole candidate range: write the disparity; else bestE / bestD.
 // s_border: stream of the border-tile launch (may equal s; a side stream lets the 1/30 of the tiles overlap the main launch)
 // right: DISPARITY_RIGHT -- gL is then the fixed (right) image's gray plane and gR the left image's.
+// last: the candidate range is [0, 16 nwave] exactly and bilateral_xq_interior_columns() is not empty: the interior tiles finish
+// it (vol gets plane 16 nwave, disp is written, both for the interior columns only); the border tiles write bestE / bestD.
 int launch_bilateral_xq(hipStream_t s, hipStream_t s_border, int nwave, const uint8_t* gL, const uint8_t* gR, int H, int W, int minD,
-                        const int4* cells, const float* lut, float* vol, double* bestE, float* bestD, float* disp, bool right)
+                        const int4* cells, const float* lut, float* vol, double* bestE, float* bestD, float* disp, bool right, bool last)
 {
-    if (nwave == 8) return launch_xq_t<8>(s, s_border, gL, gR, H, W, minD, cells, lut, vol, bestE, bestD, disp, right);
-    if (nwave == 4) return launch_xq_t<4>(s, s_border, gL, gR, H, W, minD, cells, lut, vol, bestE, bestD, disp, right);
+    if (last && !disp) return ASW_ERR_BAD_ARGUMENT;
+    if (nwave == 8) return launch_xq_t<8>(s, s_border, gL, gR, H, W, minD, cells, lut, vol, bestE, bestD, disp, right, last);
+    if (nwave == 4) return launch_xq_t<4>(s, s_border, gL, gR, H, W, minD, cells, lut, vol, bestE, bestD, disp, right, last);
     return ASW_ERR_BAD_ARGUMENT;
+}
+
+// Image columns [*lo, *hi) of the interior tiles (the rest are the border tiles'); empty when there is no interior tile.
+void bilateral_xq_interior_columns(int W, bool right, int* lo, int* hi)
+{
+    const int ntiles = (W + PXW - 1) / PXW;
+    if (right) {
+        *lo = ntiles > 1 ? PXW : W; *hi = W;
+    } else {
+        const int n_int = W >= PXW + HH ? std::min(ntiles, (W - PXW - HH) / PXW + 1) : 0;
+        *lo = 0; *hi = std::min(W, n_int * PXW);
+    }
 }
