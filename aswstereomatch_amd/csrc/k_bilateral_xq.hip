@@ -53,8 +53,8 @@
 // +0.0 to both sums: the right weight is the all-zero class there, and the left operand is finite -- the ring slots of columns
 // -3..-1 (slots 2..4) are zeroed in the prologue, columns 15..17 find older columns, and the slot index is a non-negative
 // modulus.  Registers are the whole difficulty (wave 0 needs all 128): the LASTC kernels carry nothing that is a function of
-// the lane number through the row loops (FRESH: lane, g, qrel, the packed clamped positions are taken afresh in every step, in
-// all eight wavefronts: about 30 instructions per step each), the unit's wavefront runs with its wave number as a constant (its
+// the lane number through the row loops (FRESH: the lane number is taken afresh in every step, in all eight wavefronts, and what
+// hangs on it -- clamped positions, the row loop's bases -- is read from the step tables), the unit's wavefront runs with its wave number as a constant (its
 // missing staging row folds away), and the other wavefronts' row loops carry nothing of the unit's sums.  Epilogue: sE holds NFIN + 1 planes, plane NFIN goes to vol and enters the
 // WTA last with the same strict '<' (still the first minimum in ascending d), and the kernel writes disp.
 // The border tiles (EDGE; they spill at one row per body and cannot host the unit) keep the slice sequence on their own
@@ -97,7 +97,8 @@ constexpr int LWP = 80;                   // u32 row stride of the left gray til
 //   RWC   right tile columns [posmin - 7, posmin + NPOS + 6]
 //   NFIN  candidates [0, NFIN) are finished by the kernel
 // LDS layout (bytes): left block [KS] x {float [RING][PXW] left weights, u32 [LWP] left gray} | right block [KS] x {float [2][NPOS]
-// right weights, u32 [RWP] right gray} | u8 [KS][LW8] | u8 [KS][RW8] | u16 [NCELLCOL * KS] packed cell table.  Weights and
+// right weights, u32 [RWP] right gray} | u8 [KS][LW8] | u8 [KS][RW8] | u8 [4][64] lane table | u16 [3][64] row-loop bases |
+// u32 [NCELLCOL * KS] cell table (the three tables: see "Step tables" below).  Weights and
 // grays of a window row share one row stride per side, so that every LDS address of the row loop is one of two per-lane bases
 // (three in wave 0) plus an immediate offset: two address increments per body of three rows.
 // Epilogue (over the dead tiles): double [NFIN + 1][PXW] E | per-part WTA partials double E[NW][PXW], float d[NW][PXW].
@@ -123,23 +124,31 @@ struct XqCfg {
     static constexpr int OFF_RB = OFF_LB + KS * LROW * 4;
     static constexpr int OFF_L8 = OFF_RB + KS * RROW * 4;
     static constexpr int OFF_R8 = OFF_L8 + KS * LW8;
-    static constexpr int OFF_CELL = OFF_R8 + KS * RW8;
+    // (the cell table last: its addresses are built from a constant in a register anyway, the other two tables' have to fit the
+    // 16-bit offset field next to the lane number)
+    static constexpr int OFF_LANE = OFF_R8 + KS * RW8;
+    static constexpr int OFF_BASE = OFF_LANE + 4 * 64;
+    static constexpr int OFF_CELL = OFF_BASE + 3 * 64 * 2;
+    static constexpr int OFF_STEP_END = OFF_CELL + NCELLCOL * KS * 4;
     static constexpr int OFF_E64 = 0;
     static constexpr int OFF_PART = (NFIN + 1) * PXW * 8;  // plane NFIN: the last-candidate units' (LASTC)
     // the epilogue buffers reuse the dead tiles; for NW = 8 they are the larger of the two
-    static constexpr int LDS_TOTAL = std::max((OFF_CELL + NCELLCOL * KS * 2 + 15) / 16 * 16, OFF_PART + NW * PXW * 12);
+    static constexpr int LDS_TOTAL = std::max((OFF_STEP_END + 15) / 16 * 16, OFF_PART + NW * PXW * 12);
     static_assert(LDS_TOTAL <= (NW == 8 ? 80 : 53) * 1024, "two (NW = 8) / three (NW = 4) workgroups per CU");
     static_assert(OFF_RB % 16 == 0 && (LROW * 4) % 16 == 0 && (RROW * 4) % 16 == 0 && (NPOS * 4) % 16 == 0 && (LGRAY * 4) % 16 == 0, "b128 alignment");
-    static_assert(NPOS % 64 == 0, "positions are staged in whole wavefront passes");
+    static_assert(NPOS % 64 == 0 && NPOS / 64 <= 3, "positions are staged in whole wavefront passes; three columns of the lane table");
+    static_assert(OFF_CELL % 4 == 0 && OFF_BASE % 2 == 0 && OFF_CELL < 65536 && OFF_RB + 4 * NPOS < 65536, "table alignment; offset fields; u16 bases");
+    static_assert((2 * HH) * LW8 + 2 * HH < (1 << 11) && (2 * HH) * RW8 + 2 * HH < (1 << 12), "cell entry fields");
 };
 #define XQ_CONSTS(NW)                                                                                                           \
     typedef XqCfg<NW> Cfg;                                                                                                       \
     constexpr int NWAVE = Cfg::NWAVE, NTHR = Cfg::NTHR, NJ = Cfg::NJ, NPOS = Cfg::NPOS, RWC = Cfg::RWC, NFIN = Cfg::NFIN, RW8 = Cfg::RW8,      \
                   NROWS = Cfg::NROWS, LROW = Cfg::LROW, RROW = Cfg::RROW, LGRAY = Cfg::LGRAY, RGRAY = Cfg::RGRAY,               \
                   OFF_LB = Cfg::OFF_LB, OFF_RB = Cfg::OFF_RB, OFF_L8 = Cfg::OFF_L8, OFF_R8 = Cfg::OFF_R8, OFF_CELL = Cfg::OFF_CELL,  \
+                  OFF_LANE = Cfg::OFF_LANE, OFF_BASE = Cfg::OFF_BASE,                                                            \
                   LDS_TOTAL = Cfg::LDS_TOTAL, OFF_E64 = Cfg::OFF_E64, OFF_PART = Cfg::OFF_PART;                                  \
     (void)NWAVE; (void)NTHR; (void)NJ; (void)NPOS; (void)RWC; (void)NFIN; (void)RW8; (void)NROWS; (void)LROW; (void)RROW; (void)LGRAY;  \
-    (void)RGRAY; (void)OFF_LB; (void)OFF_RB; (void)OFF_L8; (void)OFF_R8; (void)OFF_CELL; (void)LDS_TOTAL; (void)OFF_E64; (void)OFF_PART;
+    (void)RGRAY; (void)OFF_LB; (void)OFF_RB; (void)OFF_L8; (void)OFF_R8; (void)OFF_CELL; (void)OFF_LANE; (void)OFF_BASE; (void)LDS_TOTAL; (void)OFF_E64; (void)OFF_PART;
 
 struct XqParams {
     int H, W, minD;
@@ -155,15 +164,21 @@ __device__ __forceinline__ double cost_sample(uint32_t gl, uint32_t gr, uint32_t
     return __builtin_bit_cast(double, (uint64_t)c | ((uint64_t)hi0 << 32));
 }
 
-// packed cell table in LDS: (dxw + 8) | (dyw + 8) << 4 | class << 8
-template <int NW>
-__device__ __forceinline__ void cell_at(const unsigned char* smem, int idx, int& dxw, int& dyw, int& cls256)
+// Step tables: everything a step needs that depends on the window cell, the lane and two workgroup-uniform clamps only is
+// built once in the prologue and looked up in every step, instead of being derived again 18 times.
+//   cell table  u32 per cell (kx = -3..17, ky): the byte offsets of the weight's neighbour sample in the u8 gray tiles, relative
+//               to the tile column of the pixel / position itself -- left (HH + dyw) * LW8 + HH + dxw (11 bits: bits 0..7 and
+//               16..18), right (HH + dyw) * RW8 + HH + dxw (bits 20..31) -- and the class in its place in the LUT index (bits
+//               8..15).  The right fields, the ones every lane decodes, cost one instruction each; the left entry is
+//               wave-uniform and is taken apart by the scalar unit.
+//   lane table  u8 [4][64]: columns r3 = 0..2 the clamped position of lane + 64 r3, column 3 the lane's cell-table skew
+//               4 KS (lane & 3) (its positions run lane & 3 tap columns behind the step counter)
+//   bases       u16 [3][64]: the row loop's LDS bases of a lane: left 16 g, right OFF_RB + 4 qrel and wave 0's wrapped
+//               OFF_RB + 4 qrel2, the right ones for wave 0 (wavefront w is 64 w bytes below (LEFT) / above (RIGHT) them)
+__host__ __device__ constexpr uint32_t cell_entry(int dxw, int dyw, int cls256, int RW8)
 {
-    XQ_CONSTS(NW)
-    const uint32_t u = reinterpret_cast<const uint16_t*>(smem + OFF_CELL)[idx];
-    dxw = (int)(u & 15u) - 8;
-    dyw = (int)((u >> 4) & 15u) - 8;
-    cls256 = (int)(u >> 8) << 8;
+    const uint32_t loff = (uint32_t)((HH + dyw) * LW8 + HH + dxw), roff = (uint32_t)((HH + dyw) * RW8 + HH + dxw);
+    return (loff & 255u) | (uint32_t)cls256 | ((loff >> 8) << 16) | (roff << 20);
 }
 
 // Stage the weights step `Kn` consumes: left tap column Kn (ring slot Kn % RING) and the right buffer Kn & 1.
@@ -178,31 +193,43 @@ template <int NW> struct Staged { float v[XqCfg<NW>::NROWS][1 + XqCfg<NW>::NPOS 
 
 template <int NW>
 __device__ __forceinline__ void stage_issue(int Kn, const float* __restrict__ lut, const unsigned char* smem, int wave, int lane,
-                                            uint32_t ppack, Staged<NW>& st)
+                                            Staged<NW>& st)
 {
     XQ_CONSTS(NW)
     const uint8_t* sL8 = smem + OFF_L8;
     const uint8_t* sR8 = smem + OFF_R8;
+    const uint8_t* sLane = smem + OFF_LANE;
+    // the weight is evaluated AT max(0, x - d) (M.cpp:1105); its neighbour is clamped from there (tile columns are
+    // replicate-clamped, so adding the direction needs no further clamp)
+    int pc[NPOS / 64], ctr[NPOS / 64];  // clamped position of lane + 64 r3 and the gray there
+#pragma unroll
+    for (int r3 = 0; r3 < NPOS / 64; r3++) pc[r3] = sLane[64 * r3 + lane];
+    // posmin == Q (mod 4): the unit row b = lane & 3 a position belongs to is a property of the position; skew = 4 KS b
+    const int skew = sLane[64 * 3 + lane];
+#pragma unroll
+    for (int r3 = 0; r3 < NPOS / 64; r3++) ctr[r3] = sR8[HH * RW8 + HH + pc[r3]];
+    const int ctrL = Kn < KS ? sL8[HH * LW8 + HH + lane] : 0;
+    // the lane's cell entry of the wavefront's first row; the other rows are NWAVE entries on (opaque: one address per step)
+    typedef __attribute__((address_space(3))) const unsigned char lds_u8;
+    lds_u8* pcell = (lds_u8*)smem + OFF_CELL + 4 * ((Kn + 3) * KS + wave) - skew;
+    asm("" : "+v"(pcell));
 #pragma unroll
     for (int rr = 0; rr < NROWS; rr++) {
         const int ky = wave + NWAVE * rr;
         if (ky >= KS) break;  // wave-uniform
-        int dxw, dyw, cls;
+        const uint32_t u = *(const __attribute__((address_space(3))) uint32_t*)(pcell + 4 * NWAVE * rr);
         if (Kn < KS) {        // left column Kn exists
-            cell_at<NW>(smem, (Kn + 3) * KS + ky, dxw, dyw, cls);
-            const int nb = sL8[(HH + dyw) * LW8 + (lane + HH + dxw)];
-            st.v[rr][0] = lut_at(lut, __builtin_amdgcn_sad_u16(nb, sL8[HH * LW8 + lane + HH], cls));
+            // its entry is the one of the lanes with b = 0, lane 0 among them (every lane of the wavefront is active here): taken
+            // from there as a scalar, it is decoded by the scalar unit
+            const uint32_t u0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)u);
+            const int nb = sL8[((u0 & 255u) | ((u0 >> 8) & 0x700u)) + lane];
+            st.v[rr][0] = lut_at(lut, __builtin_amdgcn_sad_u16(nb, ctrL, u0 & 0xff00u));
         }
+        const int roff = (int)(u >> 20), cls = (int)(u & 0xff00u);
 #pragma unroll
         for (int r3 = 0; r3 < NPOS / 64; r3++) {
-            const int b = lane & 3;  // of p = lane + 64 * r3; posmin == Q (mod 4): the unit row a position belongs to is a property of the position
-            cell_at<NW>(smem, (Kn - b + 3) * KS + ky, dxw, dyw, cls);
-            // the weight is evaluated AT max(0, x - d) (M.cpp:1105); its neighbour is clamped from there (tile columns are
-            // replicate-clamped, so adding the direction needs no further clamp)
-            const int pc = (int)((ppack >> (8 * r3)) & 255u) + HH;  // tile column of the clamped position
-            const int ctr = sR8[HH * RW8 + pc];
-            const int nb = sR8[(HH + dyw) * RW8 + pc + dxw];
-            st.v[rr][1 + r3] = lut_at(lut, __builtin_amdgcn_sad_u16(nb, ctr, cls));
+            const int nb = sR8[roff + pc[r3]];
+            st.v[rr][1 + r3] = lut_at(lut, __builtin_amdgcn_sad_u16(nb, ctr[r3], cls));
         }
     }
 }
@@ -211,44 +238,41 @@ template <int NW>
 __device__ __forceinline__ void stage_commit(int Kn, unsigned char* smem, int wave, int lane, const Staged<NW>& st)
 {
     XQ_CONSTS(NW)
-    float* sWL = reinterpret_cast<float*>(smem + OFF_LB) + (Kn % RING) * PXW;
-    float* sWR = reinterpret_cast<float*>(smem + OFF_RB) + (Kn & 1) * NPOS;
+    // one address per side (the lane's word in the wavefront's first row), everything else in the offset fields.  The right one
+    // stands OFF_RB % 256 bytes in, so that what the offsets add is a multiple of 256 and pairs of stores need no base of their own.
+    typedef __attribute__((address_space(3))) float lds_f32;
+    typedef __attribute__((address_space(3))) unsigned char lds_u8w;
+    lds_u8w* cL = (lds_u8w*)smem + 4 * LROW * wave + 4 * lane;
+    lds_u8w* cR = (lds_u8w*)smem + 4 * RROW * wave + 4 * lane + OFF_RB % 256;
+    asm("" : "+v"(cL), "+v"(cR));
 #pragma unroll
     for (int rr = 0; rr < NROWS; rr++) {
         const int ky = wave + NWAVE * rr;
         if (ky >= KS) break;
-        if (Kn < KS) sWL[ky * LROW + lane] = st.v[rr][0];
+        if (Kn < KS) *(lds_f32*)(cL + OFF_LB + 4 * (Kn % RING) * PXW + 4 * LROW * NWAVE * rr) = st.v[rr][0];
 #pragma unroll
-        for (int r3 = 0; r3 < NPOS / 64; r3++) sWR[ky * RROW + lane + 64 * r3] = st.v[rr][1 + r3];
+        for (int r3 = 0; r3 < NPOS / 64; r3++)
+            *(lds_f32*)(cR + (OFF_RB - OFF_RB % 256) + 4 * (Kn & 1) * NPOS + 4 * RROW * NWAVE * rr + 4 * 64 * r3) = st.v[rr][1 + r3];
     }
 }
 
 template <int NW>
-__device__ __forceinline__ void stage_weights(int Kn, const float* __restrict__ lut, unsigned char* smem, int wave, int lane,
-                                              uint32_t ppack)
+__device__ __forceinline__ void stage_weights(int Kn, const float* __restrict__ lut, unsigned char* smem, int wave, int lane)
 {
     Staged<NW> st;
-    stage_issue<NW>(Kn, lut, smem, wave, lane, ppack, st);
+    stage_issue<NW>(Kn, lut, smem, wave, lane, st);
     stage_commit<NW>(Kn, smem, wave, lane, st);
 }
 
-// LASTC kernels (FRESH) take everything that is a function of the lane number -- the lane number itself, g, qrel, the packed clamped
-// positions -- afresh in every step instead of carrying it through the row loops, in ALL wavefronts of those kernels (one register
-// file size serves every path): about a dozen instructions per step and wavefront buy the registers the unit's sums need.
+// LASTC kernels (FRESH) carry nothing that is a function of the lane number through the row loops: the lane number is taken
+// afresh in every step (and once more at the mid-step commit) and the row loop's bases are read from the bases table, in ALL
+// wavefronts of those kernels (one register file size serves every path): a handful of instructions per step and wavefront buy
+// the registers the unit's sums need.
 __device__ __forceinline__ int fresh_lane()
 {
     int l;
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=&v"(l));
     return l;
-}
-template <int NPOS>
-__device__ __forceinline__ uint32_t pack_positions(int lane, int pclamp_lo, int pclamp_hi)
-{
-    uint32_t ppack = 0;
-#pragma unroll
-    for (int r3 = 0; r3 < NPOS / 64; r3++) ppack |= (uint32_t)min(max(lane + 64 * r3, pclamp_lo), pclamp_hi) << (8 * r3);
-    asm volatile("" : "+v"(ppack));
-    return ppack;
 }
 // The wavefront of the last-candidate units is the last one: plain, on another SIMD than wave 0 (waves w and w + 4 share one),
 // and the one that stages a window row fewer than the others (rows w, w + NW, ... < 15), which pays for most of the unit.
@@ -303,18 +327,17 @@ __device__ __forceinline__ void run_step(unsigned char* smem, int g, int qrel, i
     lds_u8* uL = nullptr; lds_u8* uW = nullptr; lds_u8* uG = nullptr;
     if constexpr (FRESH) {
         static_assert(!EDGE, "interior tiles");
-        const int l2 = fresh_lane();
-        g = (l2 & 7) | ((l2 >> 2) & 8);
-        const int jl = 4 * wave + ((l2 >> 3) & 3);
-        qrel = RIGHT ? 4 * g + 4 * jl : 4 * g + 4 * (NJ - jl);
-        qrel2 = jl == 0 ? (RIGHT ? 4 * g + 4 * NJ : 4 * g) : qrel;
-        bL = (lds_u8*)smem + OFF_LB + 16 * g;
-        bR = (lds_u8*)smem + OFF_RB + 4 * qrel;
-        bR2 = (lds_u8*)smem + OFF_RB + 4 * qrel2;
+        // `lane` is this step's own (run_all_steps); the bases come from the table: wave 0's, 64 w bytes off for wavefront w
+        const uint16_t* sBase = reinterpret_cast<const uint16_t*>(smem + OFF_BASE);
+        const int oL = sBase[lane], oR = sBase[64 + lane] + (RIGHT ? 64 : -64) * wave;
+        bL = (lds_u8*)smem + oL;
+        bR = (lds_u8*)smem + oR;
+        bR2 = WRAPW ? (lds_u8*)smem + sBase[128 + lane] : bR;
+        g = (oL - OFF_LB) >> 4;
     }
     if constexpr (LASTW) {
         static_assert(FRESH, "g is this step's own");
-        const int a = (fresh_lane() >> 3) & 3;
+        const int a = (lane >> 3) & 3;
         // non-negative modulus: columns -3..-1 are the slots the prologue zeroed, 15..17 hold older (finite) columns
         const int slot = a == 0 ? (K + RING) % RING : a == 1 ? (K - 1 + RING) % RING : a == 2 ? (K - 2 + RING) % RING : (K - 3 + RING) % RING;
         uL = (lds_u8*)smem + OFF_LB + 16 * g + 4 * a + 4 * PXW * slot;
@@ -465,16 +488,15 @@ __device__ __forceinline__ void run_step(unsigned char* smem, int g, int qrel, i
 // ABL (timing experiments only, results are wrong): bit 0 = no weight staging after step 0, bit 1 = no barriers between steps
 template <int NW, bool EDGE, bool WRAPW, int ABL, bool RIGHT, bool LASTW = false, bool FRESH = false>
 __device__ __forceinline__ void run_all_steps(unsigned char* smem, const float* __restrict__ lut, int wave, int lane,
-                                              uint32_t ppack, int g, int qrel, int qrel2, int xabs, int dbase, int dbase2,
-                                              int W, int x0, int posmin, double (&num)[4][4], double (&den)[4][4], USums<LASTW>& us, int pclamp_lo = 0,
-                                              int pclamp_hi = 0)
+                                              int g, int qrel, int qrel2, int xabs, int dbase, int dbase2,
+                                              int W, int x0, int posmin, double (&num)[4][4], double (&den)[4][4], USums<LASTW>& us)
 {
     Staged<NW> st;
 #define ASW_XQ_STEP(KK)                                                                                        \
+    if constexpr (FRESH) lane = fresh_lane();  /* once for the staging and the row loop's bases */              \
     if (!(ABL & 1) && (KK) + 1 < NSTEP) {                                                                        \
-        if constexpr (FRESH) { lane = fresh_lane(); ppack = pack_positions<XqCfg<NW>::NPOS>(lane, pclamp_lo, pclamp_hi); }  \
-        if constexpr (EDGE) stage_weights<NW>((KK) + 1, lut, smem, wave, lane, ppack);  /* border tiles: registers are scarcer there */ \
-        else stage_issue<NW>((KK) + 1, lut, smem, wave, lane, ppack, st);                      \
+        if constexpr (EDGE) stage_weights<NW>((KK) + 1, lut, smem, wave, lane);  /* border tiles: registers are scarcer there */ \
+        else stage_issue<NW>((KK) + 1, lut, smem, wave, lane, st);                             \
     }                                                                                                           \
     run_step<NW, (KK), EDGE, WRAPW, (!EDGE && !(ABL & 1) && (KK) + 1 < NSTEP), RIGHT, LASTW, FRESH>(smem, g, qrel, qrel2, xabs, dbase, dbase2, W, x0, \
                                                                            posmin, num, den, us, wave, lane, st); \
@@ -511,33 +533,76 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
         uint8_t* sR8 = smem + OFF_R8;
         uint32_t* sLd = reinterpret_cast<uint32_t*>(smem + OFF_LB) + Cfg::LGRAY;
         uint32_t* sRd = reinterpret_cast<uint32_t*>(smem + OFF_RB) + Cfg::RGRAY;
-        for (int i = tid; i < KS * LWC; i += NTHR) {
-            const int r = i / LWC, c = i - r * LWC;
-            const int yy = min(max(y - HH + r, 0), H - 1), xx = min(max(x0 - HH + c, 0), W - 1);
-            const int v = gL[(size_t)yy * W + xx];
-            sL8[r * LW8 + c] = (uint8_t)v;
-            sLd[r * Cfg::LROW + c] = (uint32_t)v;
+        // wavefront -> window rows r = wave + NWAVE rr, lane -> tile columns lane + 64 k (no division), and every global load of
+        // the thread -- its gray bytes and its cells of the table -- is issued before its first LDS store: one memory round trip
+        // at the head of the workgroup's life.  Every address is clamped into the image, so the lanes and rows past the tile
+        // load too (a byte they do not store).
+        constexpr int NCL = (LWC + 63) / 64, NCR = (RWC + 63) / 64, NCI = (NCELLCOL * KS + NTHR - 1) / NTHR;
+        uint32_t vL[NROWS][NCL], vR[NROWS][NCR];
+        int4 ci[NCI];
+#pragma unroll
+        for (int k = 0; k < NCI; k++) ci[k] = cells[min(tid + NTHR * k, NCELLCOL * KS - 1)];
+#pragma unroll
+        for (int rr = 0; rr < NROWS; rr++) {
+            const int yy = min(max(y - HH + wave + NWAVE * rr, 0), H - 1);  // wave-uniform
+            const uint8_t* rowL = gL + (size_t)yy * W;
+            const uint8_t* rowR = gR + (size_t)yy * W;
+#pragma unroll
+            for (int k = 0; k < NCL; k++) vL[rr][k] = rowL[min(max(x0 - HH + lane + 64 * k, 0), W - 1)];
+#pragma unroll
+            for (int k = 0; k < NCR; k++) vR[rr][k] = rowR[min(max(posmin - HH + lane + 64 * k, 0), W - 1)];
         }
-        for (int i = tid; i < KS * RWC; i += NTHR) {
-            const int r = i / RWC, c = i - r * RWC;
-            const int yy = min(max(y - HH + r, 0), H - 1), xx = min(max(posmin - HH + c, 0), W - 1);
-            const int v = gR[(size_t)yy * W + xx];
-            sR8[r * RW8 + c] = (uint8_t)v;
-            sRd[r * Cfg::RROW + c] = (uint32_t)v;
-        }
-        if constexpr (LASTC) {
-            // ring slots 2..4 stand for tap columns -3..-1 until columns 2..4 are staged (steps 1..3): the last-candidate units
-            // of lanes with a > K read them in steps 0..2 and must find a finite weight there
-            float* sWL = reinterpret_cast<float*>(smem + OFF_LB);
-            for (int i = tid; i < KS * 3 * PXW; i += NTHR) {
-                const int r = i / (3 * PXW), c = i - r * (3 * PXW);
-                sWL[r * Cfg::LROW + 2 * PXW + c] = 0.0f;
+#pragma unroll
+        for (int rr = 0; rr < NROWS; rr++) {
+            const int r = wave + NWAVE * rr;
+            if (r >= KS) break;  // wave-uniform
+#pragma unroll
+            for (int k = 0; k < NCL; k++) {
+                const int c = lane + 64 * k;
+                if (c < LWC) {
+                    sL8[r * LW8 + c] = (uint8_t)vL[rr][k];
+                    sLd[r * Cfg::LROW + c] = vL[rr][k];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < NCR; k++) {
+                const int c = lane + 64 * k;
+                if (c < RWC) {
+                    sR8[r * RW8 + c] = (uint8_t)vR[rr][k];
+                    sRd[r * Cfg::RROW + c] = vR[rr][k];
+                }
+            }
+            if constexpr (LASTC) {
+                // ring slots 2..4 stand for tap columns -3..-1 until columns 2..4 are staged (steps 1..3): the last-candidate units
+                // of lanes with a > K read them in steps 0..2 and must find a finite weight there
+                float* sWL = reinterpret_cast<float*>(smem + OFF_LB);
+#pragma unroll
+                for (int k = 0; k < 3; k++) sWL[r * Cfg::LROW + 2 * PXW + lane + 64 * k] = 0.0f;
             }
         }
-        uint16_t* sCell = reinterpret_cast<uint16_t*>(smem + OFF_CELL);
-        for (int i = tid; i < NCELLCOL * KS; i += NTHR) {
-            const int4 ci = cells[i];
-            sCell[i] = (uint16_t)((uint32_t)(ci.x + 8) | ((uint32_t)(ci.y + 8) << 4) | ((uint32_t)(ci.z >> 8) << 8));
+        // ---- the step tables (see stage_issue)
+        uint32_t* sCell = reinterpret_cast<uint32_t*>(smem + OFF_CELL);
+#pragma unroll
+        for (int k = 0; k < NCI; k++)
+            if (tid + NTHR * k < NCELLCOL * KS) sCell[tid + NTHR * k] = cell_entry(ci[k].x, ci[k].y, ci[k].z, RW8);
+        if (tid < 64) {  // wave 0: tid is the lane number
+            // positions are clamped into the image before the weight is looked up: max(0, x - d) / min(W-1, x + d) (the other
+            // bound only matters for the lanes of a partial tile, whose results are discarded)
+            const int pclamp_lo = min(max(0 - posmin, 0), NPOS - 1), pclamp_hi = min(max(W - 1 - posmin, 0), NPOS - 1);
+            static_assert(NPOS <= 256 && 4 * KS * 3 < 256, "a clamped position and a skew fit a byte");
+            uint8_t* sLane = smem + OFF_LANE;
+#pragma unroll
+            for (int r3 = 0; r3 < NPOS / 64; r3++) sLane[64 * r3 + tid] = (uint8_t)min(max(tid + 64 * r3, pclamp_lo), pclamp_hi);
+            sLane[64 * 3 + tid] = (uint8_t)(4 * KS * (tid & 3));
+            if constexpr (LASTC) {  // the bases of wave 0's lanes (run_step derives the other wavefronts' from them)
+                const int g0 = (tid & 7) | ((tid >> 2) & 8), j0 = (tid >> 3) & 3;
+                const int q0 = RIGHT ? 4 * g0 + 4 * j0 : 4 * g0 + 4 * (NJ - j0);
+                const int q2 = j0 == 0 ? (RIGHT ? 4 * g0 + 4 * NJ : 4 * g0) : q0;
+                uint16_t* sBase = reinterpret_cast<uint16_t*>(smem + OFF_BASE);
+                sBase[tid] = (uint16_t)(OFF_LB + 16 * g0);
+                sBase[64 + tid] = (uint16_t)(OFF_RB + 4 * q0);
+                sBase[128 + tid] = (uint16_t)(OFF_RB + 4 * q2);
+            }
         }
     }
     __syncthreads();
@@ -555,14 +620,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
     const int xabs = x0 + 4 * g;                           // X
     const int dbase = p.minD + 4 * jl;                     // d of the diagonal a == b
     const int dbase2 = jl == 0 ? p.minD + 4 * NJ : dbase;
-    // positions are clamped into the image before the weight is looked up: max(0, x - d) / min(W-1, x + d) (the other bound
-    // only matters for the lanes of a partial tile, whose results are discarded)
-    const int pclamp_lo = min(max(0 - posmin, 0), NPOS - 1), pclamp_hi = min(max(W - 1 - posmin, 0), NPOS - 1);
-    // the clamped positions lane + 64 r this lane stages, one byte each in one register that the compiler cannot take apart
-    // again: left to itself it keeps every clamped position, the bounds and more in registers of their own through all
-    // steps, a dozen of the 128
-    static_assert(NPOS <= 256, "a clamped position fits a byte");
-    const uint32_t ppack = pack_positions<NPOS>(lane, pclamp_lo, pclamp_hi);
 
     double num[4][4], den[4][4];
 #pragma unroll
@@ -572,19 +629,19 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
 
     USums<LASTC> us;  // the last-candidate unit of this lane (LASTC, wave UWAVE)
     USums<false> none;
-    stage_weights<NW>(0, lut, smem, wave, lane, ppack);
+    stage_weights<NW>(0, lut, smem, wave, lane);
     __syncthreads();
     // wave 0 holds the threads of block j = 0 (the wrapped units): its steps load the second right weights / gray; ONE branch
     // around the whole step sequence (a branch per step made the register allocator spill 488 VGPRs)
     if (EDGE || wave == 0)
-        run_all_steps<NW, EDGE, true, ABL, RIGHT, false, LASTC>(smem, lut, wave, lane, ppack, g, qrel, qrel2, xabs, dbase, dbase2, W,
-                                                                 x0, posmin, num, den, none, pclamp_lo, pclamp_hi);
+        run_all_steps<NW, EDGE, true, ABL, RIGHT, false, LASTC>(smem, lut, wave, lane, g, qrel, qrel2, xabs, dbase, dbase2, W,
+                                                                 x0, posmin, num, den, none);
     else if (LASTC && wave == UWAVE<NW>)  // (the wave number as a constant: the staging rows this wavefront does not have fold away)
-        run_all_steps<NW, EDGE, false, ABL, RIGHT, LASTC, LASTC>(smem, lut, UWAVE<NW>, lane, ppack, g, qrel, qrel2, xabs, dbase, dbase2, W,
-                                                                  x0, posmin, num, den, us, pclamp_lo, pclamp_hi);
+        run_all_steps<NW, EDGE, false, ABL, RIGHT, LASTC, LASTC>(smem, lut, UWAVE<NW>, lane, g, qrel, qrel2, xabs, dbase, dbase2, W,
+                                                                  x0, posmin, num, den, us);
     else
-        run_all_steps<NW, EDGE, false, ABL, RIGHT, false, LASTC>(smem, lut, wave, lane, ppack, g, qrel, qrel2, xabs, dbase, dbase2, W,
-                                                                  x0, posmin, num, den, none, pclamp_lo, pclamp_hi);
+        run_all_steps<NW, EDGE, false, ABL, RIGHT, false, LASTC>(smem, lut, wave, lane, g, qrel, qrel2, xabs, dbase, dbase2, W,
+                                                                  x0, posmin, num, den, none);
     // (the last step ended with a barrier: the tiles are dead)
 
     // ---- E = num / den (M.cpp:1111) -> LDS [candidate][pixel]; back from the scaled domain first (both ldexp are exact)
