@@ -26,7 +26,7 @@ __all__ = [
     "computeAdaptiveWeight_geodesic", "getGeodesicDist", "getGuidedFilter", "computeAdaptiveWeight_GuidedF",
     "computeAdaptiveWeight_GuidedF_2", "computeAdaptiveWeight_WeightedMedian", "winnerTakeAll", "last_status",
     "stereoMatchingBatch", "computeAdaptiveWeight_BLO1", "computeAdaptiveWeight_direct8", "computeNCC", "computeNCC_costs",
-    "computeAdaptiveWeight_GuidedF_3", "getDisparity_SGBM", "sgbm", "sgbm_paths", "filterSpeckles", "getDisparity_BM", "stereoBM",
+    "computeAdaptiveWeight_GuidedF_3", "getDisparity_SGBM", "sgbm", "sgbm_paths", "sgbm_census", "filterSpeckles", "getDisparity_BM", "stereoBM",
     "PREFILTER_NORMALIZED_RESPONSE", "PREFILTER_XSOBEL", "refineDisparity", "stereoMatchingRefined",
     "REFINE_GAMMA_C", "REFINE_GAMMA_S", "SUBPIXEL_PARABOLA", "SUBPIXEL_EQUIANGULAR",
     "SGBM_PATH_LR", "SGBM_PATH_RL", "SGBM_PATH_TB", "SGBM_PATH_BT", "SGBM_PATH_TLBR", "SGBM_PATH_TRBL", "SGBM_PATH_BRTL",
@@ -73,6 +73,7 @@ MODE_SGBM_3WAY = 2  # StereoSGBM::MODE_SGBM_3WAY, the one mode asw_sgbm serves
  SGBM_PATH_BLTR) = (1 << _i for _i in range(8))
 SGBM_PATHS_3WAY, SGBM_PATHS_HH4, SGBM_PATHS_SGBM, SGBM_PATHS_HH = 0x07, 0x0F, 0x37, 0xFF
 _SGBM_MODE_PATHS = 0x40000000  # ASW_SGBM_MODE_PATHS: asw_sgbm's mode carrying a path mask, as the header's inline asw_sgbm_paths forms it
+_SGBM_MODE_CENSUS = 0x10000  # ASW_SGBM_MODE_CENSUS: beside _SGBM_MODE_PATHS, the census cost of the header's inline asw_sgbm_census
 _ALG_CROSS_PARAMS = 0x40000000  # ASW_ALG_CROSS_PARAMS
 
 
@@ -336,6 +337,17 @@ class Context:
         mask = 0x100 if int(paths) & ~SGBM_PATHS_HH else int(paths)  # an invalid mask travels as the invalid mask 0x100
         return self._sgbm_call("asw_sgbm_paths", left, right, minDisparity, numDisparities, blockSize, P1, P2, disp12MaxDiff,
                                preFilterCap, uniquenessRatio, speckleWindowSize, speckleRange, _SGBM_MODE_PATHS | mask,
+                               return_cost_volume)
+
+    def sgbm_census(self, left, right, minDisparity, numDisparities, blockSize, P1=0, P2=0, disp12MaxDiff=0, uniquenessRatio=0,
+                    speckleWindowSize=0, speckleRange=0, paths=SGBM_PATHS_HH, return_cost_volume=False):
+        """sgbm_paths with a census cost in place of the prefilter and the Birchfield-Tomasi cost: the
+        block sum of the Hamming distance of the 62-bit census codes of the gray pair, unchanged by a gain or offset between the
+        two cameras.  No preFilterCap; numpy columns <= 10240 (asw_sgbm_census of asw_mi355x.h: asw_sgbm with the request packed
+        into its mode)."""
+        mask = 0x100 if int(paths) & ~SGBM_PATHS_HH else int(paths)  # an invalid mask travels as the invalid mask 0x100
+        return self._sgbm_call("asw_sgbm_census", left, right, minDisparity, numDisparities, blockSize, P1, P2, disp12MaxDiff, 0,
+                               uniquenessRatio, speckleWindowSize, speckleRange, _SGBM_MODE_PATHS | _SGBM_MODE_CENSUS | mask,
                                return_cost_volume)
 
     def _sgbm_call(self, where, left, right, minDisparity, numDisparities, blockSize, P1, P2, disp12MaxDiff, preFilterCap,
@@ -712,6 +724,7 @@ winnerTakeAll = _bind("winnerTakeAll")
 getDisparity_SGBM = _bind("getDisparity_SGBM")
 sgbm = _bind("sgbm")
 sgbm_paths = _bind("sgbm_paths")
+sgbm_census = _bind("sgbm_census")
 filterSpeckles = _bind("filterSpeckles")
 getDisparity_BM = _bind("getDisparity_BM")
 stereoBM = _bind("stereoBM")

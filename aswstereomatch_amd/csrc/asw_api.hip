@@ -587,11 +587,12 @@ static int disp16_finish(asw_ctx* ctx, int launches, asw_image* map, const void*
     return ASW_OK;
 }
 
-// asw_sgbm: mode 2 with the three paths of MODE_SGBM_3WAY, or with the mask that asw_sgbm_paths packed into mode
+// asw_sgbm: mode 2 with the three paths of MODE_SGBM_3WAY, or with the mask that asw_sgbm_paths packed into mode; census: the cost
+// of asw_sgbm_census in place of the prefilter and the Birchfield-Tomasi cost
 static int sgbm_host(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp16, int min_disparity,
                      int num_disparities, int block_size, int p1, int p2, int disp12_max_diff, int pre_filter_cap,
-                     int uniqueness_ratio, int speckle_window_size, int speckle_range, int mode, int paths, float* cost_volume_out,
-                     size_t cost_volume_floats)
+                     int uniqueness_ratio, int speckle_window_size, int speckle_range, int mode, int paths, bool census,
+                     float* cost_volume_out, size_t cost_volume_floats)
 {
     if (!ctx) return ASW_ERR_BAD_ARGUMENT;
     ASW_TRY(check_pair(left, right));
@@ -602,13 +603,14 @@ static int sgbm_host(asw_ctx* ctx, const asw_image* left, const asw_image* right
     SgbmParams p;
     p.minD = min_disparity; p.numD = num_disparities; p.block_size = block_size; p.P1 = p1; p.P2 = p2;
     p.disp12_max_diff = disp12_max_diff; p.pre_filter_cap = pre_filter_cap; p.uniqueness_ratio = uniqueness_ratio;
-    p.speckle_window_size = speckle_window_size; p.speckle_range = speckle_range; p.mode = mode; p.paths = paths;
+    p.speckle_window_size = speckle_window_size; p.speckle_range = speckle_range; p.mode = mode; p.paths = paths; p.census = census;
     ASW_HIP_TRY(hipSetDevice(ctx->device));
     SgbmLaunch a;
     ASW_TRY(sgbm_prepare(ctx, p, H, W, left->channels, cost_volume_out != nullptr, &a));
     Frame* f;
     ASW_TRY(disp16_stage(ctx, left, right, num_disparities, "sgbm_volume", cost_volume_out, cost_volume_floats, &f, &a.vol));
     a.L = f->L.as<uint8_t>(); a.R = f->R.as<uint8_t>();
+    if (census) ASW_TRY(gray_pair(ctx, a.L, a.R, left->channels, H, W, &a.L, &a.R));  // the cost reads one gray plane per image
     a.ev_agg0 = ctx->ev[2]; a.ev_agg1 = ctx->ev[3];
     ASW_TRY(launch_sgbm(ctx->stream, a));
     // k_sgbm_top, k_sgbm_row + one k_sgbm_line per line geometry in use (columns, diagonals, anti-diagonals)
@@ -623,12 +625,14 @@ extern "C" int asw_sgbm(asw_ctx* ctx, const asw_image* left, const asw_image* ri
                         size_t cost_volume_floats)
 {
     int paths = ASW_SGBM_PATHS_3WAY;
+    bool census = false;
     if (mode > 0 && (mode & ASW_SGBM_MODE_PATHS)) {  // asw_sgbm_paths (asw_mi355x.h): the three-path pipeline over a path mask
-        paths = mode & ~ASW_SGBM_MODE_PATHS;
+        census = (mode & ASW_SGBM_MODE_CENSUS) != 0;  // asw_sgbm_census: the same with the census cost
+        paths = mode & ~(ASW_SGBM_MODE_PATHS | ASW_SGBM_MODE_CENSUS);
         mode = 2;
     }
     return sgbm_host(ctx, left, right, disp16, min_disparity, num_disparities, block_size, p1, p2, disp12_max_diff, pre_filter_cap,
-                     uniqueness_ratio, speckle_window_size, speckle_range, mode, paths, cost_volume_out, cost_volume_floats);
+                     uniqueness_ratio, speckle_window_size, speckle_range, mode, paths, census, cost_volume_out, cost_volume_floats);
 }
 
 extern "C" int asw_filter_speckles(asw_ctx* ctx, asw_image* img, int new_val, int max_speckle_size, int max_diff)

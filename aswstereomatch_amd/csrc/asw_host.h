@@ -99,6 +99,7 @@ int run_ncc_cost(asw_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int H, int 
 struct SgbmParams {
     int minD, numD, block_size, P1, P2, disp12_max_diff, pre_filter_cap, uniqueness_ratio, speckle_window_size, speckle_range, mode;
     int paths = ASW_SGBM_PATHS_3WAY;  // the ASW_SGBM_PATH_* mask of asw_sgbm_paths (mode stays 2)
+    bool census = false;              // asw_sgbm_census: the census cost of DESIGN.md section 4.8c in place of steps 1-2 (pre_filter_cap unused)
 };
 int sgbm_prepare(asw_ctx* ctx, const SgbmParams& p, int H, int W, int cn, bool want_volume, SgbmLaunch* out);
 // StereoBM parameters as StereoBM::create + its setters take them; bm_prepare validates them (step 0) and

@@ -333,6 +333,7 @@ struct SgbmLaunch {
     int w, ftzero, P1, P2, U, M;  // effective parameters (step 0)
     int speckle_window, speckle_range;
     int paths = ASW_SGBM_PATHS_3WAY;  // ASW_SGBM_PATH_* mask, a superset of the three (asw_sgbm_paths)
+    bool census = false;  // asw_sgbm_census: L / R are the gray planes of gray_pair, cn and ftzero are not read
     void* scratch;     // sgbm_scratch_bytes()
     short* disp16;     // out [H][W], scaled by 16
     float* vol;        // optional S [D][H][W]

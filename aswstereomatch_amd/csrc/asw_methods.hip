@@ -700,7 +700,7 @@ int sgbm_prepare(asw_ctx* ctx, const SgbmParams& p, int H, int W, int cn, bool w
     if (16 * ((long long)p.minD + p.numD) > 32767) return ASW_ERR_BAD_ARGUMENT;  // the scaled map is int16
     if ((size_t)H * W >= ((size_t)1 << 31)) return ASW_ERR_BAD_ARGUMENT;         // pixel indices of the speckle filter are int
     SgbmLaunch a{};
-    a.H = H; a.W = W; a.cn = cn; a.minD = p.minD; a.D = p.numD; a.paths = p.paths;
+    a.H = H; a.W = W; a.cn = cn; a.minD = p.minD; a.D = p.numD; a.paths = p.paths; a.census = p.census;
     // step 0: StereoSGBM::compute's effective parameters
     a.ftzero = std::max(p.pre_filter_cap, 15) | 1;
     a.P1 = p.P1 > 0 ? p.P1 : 2;
@@ -713,9 +713,11 @@ int sgbm_prepare(asw_ctx* ctx, const SgbmParams& p, int H, int W, int cn, bool w
     if (a.P1 == INT_MAX) return ASW_ERR_BAD_ARGUMENT;  // P2 >= P1 + 1
     // every C, L and S is exact in int32: S <= n * (C_max + P2), n paths; the f32 volume needs the same bound below 2^24
     const double k = 2 * (a.w / 2) + 1;
-    const double bound = (double)__builtin_popcount(p.paths) * ((double)cn * (2.0 * a.ftzero + 63.0) * k * k + a.P2);
+    const double cmax = p.census ? 62.0 * k * k : (double)cn * (2.0 * a.ftzero + 63.0) * k * k;  // census: a Hamming distance per pixel
+    const double bound = (double)__builtin_popcount(p.paths) * (cmax + a.P2);
     if (bound >= 2147483648.0) return ASW_ERR_BAD_ARGUMENT;
     if (want_volume && bound >= 16777216.0) return ASW_ERR_BAD_ARGUMENT;
+    if (p.census && W > 10240) return ASW_ERR_BAD_ARGUMENT;  // k_sgbm_hcost_census stages both code rows in LDS: 16 W bytes <= 160 KB
     DevBuf& scratch = ctx->buf("sgbm_scratch");
     DevBuf& d16 = ctx->buf("sgbm_disp16");
     ASW_TRY(scratch.ensure(sgbm_scratch_bytes(H, W, cn, a.minD, a.D)));

@@ -7,6 +7,7 @@
 //
 //   k_sgbm_prefilter  step 1 + the Birchfield-Tomasi interval: {value, min, max} planes of every prefiltered plane
 //   k_sgbm_hcost      steps 2 + horizontal half of 3: one thread per (y, d) walks the row with a running window sum
+//   k_sgbm_hcost_census  asw_sgbm_census only (section 4.8c): the same hb from the Hamming distance of two census codes
 //   k_sgbm_top        vertical half of 3 + the top->bottom path: one wavefront per column, candidates in lanes
 //   k_sgbm_line       asw_sgbm_paths only: bottom->top and the four diagonal paths, one wavefront per column / (anti-)diagonal
 //   k_sgbm_row        left->right and right->left paths, winner, uniqueness, subpixel, disp2 keys: one wavefront per row
@@ -87,6 +88,48 @@ __global__ __launch_bounds__(256) void k_sgbm_hcost(const int4* __restrict__ pf,
     for (int xi = 0; xi < Wv; xi++) {
         out[(size_t)xi * D] = sum;
         sum += pix(xi + h + 1) - pix(xi - h);
+    }
+}
+
+// asw_sgbm_census: hb of the census cost, pix(y, xi, d) = popcount(codeL[y][x0 + xi] ^ codeR[y][x0 + xi -
+// (minD + d)]) in place of steps 1-2, the same clamped window sum.  One workgroup: one row, both code rows staged in LDS (16 W
+// bytes), and 256 / nd segments of seglen valid columns, nd = min(D, 256) candidates side by side; blockIdx.y continues the
+// segments.  A thread owns (segment, d; d + 256 j when D > 256), seeds its window with 2 h + 1 terms and walks its segment with the
+// running sum: the left code of a step is one address for all candidates of a segment (a broadcast read), the right codes are
+// consecutive words, the stores consecutive in d.
+__global__ __launch_bounds__(256) void k_sgbm_hcost_census(const unsigned long long* __restrict__ codeL,
+                                                           const unsigned long long* __restrict__ codeR, int W, int minD, int D, int h,
+                                                           int seglen, int* __restrict__ hb)
+{
+    extern __shared__ __align__(16) unsigned long long sgbm_code_rows[];  // [2][W]
+    unsigned long long* cl = sgbm_code_rows;
+    unsigned long long* cr = cl + W;
+    const int y = blockIdx.x, tid = threadIdx.x;
+    for (int i = tid; i < W; i += 256) {
+        cl[i] = codeL[(size_t)y * W + i];
+        cr[i] = codeR[(size_t)y * W + i];
+    }
+    __syncthreads();
+    const int x0 = minD + D, Wv = W - x0;
+    const int nd = min(D, 256), spb = 256 / nd;
+    const int sl = tid / nd;
+    if (sl >= spb) return;
+    const int xb = (blockIdx.y * spb + sl) * seglen, xe = min(Wv, xb + seglen);
+    if (xb >= xe) return;
+    const unsigned long long* l = cl + x0;  // l[xi]: the left code of valid column xi
+    for (int d = tid - sl * nd; d < D; d += nd) {
+        const unsigned long long* r = cr + (D - d);  // r[xi]: its partner, column x0 + xi - (minD + d) >= 1
+        auto ham = [&](int xi) {
+            xi = min(max(xi, 0), Wv - 1);
+            return __popcll(l[xi] ^ r[xi]);
+        };
+        int sum = 0;
+        for (int i = -h; i <= h; i++) sum += ham(xb + i);
+        int* out = hb + ((size_t)y * Wv + xb) * D + d;
+        for (int xi = xb; xi < xe; xi++, out += D) {
+            *out = sum;
+            sum += ham(xi + h + 1) - ham(xi - h);
+        }
     }
 }
 
@@ -528,13 +571,40 @@ int launch_paths(hipStream_t s, const SgbmLaunch& a, const int* hb, int* C, int*
     return ASW_OK;
 }
 
+// the census cost stage of asw_sgbm_census: a.L / a.R are the gray planes; codes: room for two code planes (8 bytes a pixel each)
+int launch_hcost_census(hipStream_t s, const SgbmLaunch& a, unsigned long long* codes, int* hb)
+{
+    const int H = a.H, W = a.W, D = a.D, h = a.w / 2;
+    const int Wv = W - (a.minD + D);
+    const size_t plane = (size_t)H * W;
+    unsigned long long* codeL = codes;
+    unsigned long long* codeR = codes + plane;
+    ASW_TRY(launch_census_transform(s, a.L, H, W, reinterpret_cast<uint2*>(codeL)));
+    ASW_TRY(launch_census_transform(s, a.R, H, W, reinterpret_cast<uint2*>(codeR)));
+    const size_t lds = (size_t)W * 16;
+    if (lds > 160 * 1024) return ASW_ERR_BAD_ARGUMENT;
+    if (lds > 64 * 1024)
+        ASW_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sgbm_hcost_census), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)lds));
+    // A row alone gives D threads work: few rows or few candidates leave the chip idle, so the valid columns are cut into
+    // segments until there are about 2048 workgroups.  A segment pays 2 h + 1 terms for its seed: none is shorter than twice that.
+    const int spb = 256 / std::min(D, 256);
+    const int want = spb * ((2048 + H - 1) / H);
+    const int nseg = std::max(1, std::min(want, Wv / std::max(32, 2 * (2 * h + 1))));
+    const int seglen = (Wv + nseg - 1) / nseg;
+    const unsigned gy = (unsigned)((Wv + seglen * spb - 1) / (seglen * spb));
+    hipLaunchKernelGGL(k_sgbm_hcost_census, dim3(H, gy), dim3(256), lds, s, codeL, codeR, W, a.minD, D, h, seglen, hb);
+    ASW_HIP_TRY(hipGetLastError());
+    return ASW_OK;
+}
+
 }  // namespace
 
 size_t sgbm_scratch_bytes(int H, int W, int cn, int minD, int D)
 {
     const size_t Wv = W > minD + D ? (size_t)(W - minD - D) : 0;
     const size_t plane = (size_t)H * W;
-    // hb, C, T volumes | prefiltered planes | disp2 keys | speckle scratch | raw disparities | left-right checked map
+    // hb, C, T volumes | prefiltered planes (asw_sgbm_census: the two code planes, plane * 16 bytes) | disp2 keys | speckle scratch | raw disparities | left-right checked map
     return 3 * ((size_t)H * Wv * D * 4) + plane * 64 * cn + plane * 8 + plane * 8 + plane * 4 + (plane * 2 + 15) / 16 * 16;
 }
 
@@ -562,10 +632,14 @@ int launch_sgbm(hipStream_t s, const SgbmLaunch& a)
     int* spk = (int*)p; p += plane * 8;
     int* disp_raw = (int*)p; p += plane * 4;
     short* lr = (short*)p;
-    hipLaunchKernelGGL(k_sgbm_prefilter, dim3(blocks(plane, 256)), dim3(256), 0, s, a.L, a.R, H, W, a.cn, a.ftzero, pf);
-    ASW_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_sgbm_hcost, dim3(blocks((size_t)H * D, 256)), dim3(256), 0, s, pf, H, W, a.cn, minD, D, a.w / 2, hb);
-    ASW_HIP_TRY(hipGetLastError());
+    if (a.census) {
+        ASW_TRY(launch_hcost_census(s, a, (unsigned long long*)pf, hb));
+    } else {
+        hipLaunchKernelGGL(k_sgbm_prefilter, dim3(blocks(plane, 256)), dim3(256), 0, s, a.L, a.R, H, W, a.cn, a.ftzero, pf);
+        ASW_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_sgbm_hcost, dim3(blocks((size_t)H * D, 256)), dim3(256), 0, s, pf, H, W, a.cn, minD, D, a.w / 2, hb);
+        ASW_HIP_TRY(hipGetLastError());
+    }
     ASW_HIP_TRY(hipMemsetAsync(key, 0xff, plane * 8, s));
     if (a.ev_agg0) ASW_HIP_TRY(hipEventRecord(a.ev_agg0, s));
     ASW_TRY(dispatch_npl(D, [&](auto npl) { return launch_paths<decltype(npl)::value>(s, a, hb, C, T, disp_raw, key); }));

@@ -176,31 +176,30 @@ inline void getDisparity_SGBM(AswMat srcLeft, AswMat srcRight, AswMat& disparity
     disparityMap = asw::detail::f32_to_u8(d);
 }
 
-// Not in the reference: getDisparity_SGBM with the aggregated cost summed over the path directions of `paths` (an OR of
-// ASW_SGBM_PATH_*, asw_sgbm_paths; DESIGN.md section 4.8b) instead of the three of MODE_SGBM_3WAY.  The same StereoSGBM settings,
-// the same CV_8U result (convertTo(CV_8U, 1/16) of the int16 map: round half to even, saturate) and the same throwing behaviour.
-inline void getDisparity_SGBM_paths(AswMat srcLeft, AswMat srcRight, AswMat& disparityMap, int winSize = 15, int minDisparity = 0,
-                                    int numDisparity = 64, int paths = ASW_SGBM_PATHS_HH)
+namespace asw {
+namespace detail {
+// getDisparity_SGBM_paths / getDisparity_SGBM_census: getDisparity_SGBM's argument rules around call(left, right, disp16, w), an
+// asw_sgbm_paths or asw_sgbm_census call, and the CV_8U map of its int16 result (convertTo(CV_8U, 1/16): round half to even, saturate)
+template <typename Call>
+inline void sgbm_u8(const MatT& srcLeft, const MatT& srcRight, MatT& disparityMap, int winSize, int numDisparity, const char* where,
+                    Call call)
 {
-    if (srcLeft.empty() || srcRight.empty()) throw std::runtime_error("getDisparity_SGBM_paths: one of the input images is empty");
     const int w = winSize > 0 ? winSize : 3;
     int rc = numDisparity % 16 != 0 || winSize % 2 == 0 ? ASW_ERR_UNSUPPORTED_METHOD : w > 4096 ? ASW_ERR_BAD_ARGUMENT : ASW_OK;
     const int H = srcLeft.rows, W = srcLeft.cols;
     std::vector<short> d16((size_t)H * W);
     if (rc == ASW_OK) {
-        asw_image li = asw::detail::view(srcLeft), ri = asw::detail::view(srcRight);
+        asw_image li = view(srcLeft), ri = view(srcRight);
         asw_image di{d16.data(), H, W, 1, ASW_16S, (size_t)W * sizeof(short)};
-        const int cn = li.channels;
-        rc = asw_sgbm_paths(asw::detail::context(), &li, &ri, &di, minDisparity, numDisparity, w, 8 * cn * w * w, 32 * cn * w * w, 200,
-                            10, 10, 175, 32, paths, nullptr, 0);
+        rc = call(&li, &ri, &di, w);
     }
-    asw::detail::raise_unless_ok(rc, "getDisparity_SGBM_paths");
+    raise_unless_ok(rc, where);
     if (rc != ASW_OK) {
-        disparityMap = AswMat();
+        disparityMap = MatT();
         return;
     }
-    AswMat u = asw::detail::make(H, W, ASW_8U, 1);
-    asw_image ui = asw::detail::view(u);
+    MatT u = make(H, W, ASW_8U, 1);
+    asw_image ui = view(u);
     for (int y = 0; y < H; y++) {
         uint8_t* dst = (uint8_t*)ui.data + (size_t)y * ui.step;
         for (int x = 0; x < W; x++) {
@@ -210,6 +209,39 @@ inline void getDisparity_SGBM_paths(AswMat srcLeft, AswMat srcRight, AswMat& dis
         }
     }
     disparityMap = u;
+}
+}  // namespace detail
+}  // namespace asw
+
+// Not in the reference: getDisparity_SGBM with the aggregated cost summed over the path directions of `paths` (an OR of
+// ASW_SGBM_PATH_*, asw_sgbm_paths; DESIGN.md section 4.8b) instead of the three of MODE_SGBM_3WAY.  The same StereoSGBM settings,
+// the same CV_8U result (convertTo(CV_8U, 1/16) of the int16 map: round half to even, saturate) and the same throwing behaviour.
+inline void getDisparity_SGBM_paths(AswMat srcLeft, AswMat srcRight, AswMat& disparityMap, int winSize = 15, int minDisparity = 0,
+                                    int numDisparity = 64, int paths = ASW_SGBM_PATHS_HH)
+{
+    if (srcLeft.empty() || srcRight.empty()) throw std::runtime_error("getDisparity_SGBM_paths: one of the input images is empty");
+    asw::detail::sgbm_u8(srcLeft, srcRight, disparityMap, winSize, numDisparity, "getDisparity_SGBM_paths",
+                         [&](asw_image* li, asw_image* ri, asw_image* di, int w) {
+                             const int cn = li->channels;
+                             return asw_sgbm_paths(asw::detail::context(), li, ri, di, minDisparity, numDisparity, w, 8 * cn * w * w,
+                                                   32 * cn * w * w, 200, 10, 10, 175, 32, paths, nullptr, 0);
+                         });
+}
+
+// Not in the reference: getDisparity_SGBM_paths with the census cost of asw_sgbm_census in place of the
+// prefilter and the Birchfield-Tomasi cost.  getDisparity_SGBM's settings with the penalties of one plane, P1 = 8 w^2 and P2 = 32 w^2
+// whatever the channel count (the cost comes from one gray plane), uniqueness 10, speckles 175 / 32, disp12MaxDiff 200.  The
+// penalties are a stated choice, carried over from the Birchfield-Tomasi cost, not a tuned one: a census pixel cost ranges over
+// 0..62.  The same CV_8U result and the same throwing behaviour.
+inline void getDisparity_SGBM_census(AswMat srcLeft, AswMat srcRight, AswMat& disparityMap, int winSize = 15, int minDisparity = 0,
+                                     int numDisparity = 64, int paths = ASW_SGBM_PATHS_HH)
+{
+    if (srcLeft.empty() || srcRight.empty()) throw std::runtime_error("getDisparity_SGBM_census: one of the input images is empty");
+    asw::detail::sgbm_u8(srcLeft, srcRight, disparityMap, winSize, numDisparity, "getDisparity_SGBM_census",
+                         [&](asw_image* li, asw_image* ri, asw_image* di, int w) {
+                             return asw_sgbm_census(asw::detail::context(), li, ri, di, minDisparity, numDisparity, w, 8 * w * w,
+                                                    32 * w * w, 200, 10, 175, 32, paths, nullptr, 0);
+                         });
 }
 
 // M.h:93 / aswMethods.cpp:100-146: StereoBM (PREFILTER_XSOBEL) with the reference's settings, CV_8U result; a 3-channel image is

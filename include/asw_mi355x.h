@@ -389,7 +389,7 @@ int asw_bgr2gray(asw_ctx* ctx, const asw_image* bgr, uint8_t* gray);
  * the reference) give ASW_ERR_UNSUPPORTED_METHOD; disparity_type is ignored (the left-view map); it has no cost volume.
  * asw_sgbm: StereoSGBM::create(min_disparity, num_disparities, block_size, p1, p2, disp12_max_diff, pre_filter_cap, uniqueness_ratio,
  * speckle_window_size, speckle_range, mode) + compute().  disp16: ASW_16S, 1 channel (else ASW_ERR_UNSUPPORTED_LAYOUT, as for
- * asw_filter_speckles), rows x cols: disparity x 16, invalid pixels 16 * (min_disparity - 1).  mode: 2 (MODE_SGBM_3WAY), or the value asw_sgbm_paths below forms; else ASW_ERR_UNSUPPORTED_METHOD.  num_disparities: a positive multiple of
+ * asw_filter_speckles), rows x cols: disparity x 16, invalid pixels 16 * (min_disparity - 1).  mode: 2 (MODE_SGBM_3WAY), or the value asw_sgbm_paths or asw_sgbm_census below forms; else ASW_ERR_UNSUPPORTED_METHOD.  num_disparities: a positive multiple of
  * 16, at most 1024; min_disparity >= 0; 16 * (min_disparity + num_disparities) <= 32767; 1 or 3 channels.  Parameters for which a sum
  * could leave int32 (3 * (C_max + P2) >= 2^31, C_max = cn * (2 * ftzero + 63) * w^2) are refused with ASW_ERR_BAD_ARGUMENT.
  * cost_volume_out (optional): the aggregated cost S of the three paths, f32 [num_disparities][rows][cols] (plane k <-> disparity
@@ -434,6 +434,32 @@ static inline int asw_sgbm_paths(asw_ctx* ctx, const asw_image* left, const asw_
     return asw_sgbm(ctx, left, right, disp16, min_disparity, num_disparities, block_size, p1, p2, disp12_max_diff, pre_filter_cap,
                     uniqueness_ratio, speckle_window_size, speckle_range, ASW_SGBM_MODE_PATHS | mask, cost_volume_out,
                     cost_volume_floats);
+}
+/* asw_sgbm_census: asw_sgbm_paths with a census cost in place of the prefilter and the Birchfield-Tomasi pixel cost (DESIGN.md section
+ * 4.8c), for pairs whose cameras differ in gain or offset: the cost compares the order of intensities, not the intensities.  With
+ * x0 = min_disparity + num_disparities, Wv = cols - x0, h = w / 2, w the effective block size:
+ *   1. gray: a 3-channel image goes through cvtColor(BGR2GRAY) (asw_set_gray_bits applies), a 1-channel image is used as it is;
+ *   2. codeL, codeR: the 62-bit census code of every pixel of the whole image (the code of asw_cost_census: a 9 x 7 window, clamped at
+ *      the border, strict '<');
+ *   3. pix(y, xi, d) = popcount(codeL[y][x0 + xi] ^ codeR[y][x0 + xi - (min_disparity + d)]), 0..62, on the valid columns;
+ *   4. C(y, xi, d) = the sum of pix over |i|, |j| <= h, xi clamped to [0, Wv - 1] and y to [0, rows - 1], as asw_sgbm clamps;
+ *   5. paths over the mask, winner, uniqueness, sub-pixel fit, left-right rule, median and speckles are asw_sgbm_paths'.
+ * There is no pre_filter_cap.  C_max = 62 * k^2, k = 2 h + 1, whatever the channel count: n * (C_max + P2) >= 2^31, n paths, is
+ * refused with ASW_ERR_BAD_ARGUMENT, and with a volume the same bound at 2^24.  cols > 10240 (both code rows of a frame row are
+ * staged in 160 KB of LDS): ASW_ERR_BAD_ARGUMENT, after the other argument checks.  Every other argument and status is
+ * asw_sgbm_paths', in the same order.  Like it an inline function of this header: the request travels in asw_sgbm's mode as
+ * ASW_SGBM_MODE_PATHS | ASW_SGBM_MODE_CENSUS | paths, pre_filter_cap 0 (asw_sgbm ignores it under this mode), an out-of-range mask
+ * as 0x100.  ASW_SGBM_MODE_CENSUS without ASW_SGBM_MODE_PATHS is no mode: ASW_ERR_UNSUPPORTED_METHOD. */
+enum { ASW_SGBM_MODE_CENSUS = 0x10000 }; /* asw_sgbm's mode, beside ASW_SGBM_MODE_PATHS: the census cost */
+static inline int asw_sgbm_census(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp16, int min_disparity,
+                                  int num_disparities, int block_size, int p1, int p2, int disp12_max_diff, int uniqueness_ratio,
+                                  int speckle_window_size, int speckle_range, int paths, float* cost_volume_out,
+                                  size_t cost_volume_floats)
+{
+    const int mask = (paths & ~ASW_SGBM_PATHS_HH) ? 0x100 : paths;
+    return asw_sgbm(ctx, left, right, disp16, min_disparity, num_disparities, block_size, p1, p2, disp12_max_diff, 0,
+                    uniqueness_ratio, speckle_window_size, speckle_range, ASW_SGBM_MODE_PATHS | ASW_SGBM_MODE_CENSUS | mask,
+                    cost_volume_out, cost_volume_floats);
 }
 /* cv::filterSpeckles, in place: 4-connected components of pixels != new_val whose neighbours differ by at most max_diff; every
  * component of at most max_speckle_size pixels becomes new_val.  img: ASW_16S, 1 channel (ASW_8U: ASW_ERR_UNSUPPORTED_LAYOUT). */

@@ -25,6 +25,12 @@ The leg adcensus is AD-Census matching (asw_alg_adcensus: the census + AD cost u
 tests/adcensus_ref.py in the same way; its cases are the cross cases plus random lambdas (adcensus_ref.random_case / build_case).
 
     python tools/fuzz_parity.py --seconds 120 --seed 1 --only adcensus
+
+The leg sgbm_census is asw_sgbm_census against tests/sgbm_census_ref.py, map and volume, with and without
+the kept volume: the sgbm_paths cases of matcher_cases.random_case sent through the census cost (their preFilterCap is dropped); a
+mismatch prints the tag matcher_cases.build_case("sgbm_paths", tag[1:]) rebuilds.
+
+    python tools/fuzz_parity.py --seconds 120 --seed 1 --only sgbm_census
 """
 import argparse
 import os
@@ -42,11 +48,31 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import adcensus_ref as ac  # noqa: E402
 import cross_ref as cr  # noqa: E402
 import matcher_cases as mc  # noqa: E402
+import sgbm_census_ref as scr  # noqa: E402
 
 A = asw.StereoMatchingAlgorithms
+
+
+class SgbmCensusLeg:
+    """the leg sgbm_census: random_case / gpu_result in the manner of cross_ref and adcensus_ref"""
+
+    @staticmethod
+    def random_case(rng, n=0):
+        return mc.random_case(rng, "sgbm_paths", n)
+
+    @staticmethod
+    def gpu_result(ctx, case):
+        minD, D, w, P1, P2, m12, _cap, U, sw, sr = case["args"]
+        want = scr.sgbm_census(case["L"], case["R"], minD, D, w, P1, P2, m12, U, sw, sr, case["paths"])
+        d, v = ctx.sgbm_census(case["L"], case["R"], minD, D, w, P1, P2, m12, U, sw, sr, paths=case["paths"], return_cost_volume=True)
+        d2 = ctx.sgbm_census(case["L"], case["R"], minD, D, w, P1, P2, m12, U, sw, sr, paths=case["paths"])
+        return (v, d, d2), (np.moveaxis(want["S"], 2, 0).astype(np.float32), want["disp"])
+
+
 # checked against the CPU oracle (oracle/); the legs (mc.FAMILIES) are checked against the restatements under tests/
-LEGS = tuple(mc.FAMILIES) + ("cross", "adcensus")
-REF_LEGS = {"cross": cr, "adcensus": ac}  # legs whose module has random_case / gpu_result of its own
+LEGS = tuple(mc.FAMILIES) + ("cross", "adcensus", "sgbm_census")
+# legs whose module has random_case / gpu_result of its own
+REF_LEGS = {"cross": cr, "adcensus": ac, "sgbm_census": SgbmCensusLeg}
 ORACLE_METHODS = ["classic", "direct8", "geodesic", "guided", "guided2", "guided3", "wmedian", "blo1", "ncc", "ncc_cost",
                   "ad_tad", "similarity", "sad", "geodist", "gfilter", "prep", "bilgrid", "lrcheck", "resident", "batch"]
 
