@@ -59,13 +59,13 @@ struct BilateralTables {  // cached per (kind, win, gamma_c, gamma_g, mirror)
 };
 
 // Measurement / test switches, read from the environment ONCE when a context is created (asw_create): a call never looks at
-// the environment.  -1 / 0 = the library's own choice.
+// the environment.  -1 / 0 = the library's own choice.  A switch stays only while a GPU test sets it
+// (tests/test_tuning_switches_cpu.py): the form it selects is otherwise code nothing checks.
 struct AswTuning {
     int bilateral_xq = -1;       // ASW_BILATERAL_XQ: 0 = one-kernel form only (k_asw_bilateral), 1 = xq form wherever it applies
     int geodesic_xq = -1;        // ASW_GEODESIC_XQ
     int wmedian_tile = -1;       // ASW_WMEDIAN_TILE: 0 = per-pixel sort (k_wmedian)
     int wmedian_tile_chunk = 0;  // ASW_WMEDIAN_TILE_CHUNK: slices per list chunk (tests: odd chunkings)
-    int wmedian_tile_split = 0;  // ASW_WMEDIAN_TILE_SPLIT: workgroups per pixel block
     int wmedian_gen_rows = 0;    // ASW_WMEDIAN_GEN_ROWS: block rows per workgroup of the general tile form (windows 17..37): 1 | 2 | 4 | 8
     int band_ab = 0, band_q = 0; // ASW_BAND_AB / ASW_BAND_Q: rows per band of the guided filter's passes
     int ring_ab = 1, ring_q = 1; // ASW_RING_AB / ASW_RING_Q: register-ring form of the two passes (k_guided.hip: launch_guided3), 0 = re-fetch
@@ -263,7 +263,7 @@ int launch_wmedian(hipStream_t s, const float* cost, const float* wLd, const flo
                    int max_off, float* out);
 size_t wmedian_tile_list_slots(int H, int W, int d_count);
 int launch_wmedian_tile(hipStream_t s, const float* cost, const float* wLd, const float* wRb, int H, int W, int numD, int max_off,
-                        int d_begin, int d_count, uint32_t* listC, uint16_t* listP, float* out, int nsplit /* A/B: AswTuning */);
+                        int d_begin, int d_count, uint32_t* listC, uint16_t* listP, float* out);
 // windows 17x17 .. 37x37 (k_wmedian_tile_gen.hip)
 bool wmedian_tile_gen_supported(int win);
 int wmedian_tile_gen_slots(int win);

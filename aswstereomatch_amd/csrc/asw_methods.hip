@@ -618,7 +618,7 @@ static int run_wmedian(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_
             const int dn = std::min(chunk, n - d0);
             if (tile15)
                 ASW_TRY(launch_wmedian_tile(ctx->stream, raw.as<float>(), wl.as<float>(), wr.as<float>(), H, W, n, max_off, d0, dn,
-                                            lc.as<uint32_t>(), lp.as<uint16_t>(), f->vol.as<float>(), ctx->tune.wmedian_tile_split));
+                                            lc.as<uint32_t>(), lp.as<uint16_t>(), f->vol.as<float>()));
             else
                 ASW_TRY(launch_wmedian_tile_gen(ctx->stream, raw.as<float>(), wl.as<float>(), wr.as<float>(), H, W, mp.win, n, max_off,
                                                 d0, dn, lc.as<uint32_t>(), lp.as<uint16_t>(), f->vol.as<float>(),

@@ -67,7 +67,6 @@
 // still (pixel X+a, position Q+b) with tap column K - b, d = (Q+b) - (X+a) = minD + 4j + b - a, so the dead units of block 0 are
 // those with b < a and the positions run to the right of the tile.  Sample columns clamp the other way round: the tile clamps
 // coincide with the reference's at the right image border, not at the left one, so the border tiles are the first of a row.
-#include <stdlib.h>
 
 #include <algorithm>
 #include <cmath>
@@ -485,8 +484,7 @@ __device__ __forceinline__ void run_step(unsigned char* smem, int g, int qrel, i
     }
 }
 
-// ABL (timing experiments only, results are wrong): bit 0 = no weight staging after step 0, bit 1 = no barriers between steps
-template <int NW, bool EDGE, bool WRAPW, int ABL, bool RIGHT, bool LASTW = false, bool FRESH = false>
+template <int NW, bool EDGE, bool WRAPW, bool RIGHT, bool LASTW = false, bool FRESH = false>
 __device__ __forceinline__ void run_all_steps(unsigned char* smem, const float* __restrict__ lut, int wave, int lane,
                                               int g, int qrel, int qrel2, int xabs, int dbase, int dbase2,
                                               int W, int x0, int posmin, double (&num)[4][4], double (&den)[4][4], USums<LASTW>& us)
@@ -494,13 +492,13 @@ __device__ __forceinline__ void run_all_steps(unsigned char* smem, const float* 
     Staged<NW> st;
 #define ASW_XQ_STEP(KK)                                                                                        \
     if constexpr (FRESH) lane = fresh_lane();  /* once for the staging and the row loop's bases */              \
-    if (!(ABL & 1) && (KK) + 1 < NSTEP) {                                                                        \
+    if ((KK) + 1 < NSTEP) {                                                                                      \
         if constexpr (EDGE) stage_weights<NW>((KK) + 1, lut, smem, wave, lane);  /* border tiles: registers are scarcer there */ \
         else stage_issue<NW>((KK) + 1, lut, smem, wave, lane, st);                             \
     }                                                                                                           \
-    run_step<NW, (KK), EDGE, WRAPW, (!EDGE && !(ABL & 1) && (KK) + 1 < NSTEP), RIGHT, LASTW, FRESH>(smem, g, qrel, qrel2, xabs, dbase, dbase2, W, x0, \
+    run_step<NW, (KK), EDGE, WRAPW, (!EDGE && (KK) + 1 < NSTEP), RIGHT, LASTW, FRESH>(smem, g, qrel, qrel2, xabs, dbase, dbase2, W, x0, \
                                                                            posmin, num, den, us, wave, lane, st); \
-    if (!(ABL & 2) || (KK) == NSTEP - 1) __syncthreads();
+    __syncthreads();
     ASW_XQ_STEP(0) ASW_XQ_STEP(1) ASW_XQ_STEP(2) ASW_XQ_STEP(3) ASW_XQ_STEP(4) ASW_XQ_STEP(5)
     ASW_XQ_STEP(6) ASW_XQ_STEP(7) ASW_XQ_STEP(8) ASW_XQ_STEP(9) ASW_XQ_STEP(10) ASW_XQ_STEP(11)
     ASW_XQ_STEP(12) ASW_XQ_STEP(13) ASW_XQ_STEP(14) ASW_XQ_STEP(15) ASW_XQ_STEP(16) ASW_XQ_STEP(17)
@@ -511,7 +509,7 @@ __device__ __forceinline__ void run_all_steps(unsigned char* smem, const float* 
 // bestE / bestD: [H][W] running minimum over candidates [0, NFIN) (strict '<' in ascending d, M.cpp:1145-1150) for the tail
 // launch to resume from; disp (when there is no tail): the disparity itself.
 // LASTC (interior tiles only): the workgroup finishes candidates [0, NFIN]: vol has NFIN + 1 planes and disp is written.
-template <int NW, bool EDGE, int ABL, bool RIGHT, bool LASTC = false>
+template <int NW, bool EDGE, bool RIGHT, bool LASTC = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8 ? 4 : 3, NW == 8 ? 4 : 3))) void k_asw_bilateral_xq(
     XqParams p, const uint8_t* __restrict__ gL, const uint8_t* __restrict__ gR, const int4* __restrict__ cells,
     const float* __restrict__ lut, float* __restrict__ vol, double* __restrict__ bestE, float* __restrict__ bestD,
@@ -634,14 +632,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW == 8
     // wave 0 holds the threads of block j = 0 (the wrapped units): its steps load the second right weights / gray; ONE branch
     // around the whole step sequence (a branch per step made the register allocator spill 488 VGPRs)
     if (EDGE || wave == 0)
-        run_all_steps<NW, EDGE, true, ABL, RIGHT, false, LASTC>(smem, lut, wave, lane, g, qrel, qrel2, xabs, dbase, dbase2, W,
-                                                                 x0, posmin, num, den, none);
+        run_all_steps<NW, EDGE, true, RIGHT, false, LASTC>(smem, lut, wave, lane, g, qrel, qrel2, xabs, dbase, dbase2, W,
+                                                           x0, posmin, num, den, none);
     else if (LASTC && wave == UWAVE<NW>)  // (the wave number as a constant: the staging rows this wavefront does not have fold away)
-        run_all_steps<NW, EDGE, false, ABL, RIGHT, LASTC, LASTC>(smem, lut, UWAVE<NW>, lane, g, qrel, qrel2, xabs, dbase, dbase2, W,
-                                                                  x0, posmin, num, den, us);
+        run_all_steps<NW, EDGE, false, RIGHT, LASTC, LASTC>(smem, lut, UWAVE<NW>, lane, g, qrel, qrel2, xabs, dbase, dbase2, W,
+                                                            x0, posmin, num, den, us);
     else
-        run_all_steps<NW, EDGE, false, ABL, RIGHT, false, LASTC>(smem, lut, wave, lane, g, qrel, qrel2, xabs, dbase, dbase2, W,
-                                                                  x0, posmin, num, den, none);
+        run_all_steps<NW, EDGE, false, RIGHT, false, LASTC>(smem, lut, wave, lane, g, qrel, qrel2, xabs, dbase, dbase2, W,
+                                                            x0, posmin, num, den, none);
     // (the last step ended with a barrier: the tiles are dead)
 
     // ---- E = num / den (M.cpp:1111) -> LDS [candidate][pixel]; back from the scaled domain first (both ldexp are exact)
@@ -733,15 +731,15 @@ int launch_xq_t(hipStream_t s, hipStream_t s_border, const uint8_t* gL, const ui
         // (columns W-8 .. W-1) must lie in the last tile's right-gray tile: x0_last + minD <= W - 1
         if ((ntiles - 1) * PXW + minD > W - 1) return ASW_ERR_BAD_ARGUMENT;
         XqParams pe{H, W, minD, 0};
-        hipLaunchKernelGGL((k_asw_bilateral_xq<NW, true, 0, true>), dim3(1, H), blk, 0, s_border, pe, gL, gR, cells, lut, vol,
+        hipLaunchKernelGGL((k_asw_bilateral_xq<NW, true, true>), dim3(1, H), blk, 0, s_border, pe, gL, gR, cells, lut, vol,
                            bestE, bestD, last ? nullptr : disp);
         if (ntiles > 1) {
             XqParams pi{H, W, minD, 1};
             if (last)
-                hipLaunchKernelGGL((k_asw_bilateral_xq<NW, false, 0, true, true>), dim3(ntiles - 1, H), blk, 0, s, pi, gL, gR, cells,
+                hipLaunchKernelGGL((k_asw_bilateral_xq<NW, false, true, true>), dim3(ntiles - 1, H), blk, 0, s, pi, gL, gR, cells,
                                    lut, vol, bestE, bestD, disp);
             else
-                hipLaunchKernelGGL((k_asw_bilateral_xq<NW, false, 0, true>), dim3(ntiles - 1, H), blk, 0, s, pi, gL, gR, cells, lut,
+                hipLaunchKernelGGL((k_asw_bilateral_xq<NW, false, true>), dim3(ntiles - 1, H), blk, 0, s, pi, gL, gR, cells, lut,
                                    vol, bestE, bestD, disp);
         }
         ASW_HIP_TRY(hipGetLastError());
@@ -749,19 +747,12 @@ int launch_xq_t(hipStream_t s, hipStream_t s_border, const uint8_t* gL, const ui
     }
     // tiles whose windows (of in-image pixels) stay left of the right border: x0 + 63 + 7 <= W - 1
     const int n_int = W >= PXW + HH ? std::min(ntiles, (W - PXW - HH) / PXW + 1) : 0;
-#ifdef ASW_XQ_ABLATION  // measurement builds only (HIPCC_EXTRA=-DASW_XQ_ABLATION): the ablated kernels compute wrong results
-    int abl = 0;
-    if (const char* e = getenv("ASW_XQ_ABLATE")) abl = atoi(e) & 3;  // profiles/r02/ablation/*.csv
-    auto ki = abl == 0 ? k_asw_bilateral_xq<NW, false, 0, false> : abl == 1 ? k_asw_bilateral_xq<NW, false, 1, false>
-            : abl == 2 ? k_asw_bilateral_xq<NW, false, 2, false> : k_asw_bilateral_xq<NW, false, 3, false>;
-#else
-    auto ki = k_asw_bilateral_xq<NW, false, 0, false>;
-#endif
-    auto ke = k_asw_bilateral_xq<NW, true, 0, false>;
+    auto ki = k_asw_bilateral_xq<NW, false, false>;
+    auto ke = k_asw_bilateral_xq<NW, true, false>;
     if (n_int > 0) {
         XqParams p{H, W, minD, 0};
         if (last)
-            hipLaunchKernelGGL((k_asw_bilateral_xq<NW, false, 0, false, true>), dim3(n_int, H), blk, 0, s, p, gL, gR, cells, lut, vol,
+            hipLaunchKernelGGL((k_asw_bilateral_xq<NW, false, false, true>), dim3(n_int, H), blk, 0, s, p, gL, gR, cells, lut, vol,
                                bestE, bestD, disp);
         else
             hipLaunchKernelGGL(ki, dim3(n_int, H), blk, 0, s, p, gL, gR, cells, lut, vol, bestE, bestD, disp);

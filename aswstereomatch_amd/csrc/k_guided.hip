@@ -1127,7 +1127,7 @@ struct PlaneDst {
 };
 // band: rows per band (0 = default); wg_strips: 1 = the four wavefronts of a workgroup take four neighbouring strips of one slice
 // (they share halo columns in L1), 0 = four slices of one strip (they share the slice-independent operands), -1 = default
-struct WalkOpts { int band = 0; int wg_strips = -1; int interleave = 0; };
+struct WalkOpts { int band = 0; int wg_strips = -1; };
 
 template <int NP, int CPL, int ND, int WPE = 4, bool NANSAFE = false, bool RING = false, int PF = 1, class Src, class Dst>
 int launch_walk_t(hipStream_t s, const Src& src, const Dst& dst, int H, int W, int k, int n, int n_active = -1, WalkOpts o = WalkOpts())
@@ -1159,9 +1159,13 @@ int launch_walk_t(hipStream_t s, const Src& src, const Dst& dst, int H, int W, i
     while (band > 2 && (long long)nxw * ((H + band - 1) / band) * ((n_eff + ND - 1) / ND) < 4096) band /= 2;
     size_t lds = (size_t)4 * ND * NP * (SW + 2) * sizeof(double);
     // register target: at least 4 waves/SIMD; asking for 6 or 8 makes the allocator serialise/spill (7.1 / 12.6 ms vs 6.2)
-    auto kern = ring ? k_box_walk<NP, CPL, ND, WPE, NANSAFE, 15, RING, PF, Src, Dst>
-              : k == 15 ? k_box_walk<NP, CPL, ND, (RING ? 3 : WPE), NANSAFE, 15, false, (RING ? 1 : PF), Src, Dst>
-                        : k_box_walk<NP, CPL, ND, (RING ? 3 : WPE), NANSAFE, 0, false, (RING ? 1 : PF), Src, Dst>;
+    // (with RING, k == 15 is the ring form's: no ring-less 15-row kernel is instantiated there)
+    auto kern = k_box_walk<NP, CPL, ND, (RING ? 3 : WPE), NANSAFE, 0, false, (RING ? 1 : PF), Src, Dst>;
+    if constexpr (RING) {
+        if (ring) kern = k_box_walk<NP, CPL, ND, WPE, NANSAFE, 15, true, PF, Src, Dst>;
+    } else {
+        if (k == 15) kern = k_box_walk<NP, CPL, ND, WPE, NANSAFE, 15, false, PF, Src, Dst>;
+    }
     // four slices of one strip per workgroup when there are enough slices (1080p D=128: GuidedF 24.1 -> 22.9 ms, BLO1 -7 %,
     // GuidedF_2 -1 %); four strips of the one slice otherwise
     int slice_par = nzs >= 4 ? 1 : 0;
@@ -1170,7 +1174,7 @@ int launch_walk_t(hipStream_t s, const Src& src, const Dst& dst, int H, int W, i
     const int ngx = slice_par ? nxw : (nxw + 3) / 4, nby = (H + band - 1) / band, nzg = (nzs + spw - 1) / spw;
     const long long nwg = (long long)((ngx * nby + 7) / 8) * 8 * nzg;  // regions rounded up to a multiple of the 8 XCDs
     if (nwg > 0x7fffffffLL) return ASW_ERR_BAD_ARGUMENT;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(BW), lds, s, src, dst, H, W, k, band, nxw, n, ngx, nby, slice_par | ((o.interleave || !ring) ? 2 : 0));
+    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(BW), lds, s, src, dst, H, W, k, band, nxw, n, ngx, nby, slice_par | (ring ? 0 : 2));
     ASW_HIP_TRY(hipGetLastError());
     return ASW_OK;
 }
@@ -1612,24 +1616,37 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     run(steps, T(), T());
 }
 
+// Launch geometry of the three pair kernels (k_q6_pair, k_ab6_pair, k_guided_pair3), into the nxw / band / nby of their argument
+// struct (H, W and n are set): strips of `xo` output columns (128 less the halo), bands that give the chip ~10 rounds of the
+// 1024 two-wavefront workgroups it holds but are `min_band` rows or taller -- the warm-up is 14 rows per band (28 in the fused
+// walk) --, workgroups rounded up to a multiple of the 8 XCDs.  forced_band > 0: the switches' rows per band (AswTuning)
+// instead of that choice.
+template <class Args>
+int pair_geometry(Args& f, int xo, int min_band, int forced_band, unsigned* nwg_out)
+{
+    f.nxw = (f.W + xo - 1) / xo;
+    int nb = (int)std::max<long long>(1, (10240 + (long long)f.nxw * f.n - 1) / ((long long)f.nxw * f.n));
+    nb = std::min(nb, std::max(1, f.H / min_band));
+    f.band = forced_band > 0 ? forced_band : (f.H + nb - 1) / nb;
+    f.nby = (f.H + f.band - 1) / f.band;
+    const long long nwg = (long long)((f.nxw * f.nby + 7) / 8) * 8 * f.n;
+    if (nwg > 0x7fffffffLL) return ASW_ERR_BAD_ARGUMENT;
+    *nwg_out = (unsigned)nwg;
+    return ASW_OK;
+}
+
 int launch_q6_pair(hipStream_t s, const GuidedLaunch& a, const GuideAccT<true>& g, int band_opt)
 {
-    constexpr int XO = 128 - 14;
     Q6Args f;
     f.g = g; f.ab = a.ab; f.q = a.q; f.H = a.H; f.W = a.W; f.n = a.n;
-    f.nxw = (a.W + XO - 1) / XO;
-    // ~10 rounds of the 1024 two-wavefront workgroups the chip holds; 14 warm-up rows per band
-    int nb = (int)std::max<long long>(1, (10240 + (long long)f.nxw * a.n - 1) / ((long long)f.nxw * a.n));
-    nb = std::min(nb, std::max(1, a.H / 30));
-    f.band = band_opt >= 16 ? band_opt : (a.H + nb - 1) / nb;
-    f.nby = (a.H + f.band - 1) / f.band;
-    const long long nwg = (long long)((f.nxw * f.nby + 7) / 8) * 8 * a.n;
-    if (nwg > 0x7fffffffLL) return ASW_ERR_BAD_ARGUMENT;
+    unsigned nwg;
+    const int rc = pair_geometry(f, 128 - 14, 30, band_opt >= 16 ? band_opt : 0, &nwg);
+    if (rc != ASW_OK) return rc;
     const size_t lds = 2 * 4 * (128 + 2) * sizeof(double) + 2 * 128 * sizeof(float);
     if (a.nan_safe)
-        hipLaunchKernelGGL(k_q6_pair<true>, dim3((unsigned)nwg), dim3(128), lds, s, f);
+        hipLaunchKernelGGL(k_q6_pair<true>, dim3(nwg), dim3(128), lds, s, f);
     else
-        hipLaunchKernelGGL(k_q6_pair<false>, dim3((unsigned)nwg), dim3(128), lds, s, f);
+        hipLaunchKernelGGL(k_q6_pair<false>, dim3(nwg), dim3(128), lds, s, f);
     ASW_HIP_TRY(hipGetLastError());
     return ASW_OK;
 }
@@ -1886,40 +1903,29 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 
 int launch_ab6_pair(hipStream_t s, const GuidedLaunch& a, const GuideAccT<true>& g, const StatsSplit& sp, int band_opt)
 {
-    constexpr int XO = 128 - 14;
     AB6Args f;
     f.g = g; f.P = a.P; f.pscales = a.pscales; f.sp = sp; f.ab = a.ab; f.H = a.H; f.W = a.W; f.n = a.n;
-    f.nxw = (a.W + XO - 1) / XO;
-    int nb = (int)std::max<long long>(1, (10240 + (long long)f.nxw * a.n - 1) / ((long long)f.nxw * a.n));
-    nb = std::min(nb, std::max(1, a.H / 30));
-    f.band = band_opt >= 16 ? band_opt : (a.H + nb - 1) / nb;
-    f.nby = (a.H + f.band - 1) / f.band;
-    const long long nwg = (long long)((f.nxw * f.nby + 7) / 8) * 8 * a.n;
-    if (nwg > 0x7fffffffLL) return ASW_ERR_BAD_ARGUMENT;
+    unsigned nwg;
+    const int rc = pair_geometry(f, 128 - 14, 30, band_opt >= 16 ? band_opt : 0, &nwg);
+    if (rc != ASW_OK) return rc;
     const size_t lds = 2 * 4 * (128 + 2) * sizeof(double) + 2 * 128 * sizeof(float);
     if (a.nan_safe)
-        hipLaunchKernelGGL(k_ab6_pair<true>, dim3((unsigned)nwg), dim3(128), lds, s, f);
+        hipLaunchKernelGGL(k_ab6_pair<true>, dim3(nwg), dim3(128), lds, s, f);
     else
-        hipLaunchKernelGGL(k_ab6_pair<false>, dim3((unsigned)nwg), dim3(128), lds, s, f);
+        hipLaunchKernelGGL(k_ab6_pair<false>, dim3(nwg), dim3(128), lds, s, f);
     ASW_HIP_TRY(hipGetLastError());
     return ASW_OK;
 }
 
 int launch_guided_fused3(hipStream_t s, const GuidedLaunch& a, const GuideAccT<false>& g, const StatsPlanes& sp, int band_opt)
 {
-    constexpr int XO2 = 128 - 28;
     FusedArgs f;
     f.g = g; f.P = a.P; f.pscales = a.pscales; f.sp = sp; f.q = a.q; f.H = a.H; f.W = a.W; f.n = a.n;
-    f.nxw = (a.W + XO2 - 1) / XO2;
-    // ~10 rounds of the 1024 two-wavefront workgroups the chip holds (four per CU); 28 warm-up rows per band
-    int nb = (int)std::max<long long>(1, (10240 + (long long)f.nxw * a.n - 1) / ((long long)f.nxw * a.n));
-    nb = std::min(nb, std::max(1, a.H / 60));
-    f.band = band_opt >= 30 ? band_opt : (a.H + nb - 1) / nb;
-    f.nby = (a.H + f.band - 1) / f.band;
-    const long long nwg = (long long)((f.nxw * f.nby + 7) / 8) * 8 * a.n;
-    if (nwg > 0x7fffffffLL) return ASW_ERR_BAD_ARGUMENT;
+    unsigned nwg;
+    const int rc = pair_geometry(f, 128 - 28, 60, band_opt >= 30 ? band_opt : 0, &nwg);
+    if (rc != ASW_OK) return rc;
     const size_t lds = 2 * 4 * (128 + 2) * sizeof(double) + 2 * 4 * 128 * sizeof(float);
-    hipLaunchKernelGGL(k_guided_pair3, dim3((unsigned)nwg), dim3(128), lds, s, f);
+    hipLaunchKernelGGL(k_guided_pair3, dim3(nwg), dim3(128), lds, s, f);
     ASW_HIP_TRY(hipGetLastError());
     return ASW_OK;
 }

@@ -294,7 +294,7 @@ __global__ __launch_bounds__(64) void k_sgbm_row(const int* __restrict__ C, int*
 // of one geometry are disjoint and both walks of a line belong to the same wavefront (lane d touches the same addresses in
 // both), so nothing in a launch shares a T entry between wavefronts.
 // The C row of the next step does not depend on the recurrence: it, and the T row of this step, are loaded before sgbm_step so
-// that the dependent chain never waits on global memory (ASW_SGBM_LINE_NO_PREFETCH: the measurement build without that).
+// that the dependent chain never waits on global memory (measured: DESIGN.md section 4.8b).
 template <int NPL>
 __device__ __forceinline__ void sgbm_line_walk(const int* __restrict__ C, int* T, ptrdiff_t first, ptrdiff_t stride, int len, int D,
                                                int P1, int P2, int* lds)
@@ -312,7 +312,6 @@ __device__ __forceinline__ void sgbm_line_walk(const int* __restrict__ C, int* T
     for (int i = 0; i < len; i++, o += stride) {
 #pragma unroll
         for (int k = 0; k < NPL; k++) c[k] = cn[k];
-#ifndef ASW_SGBM_LINE_NO_PREFETCH
         const bool more = i + 1 < len;
 #pragma unroll
         for (int k = 0; k < NPL; k++) {
@@ -328,18 +327,6 @@ __device__ __forceinline__ void sgbm_line_walk(const int* __restrict__ C, int* T
             const int d = k * 64 + lane;
             if (d < D) T[o + d] = t[k] + Lr[k];
         }
-#else
-        sgbm_step<NPL>(Lr, c, m, lds + (i & 1) * D, D, P1, P2);
-#pragma unroll
-        for (int k = 0; k < NPL; k++) {
-            const int d = k * 64 + lane;
-            if (d < D) {
-                T[o + d] += Lr[k];
-                if (i + 1 < len) cn[k] = C[o + stride + d];
-            }
-        }
-        (void)t;
-#endif
     }
 }
 

@@ -109,11 +109,10 @@ __device__ __forceinline__ uint32_t pick_reg(const uint32_t (&a)[N], int r, int 
 }
 
 // grid blocks * NSPLIT (one dimension, see the mapping below), 512 threads: wavefront w takes the slices d_begin + w, w + 8, ... and, for each, the 64 / NSPLIT pixels
-// (whole rows of the block) of this workgroup's part.  NSPLIT = 2 halves the LDS weight slab: four workgroups per CU.
-// COMPACT (NSPLIT = 4, two pixel rows per part): the windows of the part cover 16 of the region's 22 rows, so each wavefront
-// first drops the entries of the other rows from its list (a prefix-sum scatter through LDS that keeps the sorted order):
-// 352 entries in 384 slots, 6 per lane instead of 8 in every walk.
-template <int NSPLIT, bool COMPACT>
+// (two whole rows of the block) of this workgroup's part.  The windows of the part cover 16 of the region's 22 rows, so each
+// wavefront first drops the entries of the other rows from its list (a prefix-sum scatter through LDS that keeps the sorted
+// order): 352 entries in 384 slots, 6 per lane instead of 8 in every walk.
+constexpr int NSPLIT = 4;
 __global__ __launch_bounds__(64 * PICK_WAVES) void k_wm_pick(const float* __restrict__ wLd /* [H][W][225] */,
                                                              const float* __restrict__ wRb /* [H][Wb][225] */,
                                                              const uint32_t* __restrict__ listC, const uint16_t* __restrict__ listP,
@@ -122,18 +121,18 @@ __global__ __launch_bounds__(64 * PICK_WAVES) void k_wm_pick(const float* __rest
 {
     constexpr int NPART = NPIX / NSPLIT;
     __shared__ float sWL[NPART * WLS];        // 57 856 B / NSPLIT: (wL .mul wd) of this part's pixels
-    // 25 600 B (COMPACT): the weights of the pixel a wavefront is working on at its d, laid out by position RELATIVE to the window's first
+    // 25 600 B: the weights of the pixel a wavefront is working on at its d, laid out by position RELATIVE to the window's first
     // cell (t = dy * 47 + dx + 7): a list entry gathers its weight with ONE LDS read at (its position - the pixel's), no table
     // in between.  Every slot that is not a window cell holds -0.0f: adding it changes no sum (x + -0.0 = x), and its bit
     // pattern says "not a member" (a weight product is never -0.0: both factors are >= +0).
-    // COMPACT: the list holds region rows ly0 .. ly0 + 15 only and the part's pixels sit in rows ly0 / ly0 + 1, so an entry's row
+    // The compacted list holds region rows ly0 .. ly0 + 15 only and the part's pixels sit in rows ly0 / ly0 + 1, so an entry's row
     // relative to the window is -1 .. 15: with one guard row in front (and the clamp slot behind) EVERY address an entry can form
     // lies inside the layout -- no clamp, one v_add per gather instead of add / min / add.
-    constexpr int LAYW = COMPACT ? (WIN + 2) * PS + 1 : LAY;
-    constexpr int ROW0 = COMPACT ? PS : 0;   // slot of the window's first row
+    constexpr int LAYW = (WIN + 2) * PS + 1;
+    constexpr int ROW0 = PS;                 // slot of the window's first row
     __shared__ float sWR[PICK_WAVES][LAYW];
-    constexpr int KE = COMPACT ? 6 : KPL;     // list entries per lane in the walk
-    static_assert(!COMPACT || NSPLIT == 4, "the compacted list holds the 16 region rows of a two-row part");
+    constexpr int KE = 6;                     // list entries per lane in the walk
+    static_assert(NSPLIT == 4, "the compacted list holds the 16 region rows of a two-row part");
     static_assert(64 * 6 <= LAY && LAY <= (WIN + 2) * PS, "the compaction buffer (original slot << 16 | position) borrows the wavefront's layout");
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     // one-dimensional grid of (block, part) pairs; every XCD takes a contiguous run of them, so the parts of a block -- which
@@ -176,8 +175,8 @@ __global__ __launch_bounds__(64 * PICK_WAVES) void k_wm_pick(const float* __rest
                               (int)(pp.z & 0xffffu), (int)(pp.z >> 16), (int)(pp.w & 0xffffu), (int)(pp.w >> 16)};
         float* od = out + (size_t)d * plane;
         int epos[KE];       // positions of the entries the walk visits
-        uint32_t eslot[KE]; // COMPACT: their slot (lane * 8 + r) in the full list, where the cost bits are
-        if constexpr (COMPACT) {
+        uint32_t eslot[KE]; // their slot (lane * 8 + r) in the full list, where the cost bits are
+        {  // compaction: keep the entries of the part's 16 region rows, in sorted order
             const int ly0 = p_begin >> 3;
             bool keep[KPL];
             int cnt = 0;
@@ -205,9 +204,6 @@ __global__ __launch_bounds__(64 * PICK_WAVES) void k_wm_pick(const float* __rest
             }
             wave_lds_sync();
             for (int i = lane; i < 64 * KE; i += 64) wrp[i] = -0.0f;  // the borrowed part of the layout: "not a member" again
-        } else {
-#pragma unroll
-            for (int i = 0; i < KE; i++) { epos[i] = 4 * pos[i]; eslot[i] = 0; }
         }
 
         // right-image weight row of pixel p at this d: weightWinsR[y][x - offset + numDisparity - 1] (M.cpp:3274)
@@ -240,18 +236,12 @@ __global__ __launch_bounds__(64 * PICK_WAVES) void k_wm_pick(const float* __rest
             wave_lds_sync();
 
             const int base4 = 4 * ((p >> 3) * PS + (p & 7) - HW);
-            const char* wqe = wq + 4 * ROW0 - base4;  // COMPACT: wave-uniform, so a gather address is one addition
+            const char* wqe = wq + 4 * ROW0 - base4;  // wave-uniform, so a gather address is one addition
             double run = 0.0, pre[KE];
             uint32_t mb = 0;  // member flags of this lane's entries, entry r at bit KE - 1 - r
 #pragma unroll
             for (int r = 0; r < KE; r++) {
-                float w;  // the cell's weight; -0.0 outside the window
-                if constexpr (COMPACT) {
-                    w = *reinterpret_cast<const float*>(wqe + epos[r]);
-                } else {
-                    const uint32_t t4 = min((uint32_t)(epos[r] - base4), (uint32_t)(4 * (LAY - 1)));  // rows above the window wrap to huge values
-                    w = *reinterpret_cast<const float*>(wq + t4);
-                }
+                const float w = *reinterpret_cast<const float*>(wqe + epos[r]);  // the cell's weight; -0.0 outside the window
                 run = r == 0 ? (double)w : run + (double)w;
                 pre[r] = run;
                 mb = (mb << 1) | (__float_as_uint(w) != 0x80000000u ? 1u : 0u);
@@ -272,11 +262,10 @@ __global__ __launch_bounds__(64 * PICK_WAVES) void k_wm_pick(const float* __rest
             if (ball) {  // wave-uniform
                 int pl, pr;
                 last_member_before<KE, false>(ball, first, mb, pl, pr);
-                if constexpr (COMPACT) {  // (pl, pr) addresses the compacted list: back to the slot that holds the cost
-                    const int slot = (int)pick_reg(eslot, pr, pl);
-                    pl = slot >> 3;
-                    pr = slot & 7;
-                }
+                // (pl, pr) addresses the compacted list: back to the slot that holds the cost
+                const int slot = (int)pick_reg(eslot, pr, pl);
+                pl = slot >> 3;
+                pr = slot & 7;
                 res = __uint_as_float(pick_reg(cst, pr, pl));
             }
             if (lane == 0) od[(size_t)(y0 + (p >> 3)) * W + x0 + (p & 7)] = res;
@@ -295,23 +284,14 @@ size_t wmedian_tile_list_slots(int H, int W, int d_count)
 
 // Slices [d_begin, d_begin + d_count) of the 15x15 weighted median; listC: u32[slots], listP: u16[slots].
 int launch_wmedian_tile(hipStream_t s, const float* cost, const float* wLd, const float* wRb, int H, int W, int numD, int max_off,
-                        int d_begin, int d_count, uint32_t* listC, uint16_t* listP, float* out, int nsplit)
+                        int d_begin, int d_count, uint32_t* listC, uint16_t* listP, float* out)
 {
     if (d_count <= 0 || d_begin < 0 || d_begin + d_count > numD) return ASW_ERR_BAD_ARGUMENT;
     const int nbx = (W + BW - 1) / BW, nby = (H + BH - 1) / BH;
     hipLaunchKernelGGL(k_wm_sort_regions, dim3((unsigned)(nbx * nby), (unsigned)((d_count + 3) / 4)), dim3(256), 0, s, cost, H, W, nbx,
                        d_begin, d_count, listC, listP);
-    // A/B only: 1 | 2 | 4 = parts per block without compaction, 0 (default) = four parts with the compacted lists
-    const dim3 blk(64 * PICK_WAVES);
-    const unsigned nb = (unsigned)(nbx * nby);
-    if (nsplit == 1)
-        hipLaunchKernelGGL((k_wm_pick<1, false>), dim3(nb * 1), blk, 0, s, wLd, wRb, listC, listP, H, W, nbx, numD, max_off, d_begin, d_count, out);
-    else if (nsplit == 2)
-        hipLaunchKernelGGL((k_wm_pick<2, false>), dim3(nb * 2), blk, 0, s, wLd, wRb, listC, listP, H, W, nbx, numD, max_off, d_begin, d_count, out);
-    else if (nsplit == 4)
-        hipLaunchKernelGGL((k_wm_pick<4, false>), dim3(nb * 4), blk, 0, s, wLd, wRb, listC, listP, H, W, nbx, numD, max_off, d_begin, d_count, out);
-    else
-        hipLaunchKernelGGL((k_wm_pick<4, true>), dim3(nb * 4), blk, 0, s, wLd, wRb, listC, listP, H, W, nbx, numD, max_off, d_begin, d_count, out);
+    hipLaunchKernelGGL(k_wm_pick, dim3((unsigned)(nbx * nby * NSPLIT)), dim3(64 * PICK_WAVES), 0, s, wLd, wRb, listC, listP, H, W, nbx,
+                       numD, max_off, d_begin, d_count, out);
     ASW_HIP_TRY(hipGetLastError());
     return ASW_OK;
 }

@@ -1,9 +1,10 @@
 """Are the kernels of two `hipcc -S --cuda-device-only` listings the same machine code?  Pairs the kernels by demangled name and
 compares, kernel by kernel, the instruction stream and the .amdhsa_* descriptor with symbol names normalised (mangled names,
 .LBB / .Ltmp / .Lfunc labels):
-    python tools/isa_same.py old.s new.s [--map 'REGEX=>REPLACEMENT' ...]
---map rewrites the demangled names of old.s first (a refactor that drops template parameters).  Exit status 1 on any unpaired
-or differing kernel.  Listings: from inside aswstereomatch_amd/csrc, hipcc <CXXFLAGS of build.py> --cuda-device-only -S x.hip."""
+    python tools/isa_same.py old.s new.s [--map 'REGEX=>REPLACEMENT' ...] [--gone REGEX ...]
+--map rewrites the demangled names of old.s first (a refactor that drops template parameters).  --gone: kernels of old.s alone
+whose (rewritten) name matches are listed but expected (a refactor that retires kernels).  Exit status 1 on any other unpaired
+or any differing kernel.  Listings: from inside aswstereomatch_amd/csrc, hipcc <CXXFLAGS of build.py> --cuda-device-only -S x.hip."""
 import argparse
 import difflib
 import os
@@ -48,6 +49,7 @@ def main():
     ap.add_argument("old")
     ap.add_argument("new")
     ap.add_argument("--map", action="append", default=[], metavar="REGEX=>REPLACEMENT")
+    ap.add_argument("--gone", action="append", default=[], metavar="REGEX")
     args = ap.parse_args()
     old, new = kernels(args.old), kernels(args.new)
     okey = {}
@@ -60,8 +62,12 @@ def main():
     if len(okey) != len(old) or len(nkey) != len(new):
         print("two kernels of one listing share a name after demangling / --map: they cannot be paired")
         return 1
-    same = bad = 0
+    same = bad = gone = 0
     for d in sorted(set(okey) | set(nkey)):
+        if d not in nkey and any(re.search(g, d) for g in args.gone):
+            print("GONE (old only, expected): %s" % d)
+            gone += 1
+            continue
         if d not in okey or d not in nkey:
             print("UNPAIRED (%s only): %s" % ("old" if d in okey else "new", d))
             bad += 1
@@ -74,7 +80,7 @@ def main():
         print("DIFFERS: %s" % d)
         for t in list(difflib.unified_diff(a, b, "old", "new", n=0, lineterm=""))[:12]:
             print("    " + t)
-    print("%d kernels old, %d new, %d paired and identical, %d not" % (len(old), len(new), same, bad))
+    print("%d kernels old, %d new, %d paired and identical, %d gone, %d not" % (len(old), len(new), same, gone, bad))
     return 1 if bad else 0
 
 

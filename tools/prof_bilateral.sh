@@ -1,9 +1,9 @@
 #!/bin/bash
 # Kernel-level profile of the classic bilateral path on the GPU box (1080p D=128 win 15):
 #   /usr/local/graft/bin/gpurun --timeout 600 -- 'bash tools/prof_bilateral.sh <tag> [variants...]'
-# per ASW_XQ_ABLATE value (0 = the product; 1 no staging, 2 no barriers, 3 both: timing experiments -- these need a library
-# built with  HIPCC_EXTRA=-DASW_XQ_ABLATION python -m aswstereomatch_amd.build --force;  the shipped build ignores the variable) or "old": rocprofv3 kernel stats of tools/run_one.py and two SQ counter passes (separate runs, --pmc never
-# combined with other trace domains).  Output: gpurun_out/<tag>/.
+# per variant, 0 (the xq form, the default) or "old" (ASW_BILATERAL_XQ=0, the one-kernel form): rocprofv3 kernel stats of
+# tools/run_one.py and two SQ counter passes (separate runs, --pmc never combined with other trace domains).
+# Output: the directory $OUT set below, one per <tag>.
 set -e -o pipefail
 TAG=${1:-bil}; shift || true
 VARS=${@:-0}
@@ -14,7 +14,6 @@ cd /tmp && export TMPDIR=/tmp
 SQ_A="SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAVES"
 SQ_B="SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_INSTS_SALU SQ_INSTS_SMEM SQ_BUSY_CYCLES SQ_ACTIVE_INST_VMEM"
 for v in $VARS; do
-    export ASW_XQ_ABLATE=$v
     if [ "$v" = "old" ]; then export ASW_BILATERAL_XQ=0; else unset ASW_BILATERAL_XQ; fi
     rocprofv3 --kernel-trace --stats -d /tmp/st_$v -o p --output-format csv -- python3 "$ROOT/tools/run_one.py" --alg 2 --reps 5 > "$OUT/stats_$v.log" 2>&1
     cp /tmp/st_$v/p_kernel_stats.csv "$OUT/kernel_stats_var$v.csv"
