@@ -6,6 +6,11 @@ Every method of the selector is run through the C-ABI on random shapes / windows
 compared with the CPU oracle: WTA index bit-exact everywhere; cost volume bit-exact for the methods whose summation
 order the kernels reproduce, within 1e-4 (relative) for the guided-filter family.
 
+The oracle-checked ASW methods (asw_cases.METHODS: classic, direct8, geodesic, wmedian, blo1, ncc, bilgrid, guided, guided2,
+guided3) draw their cases from tests/asw_cases.py, as tests/test_gpu_asw_sweep.py does (tie-dense input kinds in rotation, frames from
+one pixel up, padded rows), and are compared by asw_cases.check; a mismatch prints the tag that asw_cases.build_case(method, tag[1:])
+rebuilds the case from.  The shares --xq, --wm15 and --wmbig still force their shapes; such a case is built by build_case as well.
+
 The legs sgbm, bm, speckles, refine, subpixel and sgbm_paths draw their cases from tests/matcher_cases.py (tie-dense inputs in
 rotation with textured ones, frames from one pixel up, padded rows) and compare exactly with the restatements under tests/; a
 mismatch prints the tag that matcher_cases.build_case(leg, tag[1:]) rebuilds the case from.
@@ -46,6 +51,7 @@ from oracle import asw_oracle as O  # noqa: E402
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import adcensus_ref as ac  # noqa: E402
+import asw_cases  # noqa: E402
 import cross_ref as cr  # noqa: E402
 import matcher_cases as mc  # noqa: E402
 import sgbm_census_ref as scr  # noqa: E402
@@ -99,8 +105,10 @@ def main():
     args = ap.parse_args()
     rng = np.random.default_rng(args.seed)
     # The legs of tests/matcher_cases.py draw from a generator of their own and skip the generic draw below, so a seed gives the
-    # oracle-checked methods the cases it always gave them, with the legs' cases in between (a fifth of all cases by default).
+    # other oracle-checked entry points the draws it always gave them, with the legs' cases in between (a fifth of all cases by
+    # default).
     rng_mc = np.random.default_rng([args.seed, 1])
+    rng_asw = np.random.default_rng([args.seed, 2])   # the ASW methods: every draw comes from tests/asw_cases.py
     names = args.only.split(",") if args.only else ORACLE_METHODS + list(LEGS)
     unknown = [m for m in names if m not in ORACLE_METHODS and m not in LEGS]
     if unknown:
@@ -144,6 +152,7 @@ def main():
                 Lp[:, :W], Rp[:, :W] = L, R
                 L, R = Lp[:, :W], Rp[:, :W]   # non-contiguous views; the oracle wrappers copy them
             method = str(rng.choice(ORACLE_METHODS))
+            forced = False
             if args.only:
                 method = str(rng.choice([m for m in names if m not in LEGS]))
             if rng.random() < args.xq:
@@ -153,25 +162,29 @@ def main():
                 minD = int(rng.choice([0, 0, 1, 5, 48, 49, 70])) if method == "classic" else int(rng.choice([0, 0, 2, 33, 130]))
                 numD = int(rng.choice([63, 64, 65, 100, 126, 127, 128, 129, 191, 192, 255, int(rng.integers(63, 128)), int(rng.integers(63, 300))]))
                 seed = int(rng.integers(0, 1 << 30))
-                L, R, _ = make_pair(H, W, max(2, min(numD, W) // 2), seed=seed, block=int(rng.choice([4, 8, 16])))
-                if rng.random() < 0.3:
-                    for img in (L, R):
-                        y0, x0 = int(rng.integers(0, H)), int(rng.integers(0, W))
-                        img[y0:y0 + int(rng.integers(1, 6)), x0:x0 + int(rng.integers(1, 60))] = rng.integers(0, 256, 3).astype(np.uint8)
+                forced = True
             if rng.random() < args.wm15:
                 method, win, dt = "wmedian", 15, 0
                 numD = int(rng.integers(1, 40))
+                forced = True
             if rng.random() < args.wmbig:
                 method, win, dt = "wmedian", int(rng.choice([3, 5, 7, 9, 11, 13, 17, 19, 21, 23, 25, 27, 29, 31, 33, 35, 37, 39, 41])), 0
                 H, W, numD = int(rng.integers(1, 36)), int(rng.integers(1, 90)), int(rng.integers(1, 20))
                 minD = int(rng.choice([0, 0, 1, 4]))
                 seed = int(rng.integers(0, 1 << 30))
-                L, R, _ = make_pair(H, W, max(2, min(numD, W) // 2), seed=seed, block=int(rng.choice([4, 8, 16])))
-                if rng.random() < 0.3:  # flat rectangles: ties
-                    for img in (L, R):
-                        y0, x0 = int(rng.integers(0, H)), int(rng.integers(0, W))
-                        img[y0:y0 + int(rng.integers(1, 12)), x0:x0 + int(rng.integers(1, 40))] = rng.integers(0, 256, 3).astype(np.uint8)
+                forced = True
             tag = (method, H, W, win, minD, numD, dt, seed)
+            if method in asw_cases.METHODS and not forced:
+                case = asw_cases.random_case(rng_asw, method, n)
+                tag = (method,) + case["tag"]
+            elif method in asw_cases.METHODS:   # a forced shape: the kind in rotation, the method's parameters drawn as the sweep draws them
+                if method == "wmedian" and win > 37:    # per-pixel sort (64-bit keys, 2048 slots): small frames only
+                    H, W, numD = min(H, 14), min(W, 40), min(numD, 6)
+                elif method == "wmedian" and win > 17:  # general tile form; the oracle's multimap per (pixel, d) sets the size
+                    H, W, numD = min(H, 24), min(W, 64), min(numD, 10)
+                case = asw_cases.build_case(method, (asw_cases.KINDS[n % len(asw_cases.KINDS)], H, W, win, minD, numD, dt,
+                                                     asw_cases.draw_params(rng_asw, method), 0, seed))
+                tag = (method,) + case["tag"]
         if args.fresh_every > 0 and n > 0 and n % args.fresh_every == 0:
             ctx.close()
             ctx = asw.Context(0)
@@ -183,47 +196,13 @@ def main():
                 ok = np.array_equal(v, vw) and np.array_equal(d, dw) and np.array_equal(d2, dw)
             elif method in mc.FAMILIES:
                 ok = mc.same(*mc.gpu_result(ctx, case))
-            elif method == "classic":
-                gc, gg = float(rng.choice([30, 5, 0.5, 100])), float(rng.choice([20, 2, 7.5, 60]))
-                rc, dw, vw = O.asw_classic(L, R, gc, gg, dt, win, minD, numD, want_vol=True)
-                d, v = ctx.computeAdaptiveWeight(L, R, gc, gg, dt, win, minD, numD, return_cost_volume=True)
-                ok = np.array_equal(v, vw, equal_nan=True) and np.array_equal(d, dw)
-            elif method == "direct8":
-                rc, dw, vw = O.asw_direct8(L, R, 0, win, minD, numD, want_vol=True)
-                d, v = ctx.computeAdaptiveWeight_direct8(L, R, 0, win, minD, numD, return_cost_volume=True)
-                ok = np.array_equal(v, vw, equal_nan=True) and np.array_equal(d, dw)
-            elif method == "geodesic":
-                if win > 15:  # (win+2)^2 relaxations per pixel and pass on the CPU side: small frames
-                    L, R = np.ascontiguousarray(L[:20, :64]), np.ascontiguousarray(R[:20, :64])
-                    numD = min(numD, 8)
-                rc, dw, vw = O.asw_geodesic(L, R, dt, win, minD, numD, want_vol=True)
-                d, v = ctx.computeAdaptiveWeight_geodesic(L, R, dt, win, minD, numD, return_cost_volume=True)
-                ok = np.array_equal(v, vw, equal_nan=True) and np.array_equal(d, dw)
-            elif method == "guided":
-                eps = float(rng.choice([1e-6, 1e-8, 1e-3]))
-                rc, dw, vw = O.asw_guided(L, R, dt, eps, win, minD, numD, want_vol=True)
-                d, v = ctx.computeAdaptiveWeight_GuidedF(L, R, dt, eps, win, minD, numD, return_cost_volume=True)
-                ok = close(v, vw) and np.array_equal(d, dw)
-            elif method == "guided2":
-                eps = float(rng.choice([1e-6, 1e-8, 1e-3]))
-                rc, dw, vw = O.asw_guided2(L, R, 0, eps, win, minD, numD, want_vol=True)
-                d, v = ctx.computeAdaptiveWeight_GuidedF_2(L, R, 0, eps, win, minD, numD, return_cost_volume=True)
-                ok = close(v, vw) and np.array_equal(d, dw)
-            elif method == "guided3":
-                rc, dw, vw = O.asw_guided3(L, R, dt, 1e-6, win, minD, numD, want_vol=True)
-                d, v = ctx.computeAdaptiveWeight_GuidedF_3(L, R, dt, 1e-6, win, minD, numD, return_cost_volume=True)
-                # flat windows make NaN costs: their WTA is build-defined on both sides, compare where finite
-                ok = close(v, vw) and np.array_equal(d[np.isfinite(vw).all(axis=0)], dw[np.isfinite(vw).all(axis=0)])
-            elif method == "bilgrid":
-                sS = float(rng.choice([2.5, 4, 6, 7.5, 10, 16]))
-                sR = float(rng.choice([3, 5, 10, 33.3, 40, 64, 128, 300]))
-                if rng.integers(0, 2):  # flat regions: bins with enough pixels for the int counts to survive
-                    L = (L // 64) * 64
-                    R = (R // 64) * 64
-                nD = min(numD, 12)
-                rc, dw, vw = O.asw_bilgrid(L, R, 0, sS, sR, minD, nD, want_vol=True)
-                d, v = ctx.computeAdaptiveWeight_bilateralGrid(L, R, 0, sS, sR, minD, nD, return_cost_volume=True)
-                ok = np.array_equal(v, vw, equal_nan=True) and np.array_equal(d, dw)
+            elif method in asw_cases.METHODS:
+                try:
+                    asw_cases.check(case, asw_cases.gpu_result(ctx, case), asw_cases.reference(O, case))
+                    ok = True
+                except AssertionError as e:
+                    ok = False
+                    print(e, flush=True)
             elif method == "resident":
                 # the resident split (asw_upload_pair / asw_match_resident / asw_download_*) against the one-call entry point
                 alg = int(rng.choice([2, 3, 4, 5, 6, 7, 8, 9, 10, 11]))
@@ -263,28 +242,6 @@ def main():
                 want, wbad = O.lr_check(a, b, tau, -1.0)
                 got, bad = ctx.leftRightCheck(a, b, tau, -1.0)
                 ok = np.array_equal(got, want) and bad == wbad
-            elif method == "wmedian":
-                if win > 37:  # per-pixel sort (64-bit keys, 2048 slots): small frames only
-                    H2, W2 = min(H, 14), min(W, 40)
-                    L, R = np.ascontiguousarray(L[:H2, :W2]), np.ascontiguousarray(R[:H2, :W2])
-                    numD = min(numD, 6)
-                elif win > 17:  # general tile form; the oracle's multimap per (pixel, d) sets the size
-                    H2, W2 = min(H, 24), min(W, 64)
-                    L, R = np.ascontiguousarray(L[:H2, :W2]), np.ascontiguousarray(R[:H2, :W2])
-                    numD = min(numD, 10)
-                rs, rr = [(10, 10), (5, 20), (3, 3), (25, 2.5)][int(rng.integers(0, 4))]
-                rc, dw, vw = O.asw_wmedian(L, R, 0, win, rs, rr, minD, numD, want_vol=True)
-                d, v = ctx.computeAdaptiveWeight_WeightedMedian(L, R, 0, win, rs, rr, minD, numD, return_cost_volume=True)
-                ok = np.array_equal(v, vw) and np.array_equal(d, dw)
-            elif method == "blo1":
-                rate = float(rng.choice([0.015, 0.05, 0.004, 0.2]))
-                rc, dw, vw = O.asw_blo1(L, R, dt, rate, win, 0, numD, want_vol=True)
-                d, v = ctx.computeAdaptiveWeight_BLO1(L, R, dt, rate, win, 0, numD, return_cost_volume=True)
-                fin = np.isfinite(vw)
-                ok = np.array_equal(v[fin], vw[fin]) and np.array_equal(np.isnan(v), np.isnan(vw)) and np.array_equal(d, dw)
-            elif method == "ncc":
-                rc, dw = O.ncc_disparity(L, R, dt, win, minD, numD)
-                ok = np.array_equal(ctx.computeNCC(L, R, dt, win, minD, numD), dw)
             elif method == "ad_tad":
                 T = int(rng.integers(-5, 261))
                 if rng.integers(0, 3) == 0:  # 1-channel branch, M.cpp:264-291
