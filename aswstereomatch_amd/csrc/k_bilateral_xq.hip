@@ -70,6 +70,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 #include "asw_device.h"
 #include "asw_internal.h"
@@ -84,6 +85,17 @@ constexpr int NSTEP = KS + 3;             // 18 steps: unit row b runs b tap col
 constexpr int RING = 5;                   // tap columns of left weights kept (4 in use + the one being staged)
 constexpr int URI = 3;                    // window rows per body of the row loop (interior tiles)
 constexpr int CROW = 6;                   // rows in front of the mid-step stage_commit
+// How far ahead of their use the interior tiles' row loops read LDS (run_step), per register class of the wavefront:
+//   class 0  plain wavefronts of the LASTC kernels (six of eight) and everything at NW = 4 (168 VGPRs)
+//   class 1  wave 0 (second right weights / gray) and the unit's wavefront of the NW = 8 LASTC kernels
+//   class 2  the NW = 8 kernels without LASTC, which carry the lane-derived values through the loops
+// PF_HEAD[class][loop]: what of a row's head is read during the previous row's last block, in the loop in front of the mid-step
+// commit (the staged weights of the next step are live there: eight more registers) and in the loop behind it -- PF_GRAY the
+// right gray and the left gray quads, PF_WR the right weights, PF_WL the left weights of the row's first block; the rest is read
+// at the head of the row itself, as it used to be.  PF_WLEAD[class]: blocks between the read of a left-weight quad and its block.
+// Each entry is the deepest form at which every kernel of the class keeps to 128 VGPRs without scratch (NW = 4: 168).
+constexpr int PF_GRAY = 4, PF_WR = 2, PF_WL = 1, PF_ALL = 7;
+constexpr int PF_HEAD[3][2] = {{PF_ALL, PF_ALL}, {PF_WR | PF_WL, PF_GRAY | PF_WL}, {0, PF_GRAY}}, PF_WLEAD[3] = {2, 2, 1};
 static_assert(KS % URI == 0 && CROW % URI == 0, "whole bodies");
 constexpr int NCELLCOL = NSTEP + 3;       // cell-table columns kx = -3 .. 17
 constexpr int LW8 = 80;                   // u8 row stride of the left tile (multiple of 4)
@@ -347,140 +359,257 @@ __device__ __forceinline__ void run_step(unsigned char* smem, int g, int qrel, i
     uint32_t hi0[7];
 #pragma unroll
     for (int i = 0; i < 7; i++) asm volatile("v_mov_b32 %0, 0" : "=v"(hi0[i]));  // seven distinct registers the compiler cannot fold
-    // UR rows per loop body: the row strides fold into the offset fields (UR - 1 rows of the right stride plus the largest in-row
-    // offset stay far below 16 bits), so the bases advance once per body.  A fence after every row keeps the next row's loads
-    // behind it: unfenced, the scheduler hoists them and spills hundreds of registers.  The mid-step stage_commit sits between
-    // two such loops, so no row tests for it.
-    constexpr int UR = EDGE ? 1 : URI;  // the border tiles' per-diagonal addresses leave no registers for it
-    auto rows = [&](int ky0, int nbody) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    typedef __attribute__((address_space(3))) const f32x4 lds_f32x4;
+    typedef __attribute__((address_space(3))) const uint32_t lds_u32;
+    typedef __attribute__((address_space(3))) const float lds_f32;
+
+    if constexpr (EDGE) {
+        // Border tiles, as they were: one row per loop body (UR = 1: the per-diagonal addresses leave no registers for more),
+        // every read where it is used, and ONE fence per row, which keeps the next row's loads behind it: unfenced, the scheduler
+        // hoists them and spills hundreds of registers.  The row is written out here and not built from the pieces of the
+        // interior tiles below: these kernels spill already, and their machine code is held to what it was (tools/isa_same.py).
+        static_assert(!COMMIT, "the border tiles stage in one piece in front of the step");
+        constexpr int UR = 1;
+        auto rows = [&](int ky0, int nbody) {
 #pragma unroll 1
-        for (int it = 0; it < nbody; it++) {
+            for (int it = 0; it < nbody; it++) {
 #pragma unroll
-            for (int u = 0; u < UR; u++) {
-                lds_u8* rL = bL + u * 4 * LROW;
-                lds_u8* rR = bR + u * 4 * RROW;
-                lds_u8* rR2 = bR2 + u * 4 * RROW;
-                double c[7];  // cost samples of the diagonals, scaled domain: |gL - gR| * 2^-1074
-                uint32_t glU = 0;  // left gray of diagonal 0 (LASTW)
-                (void)glU;
-                if constexpr (!EDGE) {
-                    const uint32_t gr = *(const __attribute__((address_space(3))) uint32_t*)(rR + 4 * (RGRAY + K));  // tile column of Q + K - 7
-                    uint32_t gr2 = gr;
-                    if constexpr (WRAPW && (RIGHT ? DHI > 0 : DLO < 0)) gr2 = *(const __attribute__((address_space(3))) uint32_t*)(rR2 + 4 * (RGRAY + K));
-                    // the left grays of the step, read as 16-byte aligned quads from a tile column that is a multiple of four (4g, LWP
-                    // and E0 are): a run the compiler cannot prove aligned is split into narrower reads (ds_read2_*), which cost
-                    // several times the LDS cycles of ds_read_b128
-                    constexpr int E0 = (K + DLO) & ~3, NQ = (K + DHI - E0 + 4) / 4;
-                    static_assert(E0 >= 0 && E0 + 4 * NQ + 4 * 15 <= LWP, "the quads stay inside a tile row");
-                    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-                    const __attribute__((address_space(3))) u32x4* pl4 = (const __attribute__((address_space(3))) u32x4*)(rL + 4 * (LGRAY + E0));
+                for (int u = 0; u < UR; u++) {
+                    lds_u8* rL = bL + u * 4 * LROW;
+                    lds_u8* rR = bR + u * 4 * RROW;
+                    lds_u8* rR2 = bR2 + u * 4 * RROW;
+                    double c[7];  // cost samples of the diagonals, scaled domain: |gL - gR| * 2^-1074
+                    const int ky = ky0 + it * UR + u;
+#pragma unroll
+                    for (int dl = DLO; dl <= DHI; dl++) c[dl + 3] = cost_sample(sLd[ky * LROW + iL[dl + 3]], sRd[ky * RROW + iR[dl + 3]], hi0[dl + 3]);
+                    const f32x4 wr4 = *(lds_f32x4*)(rR + 4 * (K & 1) * NPOS);
+                    // the right weights as the two register pairs the packed multiplies broadcast from (op_sel picks either half of a
+                    // pair).  The upper pair is made opaque: the compiler otherwise copies element 3 into the low half of a fresh pair,
+                    // one v_mov per row.
+                    f32x2 wrp[2] = {{wr4.x, wr4.y}, {wr4.z, wr4.w}};
+                    asm("" : "+v"(wrp[1]));
+                    f32x2 wr2p[2] = {wrp[0], wrp[1]};
+                    if constexpr (RIGHT ? BLO <= 2 : BHI >= 1) {  // some active unit is a wrapped one
+                        const f32x4 w2 = *(lds_f32x4*)(rR2 + 4 * (K & 1) * NPOS);
+                        wr2p[0] = f32x2{w2.x, w2.y};
+                        wr2p[1] = f32x2{w2.z, w2.w};
+                        asm("" : "+v"(wr2p[1]));
+                    }
+#pragma unroll
+                    for (int b = BLO; b <= BHI; b++) {
+                        const f32x4 wl4 = *(lds_f32x4*)(rL + 4 * ((K - b) % RING) * PXW);
+                        float ab[4];  // (see `block` below)
+#pragma unroll
+                        for (int a = 0; a < 4; a += 2) {
+                            const f32x2 wl2 = {wl4[a], wl4[a + 1]};
+                            const bool w0 = RIGHT ? b < a : a < b, w1 = RIGHT ? b < a + 1 : a + 1 < b;  // wrapped units
+                            const f32x2 s0 = (w0 ? wr2p : wrp)[b >> 1], s1 = (w1 ? wr2p : wrp)[b >> 1];
+                            f32x2 wrb;
+                            if (w0 == w1) wrb = (b & 1) ? __builtin_shufflevector(s0, s0, 1, 1) : __builtin_shufflevector(s0, s0, 0, 0);
+                            else wrb = f32x2{s0[b & 1], s1[b & 1]};
+                            const f32x2 pr = wl2 * wrb;
+                            ab[a] = pr.x; ab[a + 1] = pr.y;
+                        }
+#pragma unroll
+                        for (int a = 0; a < 4; a++) {
+                            const double abd = (double)ab[a];
+                            num[a][b] = __builtin_fma(abd, c[a - b + 3], num[a][b]);  // exact product: == num + ab*c (x 2^-954)
+                            den[a][b] = den[a][b] + abd;                              // M.cpp:1107-1108 (x 2^120)
+                        }
+                    }
+                    // the fence: the row's sums are complete here (the arithmetic has no side effect the barrier alone would order)
+                    // and no LDS read crosses
+#pragma unroll
+                    for (int b = BLO; b <= BHI; b++)
+                        asm volatile("" :: "v"(num[0][b]), "v"(num[1][b]), "v"(num[2][b]), "v"(num[3][b]),
+                                           "v"(den[0][b]), "v"(den[1][b]), "v"(den[2][b]), "v"(den[3][b]) : "memory");
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                bL += UR * 4 * LROW;
+                bR += UR * 4 * RROW;
+                asm("" : "+v"(bL), "+v"(bR));
+                bR2 += UR * 4 * RROW;
+                asm("" : "+v"(bR2));
+            }
+        };
+        rows(0, KS / UR);
+    } else {
+        // Interior tiles: URI rows per loop body -- the row strides fold into the offset fields (URI rows of the right stride plus
+        // the largest in-row offset stay far below 16 bits), so the bases advance once per body -- and the LDS reads of a row are
+        // issued ahead of their use as far as the registers of the wavefront's class allow (PF_HEAD / PF_WLEAD at the top of the
+        // file).  A row's sums are fenced per b-block (the empty asm on the block's eight sums with a memory clobber, then
+        // sched_barrier): no read crosses a fence, so a read written in front of a block's fence is issued in front of that block's
+        // arithmetic or among it, and one written a block earlier has at least that block's 14 VALU instructions between its issue
+        // and its use.  The waits are the compiler's (s_waitcnt lgkmcnt(n), the younger reads left in flight):
+        //   head   what a row needs in front of its first block -- right gray, left gray quads, right weights, the left weights of
+        //          block BLO, wave 0's second right gray and weights.  The parts the class prefetches are read at the start of the
+        //          PREVIOUS row's last block and carried across the rows of a body, across the loop's back edge and across the
+        //          mid-step commit; the others are read at the head of the row, where all of them used to be.
+        //   wl     the left weights of block b + WLEAD are read at the start of block b: the quads rotate.
+        //   unit   the three words of the last-candidate unit are read at the head of the row and used behind its second block.
+        // Boundaries.  The mid-step commit stages step K + 1: it writes ring slot (K + 1) % 5 and right buffer (K + 1) & 1.  The
+        // head reads the gray tiles (never written after the prologue), right buffer K & 1 and ring slot (K - BLO) % 5; the
+        // slots a step reads are those of columns K - 3 .. K, and K + 1 == K - 4 (mod 5) is none of them: the head of row CROW,
+        // read in front of the commit, is still the right one behind it.  The head read by a step's last row is row KS's: it
+        // lies one row stride past the blocks, inside smem (static_assert below), and nothing consumes it -- nothing is carried
+        // across the step's barrier, and the step's first row waits for its head in full.
+        constexpr int E0 = (K + DLO) & ~3, NQ = (K + DHI - E0 + 4) / 4;
+        static_assert(E0 >= 0 && E0 + 4 * NQ + 4 * 15 <= LWP, "the quads stay inside a tile row");
+        static_assert(DLO <= 0 && DHI >= 0, "diagonal 0 is in use in every step");
+        static_assert(OFF_RB + (KS + 1) * RROW * 4 <= LDS_TOTAL, "the head of row KS is read inside smem");
+        constexpr bool W2G = WRAPW && (RIGHT ? DHI > 0 : DLO < 0);   // some active diagonal belongs to wrapped units
+        constexpr bool W2W = WRAPW && (RIGHT ? BLO <= 2 : BHI >= 1);  // some active unit is a wrapped one
+        constexpr int CLS = NW != 8 ? 0 : !FRESH ? 2 : (WRAPW || LASTW) ? 1 : 0;
+        constexpr int WLEAD = PF_WLEAD[CLS];
+        constexpr int PF_PRE = PF_HEAD[CLS][COMMIT ? 0 : 1], PF_POST = PF_HEAD[CLS][1];  // (the last step has one loop only)
+        // One b-block of a row: the four units (a, b) of unit row b.  wl4: the left weights of tap column K - b; wrp / wr2p: the
+        // right weights (and the wrapped units') as the two register pairs the packed multiplies broadcast from (op_sel picks
+        // either half of a pair).
+        auto block = [&](int b, const f32x4 wl4, const double (&c)[7], const f32x2 (&wrp)[2], const f32x2 (&wr2p)[2])
+                         __attribute__((always_inline)) {
+            // the f32 products (M.cpp:1104-1105, x 2^120) written as the two packed multiplies they are issued as: pixels
+            // (a, a + 1) times the position's weight broadcast -- left to the vectoriser, the unrolled body pairs units
+            // across b and assembles the pairs with moves
+            float ab[4];
+#pragma unroll
+            for (int a = 0; a < 4; a += 2) {
+                const f32x2 wl2 = {wl4[a], wl4[a + 1]};
+                const bool w0 = RIGHT ? b < a : a < b, w1 = RIGHT ? b < a + 1 : a + 1 < b;  // wrapped units
+                const f32x2 s0 = (w0 ? wr2p : wrp)[b >> 1], s1 = (w1 ? wr2p : wrp)[b >> 1];
+                f32x2 wrb;
+                if (w0 == w1) wrb = (b & 1) ? __builtin_shufflevector(s0, s0, 1, 1) : __builtin_shufflevector(s0, s0, 0, 0);
+                else wrb = f32x2{s0[b & 1], s1[b & 1]};
+                const f32x2 pr = wl2 * wrb;
+                ab[a] = pr.x; ab[a + 1] = pr.y;
+            }
+#pragma unroll
+            for (int a = 0; a < 4; a++) {
+                const double abd = (double)ab[a];
+                num[a][b] = __builtin_fma(abd, c[a - b + 3], num[a][b]);  // exact product: == num + ab*c (x 2^-954)
+                den[a][b] = den[a][b] + abd;                              // M.cpp:1107-1108 (x 2^120)
+            }
+        };
+        // the right weights as register pairs.  The upper pair is made opaque: the compiler otherwise copies element 3 into the
+        // low half of a fresh pair, one v_mov per row.
+        auto pairs = [](const f32x4 w, f32x2 (&p)[2]) __attribute__((always_inline)) {
+            p[0] = f32x2{w.x, w.y};
+            p[1] = f32x2{w.z, w.w};
+            asm("" : "+v"(p[1]));
+        };
+        struct Head {
+            uint32_t gr, gr2;  // right gray: tile column of Q + K - 7 (and the wrapped units')
+            u32x4 gl[NQ];      // left grays of the step's diagonals
+            f32x4 wr, wr2, wl;
+        };
+        // read the parts `pf` of the head of row u of the body (u = URI: the next body's first) into h
+        auto load_head = [&](int u, auto pf, Head h) __attribute__((always_inline)) {
+            constexpr int PF = decltype(pf)::value;
+            lds_u8* rL = bL + u * 4 * LROW;
+            lds_u8* rR = bR + u * 4 * RROW;
+            lds_u8* rR2 = bR2 + u * 4 * RROW;
+            if constexpr (PF & PF_GRAY) {
+                h.gr = *(lds_u32*)(rR + 4 * (RGRAY + K));
+                h.gr2 = h.gr;
+                if constexpr (W2G) h.gr2 = *(lds_u32*)(rR2 + 4 * (RGRAY + K));
+                // the left grays, read as 16-byte aligned quads from a tile column that is a multiple of four (4g, LWP and E0
+                // are): a run the compiler cannot prove aligned is split into narrower reads (ds_read2_*), which cost several
+                // times the LDS cycles of ds_read_b128
+                const __attribute__((address_space(3))) u32x4* pl4 = (const __attribute__((address_space(3))) u32x4*)(rL + 4 * (LGRAY + E0));
+#pragma unroll
+                for (int i = 0; i < NQ; i++) h.gl[i] = pl4[i];
+            }
+            if constexpr (PF & PF_WR) {
+                h.wr = *(lds_f32x4*)(rR + 4 * (K & 1) * NPOS);
+                h.wr2 = h.wr;
+                if constexpr (W2W) h.wr2 = *(lds_f32x4*)(rR2 + 4 * (K & 1) * NPOS);
+            }
+            if constexpr (PF & PF_WL) h.wl = *(lds_f32x4*)(rL + 4 * ((K - BLO) % RING) * PXW);
+            return h;
+        };
+        Head h = load_head(0, std::integral_constant<int, PF_PRE>{}, Head{});
+        auto rows = [&](int nbody, auto pf) {
+            constexpr int PF = decltype(pf)::value;
+#pragma unroll 1
+            for (int it = 0; it < nbody; it++) {
+#pragma unroll
+                for (int u = 0; u < URI; u++) {
+                    lds_u8* rL = bL + u * 4 * LROW;
+                    const Head cur = load_head(u, std::integral_constant<int, PF_ALL & ~PF>{}, h);  // what was not prefetched
+                    f32x4 wl[4];
+                    wl[BLO] = cur.wl;
+#pragma unroll
+                    for (int b = BLO + 1; b < BLO + WLEAD && b <= BHI; b++) wl[b] = *(lds_f32x4*)(rL + 4 * ((K - b) % RING) * PXW);
+                    // lane -> pixel 4g + a, a = (lane >> 3) & 3, candidate NFIN: position 4g + a (+ 4 NJ), unit row b = a, tap column
+                    // K - a; the grays are the tile columns 4g + K (left: the diagonal-0 sample of the row's own quads) and
+                    // 4g + K (+ 4 NJ) (right): the skew a cancels in both
+                    float wlU = 0.0f, wrU = 0.0f;
+                    uint32_t grU = 0;
+                    if constexpr (LASTW) {
+                        wlU = *(lds_f32*)(uL + u * 4 * LROW);
+                        wrU = *(lds_f32*)(uW + u * 4 * RROW);
+                        grU = *(lds_u32*)(uG + u * 4 * RROW + 4 * (RGRAY + K));
+                    }
+                    double c[7];  // cost samples of the diagonals, scaled domain: |gL - gR| * 2^-1074
                     uint32_t glv[4 * NQ];
 #pragma unroll
                     for (int i = 0; i < NQ; i++) {
-                        u32x4 t = pl4[i];
+                        u32x4 t = cur.gl[i];
                         asm("" : "+v"(t));  // all four words in use: otherwise the compiler narrows a quad whose first word no diagonal
                                             // needs into a misaligned 12-byte read and splits that into ds_read2_b32 + ds_read_b32
                         glv[4 * i] = t.x; glv[4 * i + 1] = t.y; glv[4 * i + 2] = t.z; glv[4 * i + 3] = t.w;
                     }
 #pragma unroll
-                    for (int dl = DLO; dl <= DHI; dl++) c[dl + 3] = cost_sample(glv[K + dl - E0], (RIGHT ? dl > 0 : dl < 0) ? gr2 : gr, hi0[dl + 3]);
-                    static_assert(DLO <= 0 && DHI >= 0, "diagonal 0 is in use in every step");
-                    glU = glv[K - E0];
-                } else {
-                    const int ky = ky0 + it * UR + u;
+                    for (int dl = DLO; dl <= DHI; dl++) c[dl + 3] = cost_sample(glv[K + dl - E0], (RIGHT ? dl > 0 : dl < 0) ? cur.gr2 : cur.gr, hi0[dl + 3]);
+                    f32x2 wrp[2], wr2p[2];
+                    pairs(cur.wr, wrp);
+                    wr2p[0] = wrp[0]; wr2p[1] = wrp[1];
+                    if constexpr (W2W) pairs(cur.wr2, wr2p);
 #pragma unroll
-                    for (int dl = DLO; dl <= DHI; dl++) c[dl + 3] = cost_sample(sLd[ky * LROW + iL[dl + 3]], sRd[ky * RROW + iR[dl + 3]], hi0[dl + 3]);
-                }
-                typedef float f32x4 __attribute__((ext_vector_type(4)));
-                typedef __attribute__((address_space(3))) const f32x4 lds_f32x4;
-                const f32x4 wr4 = *(lds_f32x4*)(rR + 4 * (K & 1) * NPOS);
-                // the right weights as the two register pairs the packed multiplies broadcast from (op_sel picks either half of a
-                // pair).  The upper pair is made opaque: the compiler otherwise copies element 3 into the low half of a fresh pair,
-                // one v_mov per row.
-                typedef float f32x2 __attribute__((ext_vector_type(2)));
-                f32x2 wrp[2] = {{wr4.x, wr4.y}, {wr4.z, wr4.w}};
-                asm("" : "+v"(wrp[1]));
-                f32x2 wr2p[2] = {wrp[0], wrp[1]};
-                if constexpr ((WRAPW || EDGE) && (RIGHT ? BLO <= 2 : BHI >= 1)) {  // some active unit is a wrapped one
-                    const f32x4 w2 = *(lds_f32x4*)(rR2 + 4 * (K & 1) * NPOS);
-                    wr2p[0] = f32x2{w2.x, w2.y};
-                    wr2p[1] = f32x2{w2.z, w2.w};
-                    asm("" : "+v"(wr2p[1]));
-                }
-#pragma unroll
-                for (int b = BLO; b <= BHI; b++) {
-                    const f32x4 wl4 = *(lds_f32x4*)(rL + 4 * ((K - b) % RING) * PXW);
-                    // the f32 products (M.cpp:1104-1105, x 2^120) written as the two packed multiplies they are issued as: pixels
-                    // (a, a + 1) times the position's weight broadcast -- left to the vectoriser, the unrolled body pairs units
-                    // across b and assembles the pairs with moves
-                    float ab[4];
-#pragma unroll
-                    for (int a = 0; a < 4; a += 2) {
-                        const f32x2 wl2 = {wl4[a], wl4[a + 1]};
-                        const bool w0 = RIGHT ? b < a : a < b, w1 = RIGHT ? b < a + 1 : a + 1 < b;  // wrapped units
-                        const f32x2 s0 = (w0 ? wr2p : wrp)[b >> 1], s1 = (w1 ? wr2p : wrp)[b >> 1];
-                        f32x2 wrb;
-                        if (w0 == w1) wrb = (b & 1) ? __builtin_shufflevector(s0, s0, 1, 1) : __builtin_shufflevector(s0, s0, 0, 0);
-                        else wrb = f32x2{s0[b & 1], s1[b & 1]};
-                        const f32x2 pr = wl2 * wrb;
-                        ab[a] = pr.x; ab[a + 1] = pr.y;
+                    for (int b = BLO; b <= BHI; b++) {
+                        if (b + WLEAD <= BHI) wl[b + WLEAD] = *(lds_f32x4*)(rL + 4 * ((K - b - WLEAD) % RING) * PXW);
+                        if (b == BHI) h = load_head(u + 1, std::integral_constant<int, PF>{}, Head{});  // (before the bases advance)
+                        block(b, wl[b], c, wrp, wr2p);
+                        if constexpr (LASTW) if (b == (BLO < BHI ? BLO + 1 : BLO)) {
+                            // inactive lane-steps (K - a outside 0..14): wrU is the all-zero class and wlU is finite (a zeroed slot or an
+                            // older column), so ab = +0: fma(+0, c, num) = num + (+0) = num (c >= 0 is finite; num is +0 or positive, so
+                            // the sum keeps its sign) and den + (+0) = den, in the scaled domain as in the plain one
+                            const double abU = (double)(wlU * wrU);
+                            us.num = __builtin_fma(abU, cost_sample(glv[K - E0], grU, hi0[3]), us.num);
+                            us.den = us.den + abU;
+                            asm volatile("" :: "v"(us.num), "v"(us.den));
+                        }
+                        asm volatile("" :: "v"(num[0][b]), "v"(num[1][b]), "v"(num[2][b]), "v"(num[3][b]),
+                                           "v"(den[0][b]), "v"(den[1][b]), "v"(den[2][b]), "v"(den[3][b]) : "memory");
+                        __builtin_amdgcn_sched_barrier(0);
                     }
-#pragma unroll
-                    for (int a = 0; a < 4; a++) {
-                        const double abd = (double)ab[a];
-                        num[a][b] = __builtin_fma(abd, c[a - b + 3], num[a][b]);  // exact product: == num + ab*c (x 2^-954)
-                        den[a][b] = den[a][b] + abd;                              // M.cpp:1107-1108 (x 2^120)
-                    }
+                }
+                bL += URI * 4 * LROW;
+                bR += URI * 4 * RROW;
+                asm("" : "+v"(bL), "+v"(bR));
+                if constexpr (WRAPW) {
+                    bR2 += URI * 4 * RROW;
+                    asm("" : "+v"(bR2));
                 }
                 if constexpr (LASTW) {
-                    constexpr int E0 = (K + DLO) & ~3;
-                    (void)E0;
-                    typedef __attribute__((address_space(3))) const uint32_t lds_u32;
-                    // lane -> pixel 4g + a, a = (lane >> 3) & 3, candidate NFIN: position 4g + a (+ 4 NJ), unit row b = a, tap column
-                    // K - a; the grays are the tile columns 4g + K (left: the diagonal-0 sample the row has loaded anyway) and
-                    // 4g + K (+ 4 NJ) (right): the skew a cancels in both
-                    typedef __attribute__((address_space(3))) const float lds_f32;
-                    const float wlU = *(lds_f32*)(uL + u * 4 * LROW);
-                    const float wrU = *(lds_f32*)(uW + u * 4 * RROW);
-                    const uint32_t grU = *(lds_u32*)(uG + u * 4 * RROW + 4 * (RGRAY + K));
-                    // inactive lane-steps (K - a outside 0..14): wrU is the all-zero class and wlU is finite (a zeroed slot or an
-                    // older column), so ab = +0: fma(+0, c, num) = num + (+0) = num (c >= 0 is finite; num is +0 or positive, so
-                    // the sum keeps its sign) and den + (+0) = den, in the scaled domain as in the plain one
-                    const double abU = (double)(wlU * wrU);
-                    us.num = __builtin_fma(abU, cost_sample(glU, grU, hi0[3]), us.num);
-                    us.den = us.den + abU;
-                    asm volatile("" :: "v"(us.num), "v"(us.den));
+                    uL += URI * 4 * LROW;
+                    uW += URI * 4 * RROW;
+                    uG += URI * 4 * RROW;
+                    asm("" : "+v"(uL), "+v"(uW), "+v"(uG));
                 }
-                // the fence: the row's sums are complete here (the arithmetic has no side effect the barrier alone would order)
-                // and no LDS read crosses
-#pragma unroll
-                for (int b = BLO; b <= BHI; b++)
-                    asm volatile("" :: "v"(num[0][b]), "v"(num[1][b]), "v"(num[2][b]), "v"(num[3][b]),
-                                       "v"(den[0][b]), "v"(den[1][b]), "v"(den[2][b]), "v"(den[3][b]) : "memory");
-                __builtin_amdgcn_sched_barrier(0);
             }
-            bL += UR * 4 * LROW;
-            bR += UR * 4 * RROW;
-            asm("" : "+v"(bL), "+v"(bR));
-            if constexpr (WRAPW || EDGE) {
-                bR2 += UR * 4 * RROW;
-                asm("" : "+v"(bR2));
-            }
-            if constexpr (LASTW) {
-                uL += UR * 4 * LROW;
-                uW += UR * 4 * RROW;
-                uG += UR * 4 * RROW;
-                asm("" : "+v"(uL), "+v"(uW), "+v"(uG));
-            }
+        };
+        if constexpr (COMMIT) {
+            // the gathers issued before this loop have landed after CROW rows
+            rows(CROW / URI, std::integral_constant<int, PF_PRE>{});
+            stage_commit<NW>(K + 1, smem, wave, FRESH ? fresh_lane() : lane, st);
+            h = load_head(0, std::integral_constant<int, PF_POST & ~PF_PRE>{}, h);  // what the second loop carries and the first did not
+            rows((KS - CROW) / URI, std::integral_constant<int, PF_POST>{});
+        } else {
+            rows(KS / URI, std::integral_constant<int, PF_PRE>{});
         }
-    };
-    if constexpr (COMMIT) {
-        // the gathers issued before this loop have landed after CROW rows
-        rows(0, CROW / UR);
-        stage_commit<NW>(K + 1, smem, wave, FRESH ? fresh_lane() : lane, st);
-        rows(CROW, (KS - CROW) / UR);
-    } else {
-        rows(0, KS / UR);
     }
 }
 
