@@ -279,7 +279,7 @@ extern "C" int asw_cost_sad(asw_ctx* ctx, const asw_image* left, const asw_image
     if (!ctx || !cost) return ASW_ERR_BAD_ARGUMENT;
     ASW_TRY(check_pair(left, right));
     if (win_size % 2 == 0) return ASW_ERR_EVEN_WINDOW;  // M.cpp:2458-2462
-    if (num_disparity <= 0 || min_disparity < 0 || win_size < 1 || win_size > 128) return ASW_ERR_BAD_ARGUMENT;
+    if (num_disparity <= 0 || min_disparity < 0 || win_size < 1 || win_size > walk_max_kernel()) return ASW_ERR_BAD_ARGUMENT;
     if (left->channels != 3 && left->channels != 1) return ASW_ERR_UNSUPPORTED_LAYOUT;
     if (disparity_type != ASW_DISPARITY_LEFT && disparity_type != ASW_DISPARITY_RIGHT) return ASW_ERR_BAD_ARGUMENT;
     ASW_HIP_TRY(hipSetDevice(ctx->device));
@@ -302,7 +302,7 @@ extern "C" int asw_cost_sad_d(asw_ctx* ctx, const asw_image* left, const asw_ima
     ASW_TRY(check_u8_image(right));
     if ((left->channels != 1 && left->channels != 3) || (right->channels != 1 && right->channels != 3)) return ASW_ERR_UNSUPPORTED_LAYOUT;
     if (win_size % 2 == 0) return ASW_ERR_EVEN_WINDOW;  // M.cpp:2458-2462
-    if (win_size < 1 || win_size > 128) return ASW_ERR_BAD_ARGUMENT;
+    if (win_size < 1 || win_size > walk_max_kernel()) return ASW_ERR_BAD_ARGUMENT;
     if (disparity_type != ASW_DISPARITY_LEFT && disparity_type != ASW_DISPARITY_RIGHT) return ASW_ERR_BAD_ARGUMENT;
     const bool lref = disparity_type == ASW_DISPARITY_LEFT;
     const asw_image* ref = lref ? left : right;   // the view the cost plane belongs to
@@ -343,7 +343,8 @@ extern "C" int asw_cost_ncc(asw_ctx* ctx, const asw_image* left, const asw_image
     if (!ctx || !cost) return ASW_ERR_BAD_ARGUMENT;
     ASW_TRY(check_pair(left, right));
     if (win_size % 2 == 0) return ASW_ERR_EVEN_WINDOW;  // M.cpp:939-942
-    if (num_disparity <= 0 || min_disparity < 0 || win_size < 1 || win_size > 63) return ASW_ERR_BAD_ARGUMENT;
+    if (num_disparity <= 0 || min_disparity < 0 || win_size < 1 || win_size > std::min(ncc_max_window(), walk_max_kernel()))
+        return ASW_ERR_BAD_ARGUMENT;  // run_ncc_cost's limit, before the upload
     if (left->channels != 3 && left->channels != 1) return ASW_ERR_UNSUPPORTED_LAYOUT;
     if (disparity_type != ASW_DISPARITY_LEFT && disparity_type != ASW_DISPARITY_RIGHT) return ASW_ERR_BAD_ARGUMENT;
     ASW_HIP_TRY(hipSetDevice(ctx->device));
@@ -386,7 +387,7 @@ extern "C" int asw_guided_filter(asw_ctx* ctx, const asw_image* guide, const flo
     if (!ctx || !p || !q) return ASW_ERR_BAD_ARGUMENT;
     ASW_TRY(check_u8_image(guide));
     if (guide->channels != 3 && guide->channels != 6) return ASW_ERR_UNSUPPORTED_LAYOUT;  // M.cpp:2732-2734
-    if (r < 1 || r > 128) return ASW_ERR_BAD_ARGUMENT;
+    if (r < 1 || r > walk_max_kernel()) return ASW_ERR_BAD_ARGUMENT;  // r is the box side of every walk
     ASW_HIP_TRY(hipSetDevice(ctx->device));
     const int H = guide->rows, W = guide->cols, C = guide->channels;
     const size_t plane = (size_t)H * W;

@@ -166,6 +166,9 @@ int launch_merge_slices(hipStream_t s, const double* partE, const float* partD, 
 int launch_merge_slices_cols(hipStream_t s, const double* partE, const float* partD, int nz, int H, int W, int col_lo, int col_hi,
                              float* disp);
 int bilateral_lds_row_stride(int win);  // LW of the kernel's sample tile (taps[].x is expressed in it)
+// largest window launch_bilateral serves: the last odd one whose LDS layout fits a workgroup's 160 KB (63: 160160 bytes).  The host
+// entries refuse a larger window before they build a table
+int bilateral_max_window();
 
 // ---- cost kernels (k_cost.hip) ----
 int launch_scharr_x(hipStream_t s, const uint8_t* img, int H, int W, int pad, short* grad /* [H][W+pad][3] */);
@@ -198,6 +201,8 @@ int launch_pad_gray(hipStream_t s, const uint8_t* g, int H, int W, int padL, int
 int launch_box_mean_u8(hipStream_t s, const uint8_t* img, int H, int W, int win, float* mean);  // boxFilter(8U -> 32F)
 int launch_ncc_selfsum(hipStream_t s, const uint8_t* g, const float* mean, int H, int W, int win, double* ss);
 int launch_ncc(hipStream_t s, const NccLaunch& a);
+// largest window launch_ncc serves: the last odd one whose two f32 tiles fit 64 KB of LDS (59: 64232 bytes)
+int ncc_max_window();
 int launch_apply_scales(hipStream_t s, float* vol, int n, size_t plane, const float2* scales);
 
 // ---- driver-side pre/post-processing (k_prep.hip), SURVEY 8f row f3 ----
@@ -208,6 +213,9 @@ int launch_boost_hsv2bgr(hipStream_t s, const uint8_t* hsv, int H, int W, const 
 int launch_disp_to_u8(hipStream_t s, const float* disp, size_t n, int normalize, uint8_t* out, int* mm_scratch);
 
 // ---- box means / guided filter (k_guided.hip) ----
+// largest box side k of the sliding walk behind launch_cost_sad, launch_box_mean_u8 and launch_guided (`r` there): k - 1 halo columns
+// must leave outputs in a two-columns-per-lane strip (64)
+int walk_max_kernel();
 int launch_cost_sad(hipStream_t s, const uint8_t* gl, const uint8_t* gr, int H, int W, int disp_type, int win, int minD,
                     int numD, float* cost);
 struct GuidedLaunch {
@@ -273,6 +281,9 @@ int launch_wmedian_tile_gen(hipStream_t s, const float* cost, const float* wLd, 
 // ---- O(1)-bilateral ASW (BLO1), k_blo1.hip ----
 int launch_blo1(hipStream_t s, const uint8_t* gl, const uint8_t* gr, const float* cost, int step, int H, int W, int disp_type,
                 int win, int numD, float* vol, float* disp);
+// largest window launch_blo1 serves: the last odd one whose tile fits 160 KB of LDS at chunk width 1.  run_blo1 also builds the SAD
+// cost with the walk, so the entry serves min(blo1_max_window(), walk_max_kernel()) rounded down to odd
+int blo1_max_window();
 
 int launch_lr_check(hipStream_t s, const float* dl, const float* dr, int H, int W, float max_diff, float invalid, float* out,
                     unsigned* n_invalid);

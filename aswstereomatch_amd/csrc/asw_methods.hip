@@ -199,7 +199,7 @@ static int run_bilateral(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool kee
     ASW_TRY(check_direction(mp.disparity_type));
     if (direct8 && mp.disparity_type != ASW_DISPARITY_LEFT) return ASW_ERR_UNSUPPORTED_LAYOUT;
     const int flip = mp.disparity_type == ASW_DISPARITY_RIGHT ? 1 : 0;
-    if (mp.win > 127) return ASW_ERR_BAD_ARGUMENT;
+    if (mp.win > bilateral_max_window()) return ASW_ERR_BAD_ARGUMENT;  // before any table, buffer or launch
     const int H = f->rows, W = f->cols;
     const int nD = method_info(direct8 ? ASW_ALG_ADAPTIVE_WEIGHT_8DIRECT : ASW_ALG_ADAPTIVE_WEIGHT)->planes(mp.numD);
     if (direct8)
@@ -311,7 +311,8 @@ int run_ncc_cost(asw_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int H, int 
                         int channels)
 {
     if (win % 2 == 0) return ASW_ERR_EVEN_WINDOW;  // M.cpp:828-831, 939-942
-    if (win < 1 || win > 63) return ASW_ERR_BAD_ARGUMENT;
+    // the box means go through the walk, the cost through k_ncc: both launchers' limits, before the first buffer or launch
+    if (win < 1 || win > std::min(ncc_max_window(), walk_max_kernel())) return ASW_ERR_BAD_ARGUMENT;
     const bool right = disparity_type == ASW_DISPARITY_RIGHT;
     const int max_off = minD + numD - 1, Wp = W + max_off;
     const size_t plane = (size_t)H * W, pplane = (size_t)H * Wp;
@@ -354,6 +355,7 @@ static int run_ncc(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_volu
     if (f->channels != 3) return ASW_ERR_UNSUPPORTED_LAYOUT;
     ASW_TRY(check_direction(mp.disparity_type));
     if (mp.win % 2 == 0) return ASW_ERR_EVEN_WINDOW;
+    if (mp.win < 1 || mp.win > std::min(ncc_max_window(), walk_max_kernel())) return ASW_ERR_BAD_ARGUMENT;  // run_ncc_cost's limit, before agg_begin
     const int H = f->rows, W = f->cols;
     const bool right = mp.disparity_type == ASW_DISPARITY_RIGHT;
     // LEFT, kept: the raw (un-normalised) costs of all numD offsets, for inspection
@@ -382,7 +384,9 @@ static int run_guided(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_v
     ASW_TRY(check_direction(mp.disparity_type));
     const bool right = mp.disparity_type == ASW_DISPARITY_RIGHT;
     if (!variant2 && mp.win % 2 == 0) return ASW_ERR_EVEN_WINDOW;  // getCostSAD_d, M.cpp:2458-2462; computeNCC, M.cpp:939-942
-    if (mp.win < 1 || mp.win > 128) return ASW_ERR_BAD_ARGUMENT;
+    // the window is the box side of every walk (SAD cost, statistics, a/b, q); GuidedF_3 builds its cost with k_ncc as well
+    const int max_win = ncc ? std::min(walk_max_kernel(), ncc_max_window()) : walk_max_kernel();
+    if (mp.win < 1 || mp.win > max_win) return ASW_ERR_BAD_ARGUMENT;
     const int H = f->rows, W = f->cols, n = mp.numD, C = plain3 ? 3 : 6;
     const size_t plane = (size_t)H * W;
     DevBuf& raw = ctx->buf("g_raw");
@@ -641,7 +645,8 @@ static int run_blo1(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_vol
     ASW_TRY(check_direction(mp.disparity_type));
     // the reference indexes setsJB_ks_ds_x[key][offset] with the ABSOLUTE offset (M.cpp:2659): out of range unless 0
     if (mp.minD != 0) return ASW_ERR_BAD_ARGUMENT;
-    if (mp.win < 1 || mp.win > 64) return ASW_ERR_BAD_ARGUMENT;
+    // the SAD cost comes from the walk, the aggregation from k_blo1
+    if (mp.win < 1 || mp.win > std::min(blo1_max_window(), walk_max_kernel())) return ASW_ERR_BAD_ARGUMENT;
     const int step = (int)(256 * mp.blo_rate_r);  // M.cpp:2550
     if (step <= 0) return ASW_ERR_BAD_ARGUMENT;   // the reference's key loop would not terminate
     const int H = f->rows, W = f->cols, n = mp.numD;

@@ -345,9 +345,13 @@ __global__ __launch_bounds__(64) void k_merge_slices_cols(const double* __restri
     disp[o] = bd;
 }
 
+constexpr int GT = 4;  // taps per staging group of every launched form: one LDS layout per window
+constexpr bool lds_fits(int win) { return Layout(win / 2, GT).total <= 160 * 1024; }
+
 template <int HH, int G, int WPE = 2>
 int launch_t(hipStream_t s, const BilateralLaunch& a)
 {
+    static_assert(G == GT, "bilateral_max_window() measures the layout of GT taps per group");
     BilParams p;
     p.H = a.H; p.W = a.W; p.h = a.win / 2; p.minD = a.minD; p.nD = a.nD; p.ntaps = a.ntaps; p.flip = a.flip;
     p.c_begin = a.c_begin; p.resume = a.resume; p.out_slice = a.out_slice;
@@ -359,7 +363,7 @@ int launch_t(hipStream_t s, const BilateralLaunch& a)
     p.x_hi = a.flip ? a.W - c_lo : c_hi;
     p.tile0 = p.x_lo / TW;
     const Layout lay(p.h, G);
-    if (lay.total > 160 * 1024) return ASW_ERR_BAD_ARGUMENT;
+    if (!lds_fits(a.win)) return ASW_ERR_BAD_ARGUMENT;
     auto kern = k_asw_bilateral<HH, G, WPE>;
     if (lay.total > 64 * 1024)
         ASW_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lay.total));
@@ -387,6 +391,16 @@ int launch_t(hipStream_t s, const BilateralLaunch& a)
 
 int bilateral_lds_row_stride(int win) { return TW + 2 * (win / 2); }
 
+int bilateral_max_window()
+{
+    static const int last = [] {  // asked on every call of a host entry: worked out once
+        int win = 1;
+        while (lds_fits(win + 2)) win += 2;
+        return win;
+    }();
+    return last;
+}
+
 int launch_merge_slices(hipStream_t s, const double* partE, const float* partD, int nz, size_t plane, float* disp)
 {
     hipLaunchKernelGGL(k_merge_slices, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, s, partE, partD, nz, plane, disp);
@@ -409,8 +423,8 @@ int launch_bilateral(hipStream_t s, const BilateralLaunch& a)
     switch (a.win) {
     // <half window, taps per staging group, waves per SIMD the register allocator must allow>.
     // win 15, measured on MI355X (1080p, D=128): <7,8,2> 18.6 ms, <7,8,3> 15.7, <7,4,3> 16.3, <7,4,4> 14.3 ms.
-    case 15: return launch_t<7, 4, 4>(s, a);   // the reference's call site (main.cpp:94) and configs C1/C5
-    case 35: return launch_t<17, 4, 2>(s, a);  // config C2 (cost tile 60 KB: two workgroups per CU)
-    default: return launch_t<0, 4, 3>(s, a);   // any other odd window: layout computed at run time
+    case 15: return launch_t<7, GT, 4>(s, a);   // the reference's call site (main.cpp:94) and configs C1/C5
+    case 35: return launch_t<17, GT, 2>(s, a);  // config C2 (cost tile 60 KB: two workgroups per CU)
+    default: return launch_t<0, GT, 3>(s, a);   // any other odd window: layout computed at run time
     }
 }

@@ -144,11 +144,14 @@ __global__ __launch_bounds__(256) void k_blo1(BloParams p, const uint8_t* __rest
     if (x < W && y < H) disp[(size_t)y * W + x] = bd;
 }
 
+// LDS bytes of the form with chunk width dc at this window; launch_blo1 runs the widest chunk that fits its budget
+size_t blo1_lds_bytes(int win, int dc) { return (size_t)(BTH + win - 1) * (BTW + win - 1) * (dc * 5 + 1) + 16; }
+bool blo1_fits1(int win) { return blo1_lds_bytes(win, 1) <= 160 * 1024; }
+
 template <int DC>
 int launch_t(hipStream_t s, const BloParams& p, const uint8_t* gF, const uint8_t* gS, const float* cost, float* vol, float* disp)
 {
-    const size_t cells = (size_t)(BTH + p.win - 1) * (BTW + p.win - 1);
-    const size_t lds = cells * (DC * 5 + 1) + 16;
+    const size_t lds = blo1_lds_bytes(p.win, DC);
     auto kern = k_blo1<DC>;
     if (lds > 64 * 1024)
         ASW_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -160,6 +163,16 @@ int launch_t(hipStream_t s, const BloParams& p, const uint8_t* gF, const uint8_t
 
 }  // namespace
 
+int blo1_max_window()
+{
+    static const int last = [] {  // asked on every call of a host entry: worked out once
+        int win = 1;
+        while (blo1_fits1(win + 2)) win += 2;
+        return win;
+    }();
+    return last;
+}
+
 int launch_blo1(hipStream_t s, const uint8_t* gl, const uint8_t* gr, const float* cost, int step, int H, int W, int disp_type,
                 int win, int numD, float* vol, float* disp)
 {
@@ -167,10 +180,9 @@ int launch_blo1(hipStream_t s, const uint8_t* gl, const uint8_t* gr, const float
     BloParams p{H, W, win, numD, step, left ? -1 : 1};
     const uint8_t* gF = left ? gl : gr;
     const uint8_t* gS = left ? gr : gl;
-    const size_t cells = (size_t)(BTH + win - 1) * (BTW + win - 1);
     // chunk width at win 15, 1080p D=128: 2 -> 29.6 ms, 4 -> 26.6 ms, 8 -> 30.0 ms
-    if (cells * 21 + 16 <= 48 * 1024) return launch_t<4>(s, p, gF, gS, cost, vol, disp);   // win <= 21
-    if (cells * 11 + 16 <= 64 * 1024) return launch_t<2>(s, p, gF, gS, cost, vol, disp);   // win <= 41
-    if (cells * 6 + 16 <= 160 * 1024) return launch_t<1>(s, p, gF, gS, cost, vol, disp);
+    if (blo1_lds_bytes(win, 4) <= 48 * 1024) return launch_t<4>(s, p, gF, gS, cost, vol, disp);   // win <= 23
+    if (blo1_lds_bytes(win, 2) <= 64 * 1024) return launch_t<2>(s, p, gF, gS, cost, vol, disp);   // win <= 49
+    if (blo1_fits1(win)) return launch_t<1>(s, p, gF, gS, cost, vol, disp);                        // win <= blo1_max_window()
     return ASW_ERR_BAD_ARGUMENT;
 }

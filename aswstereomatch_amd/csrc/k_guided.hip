@@ -1129,11 +1129,15 @@ struct PlaneDst {
 // (they share halo columns in L1), 0 = four slices of one strip (they share the slice-independent operands), -1 = default
 struct WalkOpts { int band = 0; int wg_strips = -1; };
 
+// largest box side of a walk with CPL columns per lane: k-1 halo columns must leave outputs in the 64 * CPL columns of a strip
+constexpr int walk_max_kernel_cpl(int cpl) { return 64 * cpl / 2; }
+constexpr int WALK_CPL = 2;  // columns per lane of launch_walk and of every form launch_guided picks for a box wider than 32
+
 template <int NP, int CPL, int ND, int WPE = 4, bool NANSAFE = false, bool RING = false, int PF = 1, class Src, class Dst>
 int launch_walk_t(hipStream_t s, const Src& src, const Dst& dst, int H, int W, int k, int n, int n_active = -1, WalkOpts o = WalkOpts())
 {
     constexpr int SW = 64 * CPL;
-    if (k < 1 || k > SW / 2) return ASW_ERR_BAD_ARGUMENT;  // k-1 halo columns must leave outputs in the strip
+    if (k < 1 || k > walk_max_kernel_cpl(CPL)) return ASW_ERR_BAD_ARGUMENT;
     const int XO = SW - (k - 1);
     const int nxw = (W + XO - 1) / XO;
     const int nzs = (n + ND - 1) / ND;
@@ -1188,7 +1192,7 @@ int launch_walk(hipStream_t s, const Src& src, const Dst& dst, int H, int W, int
     // columns per lane save the shared horizontal sum, ND slices per wavefront share the slice-independent loads.
     // ND > 1 (several slices per wavefront sharing guide pixel and statistics) was measured and rejected: <CPL,ND> =
     // <2,1> 6.2 ms, <2,2> 7.4, <1,2> 7.5, <1,4> 9.7 -- the extra registers cost more occupancy than the traffic saves.
-    return launch_walk_t<NP, 2, ND, 4, NANSAFE>(s, src, dst, H, W, k, n, n_active, o);
+    return launch_walk_t<NP, WALK_CPL, ND, 4, NANSAFE>(s, src, dst, H, W, k, n, n_active, o);
 }
 
 // one ring-less walk form, NaN-safe or plain
@@ -1980,6 +1984,8 @@ int launch_guided3(hipStream_t s, const GuidedLaunch& a, const GuideAccT<SHIFT>&
 }
 
 }  // namespace
+
+int walk_max_kernel() { return walk_max_kernel_cpl(WALK_CPL); }
 
 int launch_cost_sad(hipStream_t s, const uint8_t* gl, const uint8_t* gr, int H, int W, int disp_type, int win, int minD,
                     int numD, float* cost)

@@ -158,12 +158,29 @@ int launch_ncc_selfsum(hipStream_t s, const uint8_t* g, const float* mean, int H
     return ASW_OK;
 }
 
+// the reference tile and one chunk's tile of the other image, f32; no opt-in above 64 KB: the kernel is not built for it
+static size_t ncc_lds_bytes(int win)
+{
+    const int h = win / 2;
+    return (size_t)(NTH + 2 * h) * ((NTW + 2 * h) + (NTW + 2 * h + NDC - 1)) * sizeof(float);
+}
+static bool ncc_fits(int win) { return ncc_lds_bytes(win) <= 64 * 1024; }
+
+int ncc_max_window()
+{
+    static const int last = [] {  // asked on every call of a host entry: worked out once
+        int win = 1;
+        while (ncc_fits(win + 2)) win += 2;
+        return win;
+    }();
+    return last;
+}
+
 int launch_ncc(hipStream_t s, const NccLaunch& a)
 {
     NccParams p{a.H, a.W, a.Wp, a.win, a.minD, a.numD, a.right, a.nwta};
-    const int h = a.win / 2;
-    const size_t lds = (size_t)(NTH + 2 * h) * ((NTW + 2 * h) + (NTW + 2 * h + NDC - 1)) * sizeof(float);
-    if (lds > 64 * 1024) return ASW_ERR_BAD_ARGUMENT;
+    const size_t lds = ncc_lds_bytes(a.win);
+    if (!ncc_fits(a.win)) return ASW_ERR_BAD_ARGUMENT;
     dim3 grid((a.W + NTW - 1) / NTW, (a.H + NTH - 1) / NTH);
     if (a.right)
         hipLaunchKernelGGL(k_ncc<true>, grid, dim3(256), lds, s, p, a.gref, a.mref, a.sref, a.goth, a.moth, a.soth, a.vol, a.disp);

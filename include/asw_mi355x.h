@@ -226,6 +226,26 @@ int asw_preprocess_pair(asw_ctx* ctx, int slot, const asw_image* left_full, cons
 int asw_download_pair(asw_ctx* ctx, int slot, asw_image* left, asw_image* right);
 int asw_download_disparity_u8(asw_ctx* ctx, int slot, asw_image* disp_u8, int normalize);
 
+/* ---- served windows ----
+ * win_size from 1 up to the value below, odd unless stated; the same range holds through asw_stereo_match, asw_match_resident,
+ * asw_stereo_match_batch and the refined entry points.  Order of the checks: an even window gives ASW_ERR_EVEN_WINDOW (the
+ * reference's empty Mat) whatever its size, an odd window past the range gives ASW_ERR_BAD_ARGUMENT before anything is allocated
+ * or launched, and the context serves the next call as if the refused one had not been made.  Each limit is the limit of the kernel
+ * launcher itself (what fits a workgroup's LDS, or a walk's strip); tests/test_gpu_large_windows.py runs every entry at its last
+ * window and at the first refused one.
+ *   asw_aggregate_bilateral, asw_aggregate_direct8 (enum 2, 3)   63   the tile's LDS layout: 160160 of 163840 bytes
+ *   asw_ncc_disparity (enum 11), asw_cost_ncc                    59   two f32 tiles in 64 KB of LDS
+ *   asw_aggregate_guided (enum 7)                                63   box side of the sliding walk <= 64
+ *   asw_aggregate_guided2 (enum 8)                               64   the same; the window is the box side as it stands, even or odd
+ *   asw_aggregate_guided3 (enum 9)                               59   the smaller of the walk's limit and NCC's
+ *   asw_guided_filter                                         r <= 64   even or odd
+ *   asw_cost_sad, asw_cost_sad_d                                 63   box side of the walk
+ *   asw_aggregate_blo1 (enum 6)                                  63   its SAD cost comes from the walk (the kernel's own LDS: 133)
+ *   asw_aggregate_wmedian (enum 10)                              45   2048 slots of the per-pixel sort
+ *   asw_aggregate_geodesic (enum 4), asw_geodesic_dist           35   instantiated window sizes
+ *   cross-based aggregation, AD-Census (enum 12), refinement     35   see above and below
+ * asw_aggregate_bilgrid takes no window. */
+
 /* ---- per-method entry points with explicit parameters (M.h:133-184) ---- */
 /* computeAdaptiveWeight, M.h:133-134, M.cpp:1016-1156 */
 int asw_aggregate_bilateral(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp,
