@@ -33,6 +33,7 @@ __all__ = [
     "SGBM_PATH_BLTR", "SGBM_PATHS_3WAY", "SGBM_PATHS_HH4", "SGBM_PATHS_SGBM", "SGBM_PATHS_HH",
     "cross_algorithm", "computeAdaptiveWeight_cross",
     "adcensus_algorithm", "computeCensus", "computeADCensus", "computeAdaptiveWeight_adcensus",
+    "twopass_algorithm", "computeAdaptiveWeight_twopass",
     "AswError",
 ]
 
@@ -99,6 +100,19 @@ def adcensus_algorithm(tau=20, lambda_ad=10, lambda_census=30):
     bad = tau < 0 or tau > 255 or lambda_ad < 1 or lambda_ad > 31 or lambda_census < 1 or lambda_census > 255
     return (_ALG_ADCENSUS_PARAMS | ((0 if bad else lambda_ad) << 24) | ((lambda_census & 0xFF) << 16) | ((tau & 0xFF) << 8) |
             int(StereoMatchingAlgorithms.ADAPTIVE_WEIGHT_CROSS))
+
+
+_ALG_TWOPASS_PARAMS = 0x10000000  # ASW_ALG_TWOPASS_PARAMS
+
+
+def twopass_algorithm(gamma_c=30, gamma_g=20):
+    """asw_alg_twopass of asw_mi355x.h: the value of `algorithmType` that runs ADAPTIVE_WEIGHT as the two-pass (separable)
+    approximation with the integer gammas gamma_c and gamma_g (1..255 each) in every call that takes an
+    algorithm; an argument out of range gives a value the library refuses with ERR_BAD_ARGUMENT (that gamma's field 0)."""
+    gamma_c, gamma_g = int(gamma_c), int(gamma_g)
+    c = 0 if (gamma_c < 1 or gamma_c > 255) else gamma_c
+    g = 0 if (gamma_g < 1 or gamma_g > 255) else gamma_g
+    return _ALG_TWOPASS_PARAMS | (g << 16) | (c << 8) | int(StereoMatchingAlgorithms.ADAPTIVE_WEIGHT)
 
 
 PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL = 0, 1  # StereoBM::PREFILTER_*; asw_stereo_bm serves XSOBEL
@@ -312,6 +326,18 @@ class Context:
             return self._lib.asw_stereo_match(h, l, r, d, int(dispType), alg, winSize, minDisparity, numDisparity, *args)
         return self._aggregate("asw_aggregate_adcensus", _A.ADAPTIVE_WEIGHT_CROSS, numDisparity, leftImg, rightImg, (),
                                return_cost_volume, fn=call)
+
+    def computeAdaptiveWeight_twopass(self, leftImg, rightImg, gamma_c=30, gamma_g=20, dispType=DISPARITY_LEFT, winSize=15,
+                                      minDisparity=0, numDisparity=64, return_cost_volume=False):
+        """Two-pass (separable) adaptive-support-weight aggregation (asw_aggregate_twopass; not in the
+        reference): a vertical, then a horizontal 1-D weighted pass, 2 * winSize taps in place of winSize^2 - 1; integer gammas
+        1..255; candidates minDisparity .. minDisparity + numDisparity inclusive; 1- or 3-channel pairs."""
+        alg = twopass_algorithm(gamma_c, gamma_g)
+
+        def call(h, l, r, d, *args):
+            return self._lib.asw_stereo_match(h, l, r, d, int(dispType), alg, winSize, minDisparity, numDisparity, *args)
+        return self._aggregate("asw_aggregate_twopass", _A.ADAPTIVE_WEIGHT, numDisparity, leftImg, rightImg, (), return_cost_volume,
+                               fn=call)
 
     # ---- semi-global block matching (DESIGN.md section 4.8) ----
     def getDisparity_SGBM(self, srcLeft, srcRight, winSize=15, minDisparity=0, numDisparity=64):
@@ -720,6 +746,7 @@ computeAdaptiveWeight_cross = _bind("computeAdaptiveWeight_cross")
 computeCensus = _bind("computeCensus")
 computeADCensus = _bind("computeADCensus")
 computeAdaptiveWeight_adcensus = _bind("computeAdaptiveWeight_adcensus")
+computeAdaptiveWeight_twopass = _bind("computeAdaptiveWeight_twopass")
 winnerTakeAll = _bind("winnerTakeAll")
 getDisparity_SGBM = _bind("getDisparity_SGBM")
 sgbm = _bind("sgbm")

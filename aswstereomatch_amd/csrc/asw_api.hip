@@ -40,7 +40,15 @@ int match_host(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_
 int decode_algorithm(int algorithm, int* method, MatchParams* mp)
 {
     *method = algorithm;
-    if (!(algorithm & (ASW_ALG_CROSS_PARAMS | ASW_ALG_ADCENSUS_PARAMS))) return ASW_OK;
+    if (!(algorithm & (ASW_ALG_CROSS_PARAMS | ASW_ALG_ADCENSUS_PARAMS | ASW_ALG_TWOPASS_PARAMS))) return ASW_OK;
+    if (!(algorithm & (ASW_ALG_CROSS_PARAMS | ASW_ALG_ADCENSUS_PARAMS))) {  // asw_alg_twopass(): bit 28 is adcensus's lambda_ad otherwise
+        if ((algorithm & 0xFF) != ASW_ALG_ADAPTIVE_WEIGHT) return ASW_ERR_UNSUPPORTED_METHOD;
+        const int gamma_c = (algorithm >> 8) & 0xFF, gamma_g = (algorithm >> 16) & 0xFF;  // bits 24..27 and 31 stay clear
+        if (gamma_c == 0 || gamma_g == 0 || (algorithm & 0x0F000000) || algorithm < 0) return ASW_ERR_BAD_ARGUMENT;
+        if (mp) { mp->twopass = 1; mp->gamma_c = gamma_c; mp->gamma_g = gamma_g; }
+        *method = ASW_ALG_ADAPTIVE_WEIGHT;
+        return ASW_OK;
+    }
     const MethodInfo* m = method_info(algorithm & 0xFF);
     if (!m || !m->packed_params) return ASW_ERR_UNSUPPORTED_METHOD;
     const int tau = (algorithm >> 8) & 0xFF, f16 = (algorithm >> 16) & 0xFF;

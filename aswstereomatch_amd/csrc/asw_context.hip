@@ -133,6 +133,7 @@ extern "C" void asw_destroy(asw_ctx* ctx)
     ctx->bil.cells.release();
     ctx->refine.tc.release();
     ctx->refine.ts.release();
+    ctx->twopass.t.release();
     ctx->wm_lut2.release();
     ctx->wm_wd.release();
     for (int i = 0; i < 4; i++)

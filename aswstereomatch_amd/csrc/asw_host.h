@@ -33,6 +33,7 @@ struct MatchParams {
     int disparity_type, win, minD, numD;  // disparity_type as the caller passed it; run_method strips the sub-pixel flag into `subpixel`
     int subpixel = 0;                   // 0 | ASW_DISPARITY_SUBPIXEL_PARABOLA | ASW_DISPARITY_SUBPIXEL_EQUIANGULAR
     double gamma_c = 30, gamma_g = 20;  // M.cpp:58
+    int twopass = 0;                    // entry 2 as the two-pass approximation (asw_alg_twopass()): the gammas above are its integers
     double eps = 1e-6;                  // M.cpp:73,76
     double rate_s = 10, rate_r = 10;    // M.cpp:82
     double blo_rate_r = 0.015;          // M.cpp:70
@@ -64,9 +65,10 @@ struct MethodInfo {
 const MethodInfo* method_info(int method);  // the row of a plain (decoded) selector value; null for a value outside the table
 
 // The selector's `algorithm` as a caller passes it -> the plain enum value in *method and, for an asw_alg_cross() or
-// asw_alg_adcensus() value, its parameters in mp's cross_* / lambda_* fields (left alone otherwise; mp may be null).
-// ASW_ERR_UNSUPPORTED_METHOD / ASW_ERR_BAD_ARGUMENT for the encodings asw_mi355x.h refuses; a value with neither
-// ASW_ALG_CROSS_PARAMS nor ASW_ALG_ADCENSUS_PARAMS passes through as it is.
+// asw_alg_adcensus() value, its parameters in mp's cross_* / lambda_* fields, for an asw_alg_twopass() value mp's twopass flag and
+// gammas (left alone otherwise; mp may be null).
+// ASW_ERR_UNSUPPORTED_METHOD / ASW_ERR_BAD_ARGUMENT for the encodings asw_mi355x.h refuses; a value with none of
+// ASW_ALG_CROSS_PARAMS, ASW_ALG_ADCENSUS_PARAMS and ASW_ALG_TWOPASS_PARAMS passes through as it is.
 int decode_algorithm(int algorithm, int* method, MatchParams* mp);
 // AD-Census cost of a device pair into cost u8 [numD][H][W]: gray pair, two census transforms, then the
 // Hamming distance alone (lambda_ad = 0) or TA[AD] + TC[Hamming] with the tables of the two lambdas (each 1..255)

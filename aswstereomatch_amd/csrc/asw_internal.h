@@ -86,6 +86,11 @@ struct RefineTables {  // cached per (win, gamma_c, gamma_s, channels): integer 
     DevBuf ts;  // u32 [win/2 + 1][win/2 + 1]: floor(256 * exp(-sqrt(i*i + j*j) / gamma_s) + 0.5)
 };
 
+struct TwoPassTable {  // cached per (win, gamma_c, gamma_g): the weight table of the two-pass method (k_twopass.hip)
+    int win = 0, gamma_c = 0, gamma_g = 0;
+    DevBuf t;  // float [win / 2 + 1][256]: (float)exp(-(dc / gamma_c + r / gamma_g))
+};
+
 struct asw_ctx {
     int device = 0;
     AswTuning tune;
@@ -98,6 +103,7 @@ struct asw_ctx {
     std::map<std::string, DevBuf> scratch;  // named grow-only scratch buffers
     BilateralTables bil;
     RefineTables refine;
+    TwoPassTable twopass;
     int census_lambda_ad = 0, census_lambda_census = 0;  // what buf("census_tables") holds (asw_methods.hip: ensure_census_tables)
     // weighted-median tables: exp() LUT of the colour weight per rateR, space kernel per (win, rateS)
     DevBuf wm_lut2, wm_wd;
@@ -169,6 +175,21 @@ int bilateral_lds_row_stride(int win);  // LW of the kernel's sample tile (taps[
 // largest window launch_bilateral serves: the last odd one whose LDS layout fits a workgroup's 160 KB (63: 160160 bytes).  The host
 // entries refuse a larger window before they build a table
 int bilateral_max_window();
+
+// ---- two-pass (separable) ASW (k_twopass.hip), DESIGN.md section 4.16 ----
+struct TwoPassLaunch {
+    const uint8_t* gL;   // reference gray image (RIGHT: the right image), read mirrored when flip
+    const uint8_t* gR;
+    int H, W, win, minD, nD;  // nD = number of candidates (numD + 1: the inclusive range of entry 2)
+    const float* table;  // TwoPassTable: [win / 2 + 1][256]
+    int flip;            // 1: mirrored problem (DISPARITY_RIGHT)
+    float* vol;          // optional [nD][H][W]
+    float* disp;         // [H][W]
+};
+int launch_twopass(hipStream_t s, const TwoPassLaunch& a);
+// largest window launch_twopass serves: the last odd one whose LDS layout (sums of a chunk, table, two gray tiles) fits a
+// workgroup's 160 KB (95: 162976 bytes).  The host entry refuses a larger window before it builds a table
+int twopass_max_window();
 
 // ---- cost kernels (k_cost.hip) ----
 int launch_scharr_x(hipStream_t s, const uint8_t* img, int H, int W, int pad, short* grad /* [H][W+pad][3] */);

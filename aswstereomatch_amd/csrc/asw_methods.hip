@@ -273,8 +273,55 @@ static int run_bilateral(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool kee
     return agg_end(ctx, 1);
 }
 
+// ------------------------------------------------------------------------------------------
+// two-pass (separable) ASW (Wang et al. 2006): entry 2 with an asw_alg_twopass() value; not in the reference
+// ------------------------------------------------------------------------------------------
+static int ensure_twopass_table(asw_ctx* ctx, int win, int gamma_c, int gamma_g)
+{
+    TwoPassTable& t = ctx->twopass;
+    if (t.win == win && t.gamma_c == gamma_c && t.gamma_g == gamma_g && t.t.p) return ASW_OK;
+    t.win = 0;
+    const int h = win / 2;
+    std::vector<float> tab((size_t)(h + 1) * 256);
+    for (int r = 0; r <= h; r++)
+        for (int dc = 0; dc < 256; dc++) tab[(size_t)r * 256 + dc] = (float)exp(-((double)dc / gamma_c + (double)r / gamma_g));
+    ASW_TRY(t.t.ensure(tab.size() * sizeof(float)));
+    ASW_HIP_TRY(hipMemcpyAsync(t.t.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));  // the host vector dies at return
+    t.win = win; t.gamma_c = gamma_c; t.gamma_g = gamma_g;
+    return ASW_OK;
+}
+
+static int run_twopass(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_volume)
+{
+    if (mp.win % 2 == 0) return ASW_ERR_EVEN_WINDOW;
+    if (mp.win < 1 || mp.win > twopass_max_window()) return ASW_ERR_BAD_ARGUMENT;  // before any table, buffer or launch
+    if (f->channels != 3 && f->channels != 1) return ASW_ERR_UNSUPPORTED_LAYOUT;
+    ASW_TRY(check_direction(mp.disparity_type));
+    const int gamma_c = (int)mp.gamma_c, gamma_g = (int)mp.gamma_g;  // decode_algorithm: integers in 1..255
+    if (gamma_c < 1 || gamma_c > 255 || gamma_g < 1 || gamma_g > 255) return ASW_ERR_BAD_ARGUMENT;
+    const int flip = mp.disparity_type == ASW_DISPARITY_RIGHT ? 1 : 0;
+    const int H = f->rows, W = f->cols, nD = method_info(ASW_ALG_ADAPTIVE_WEIGHT)->planes(mp.numD);
+    ASW_TRY(ensure_twopass_table(ctx, mp.win, gamma_c, gamma_g));
+    ASW_TRY(ensure_outputs(f, nD, keep_volume));
+    const uint8_t *gl, *gr;
+    ASW_TRY(gray_pair(ctx, f->L.as<uint8_t>(), f->R.as<uint8_t>(), f->channels, H, W, &gl, &gr));
+    TwoPassLaunch a;
+    a.gL = flip ? gr : gl;  // RIGHT: reference image = right, read mirrored in the kernel
+    a.gR = flip ? gl : gr;
+    a.flip = flip;
+    a.H = H; a.W = W; a.win = mp.win; a.minD = mp.minD; a.nD = nD;
+    a.table = ctx->twopass.t.as<float>();
+    a.vol = keep_volume ? f->vol.as<float>() : nullptr;
+    a.disp = f->disp.as<float>();
+    ASW_TRY(agg_begin(ctx));
+    ASW_TRY(launch_twopass(ctx->stream, a));
+    return agg_end(ctx, 1);
+}
+
 static int run_bilateral_classic(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_volume)
 {
+    if (mp.twopass) return run_twopass(ctx, f, mp, keep_volume);
     return run_bilateral(ctx, f, mp, keep_volume, false);
 }
 

@@ -429,6 +429,17 @@ inline AswMat computeAdaptiveWeight_adcensus(AswMat leftImg, AswMat rightImg, Di
     }, "computeAdaptiveWeight_adcensus");
 }
 
+// Not in the reference: two-pass (separable) adaptive-support-weight aggregation (asw_aggregate_twopass) -- a
+// vertical, then a horizontal 1-D weighted pass, integer gammas 1..255 -> the f32 map; empty Mat for an even window
+inline AswMat computeAdaptiveWeight_twopass(AswMat leftImg, AswMat rightImg, int gamma_c = 30, int gamma_g = 20,
+                                            DisparityType dispType = DISPARITY_LEFT, int winSize = 15, int minDisparity = 0,
+                                            int numDisparity = 64)
+{
+    return asw::detail::aggregate(leftImg, rightImg, [&](asw_ctx* c, asw_image* l, asw_image* r, asw_image* o) {
+        return asw_aggregate_twopass(c, l, r, o, gamma_c, gamma_g, (int)dispType, winSize, minDisparity, numDisparity, nullptr, 0);
+    }, "computeAdaptiveWeight_twopass");
+}
+
 // Not in the reference: the cross-check that consumes a DISPARITY_LEFT and a DISPARITY_RIGHT map (asw_lr_check)
 inline AswMat leftRightCheck(AswMat dispLeft, AswMat dispRight, float maxDiff = 1.0f, float invalidValue = -1.0f, int* nInvalid = nullptr)
 {

@@ -128,6 +128,35 @@ static inline int asw_alg_adcensus(int tau, int lambda_ad, int lambda_census)
            ASW_ALG_ADAPTIVE_WEIGHT_CROSS;
 }
 
+/* ---- two-pass (separable) adaptive-support-weight aggregation (Wang et al. 2006; not in the reference) ----
+ * Selector entry 2 with the support weight w(p, q) replaced by w(p, p') w(p', q), p' the pixel in p's row and q's column: a vertical
+ * 1-D weighted pass, then a horizontal one over its sums -- 2 win taps per (pixel, candidate) instead of win^2 - 1.  Every call that
+ * takes `algorithm` serves it; both directions, 1- or 3-channel 8U pairs (3 channels through the context's cvtColor(BGR2GRAY),
+ * asw_set_gray_bits; 1 channel as it is), the sub-pixel flags as for the other methods; candidates min_d .. min_d + num_d inclusive
+ * (asw_volume_planes = num_d + 1, as for the plain value 2).  gL / gR the gray pair, h = win_size / 2, clamp to the image:
+ *   T[r][dc] = (float)exp(-((double)dc / gamma_c + (double)r / gamma_g)), r = 0..h, dc = 0..255 (libm, double); the centre tap counts;
+ *   DISPARITY_LEFT, xr = max(0, x - d):
+ *   vertical, j = -h..h ascending, yy = clamp(y + j): ab = T[|j|][|gL(yy,x) - gL(y,x)|] * T[|j|][|gR(yy,xr) - gR(y,xr)|] (f32);
+ *     vn += (double)ab * |gL(yy,x) - gR(yy,xr)|, vd += (double)ab (f64);
+ *   horizontal, i = -h..h ascending, xx = clamp(x + i), xri = clamp(xr + i):
+ *     ab = T[|i|][|gL(y,xx) - gL(y,x)|] * T[|i|][|gR(y,xri) - gR(y,xr)|] (f32);
+ *     num = num + (double)ab * vn(xx,y,d), den = den + (double)ab * vd(xx,y,d) (f64, each product rounded before it is added);
+ *   E = num / den (f64); volume plane (float)E; map: strict '<' of E in ascending d, min_d + index.
+ *   DISPARITY_RIGHT: DISPARITY_LEFT of the x-mirrored, swapped pair, mirrored back.
+ * asw_alg_twopass(gamma_c, gamma_g) forms the value of `algorithm`: bits 0-7 = 2, bits 8-15 = gamma_c (1..255), bits 16-23 = gamma_g
+ * (1..255), bit 28 set (ASW_ALG_TWOPASS_PARAMS), bits 24-27 and 29-31 clear; an argument out of range gives that gamma's field 0.  A
+ * value with bit 29 or 30 set is read as above (bit 28 belongs to lambda_ad there); otherwise, with bit 28 set, a low byte other than
+ * 2 gives ASW_ERR_UNSUPPORTED_METHOD and a gamma field 0 or any of bits 24-27 / 31 ASW_ERR_BAD_ARGUMENT (asw_volume_planes: 0).
+ * win_size odd (even: ASW_ERR_EVEN_WINDOW) in 1..95 (above: ASW_ERR_BAD_ARGUMENT, before anything is allocated); rows * cols < 2^31
+ * and rows <= 262140.  asw_get_timing: aggregate_ms covers the one kernel (aggregate_launches = 1), cost_ms the gray conversion.
+ * asw_aggregate_twopass (inline, after asw_stereo_match below) is the per-method form; neither is a symbol of the library. */
+enum { ASW_ALG_TWOPASS_PARAMS = 0x10000000 };
+static inline int asw_alg_twopass(int gamma_c, int gamma_g)
+{
+    const int c = (gamma_c < 1 || gamma_c > 255) ? 0 : gamma_c, g = (gamma_g < 1 || gamma_g > 255) ? 0 : gamma_g;
+    return ASW_ALG_TWOPASS_PARAMS | (g << 16) | (c << 8) | ASW_ALG_ADAPTIVE_WEIGHT;
+}
+
 /* cv::Mat depth codes */
 enum { ASW_8U = 0, ASW_16S = 3, ASW_32F = 5 };
 
@@ -196,6 +225,15 @@ static inline int asw_aggregate_adcensus(asw_ctx* ctx, const asw_image* left, co
 {
     return asw_stereo_match(ctx, left, right, disp, disparity_type, asw_alg_adcensus(tau, lambda_ad, lambda_census), win_size,
                             min_disparity, num_disparity, cost_volume_out, cost_volume_floats);
+}
+
+/* Two-pass ASW with explicit parameters (above): asw_stereo_match with algorithm = asw_alg_twopass(gamma_c, gamma_g). */
+static inline int asw_aggregate_twopass(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp, int gamma_c,
+                                        int gamma_g, int disparity_type, int win_size, int min_disparity, int num_disparity,
+                                        float* cost_volume_out, size_t cost_volume_floats)
+{
+    return asw_stereo_match(ctx, left, right, disp, disparity_type, asw_alg_twopass(gamma_c, gamma_g), win_size, min_disparity,
+                            num_disparity, cost_volume_out, cost_volume_floats);
 }
 
 /* Planes of the cost volume `algorithm` produces for num_disparity candidates (what cost_volume_out must hold);

@@ -36,6 +36,12 @@ the kept volume: the sgbm_paths cases of matcher_cases.random_case sent through 
 mismatch prints the tag matcher_cases.build_case("sgbm_paths", tag[1:]) rebuilds.
 
     python tools/fuzz_parity.py --seconds 120 --seed 1 --only sgbm_census
+
+The leg twopass is the two-pass (separable) ASW (asw_alg_twopass over entry 2) against tests/twopass_ref.py,
+volume and map, with and without the kept volume; its cases come from twopass_ref.random_case and a mismatch prints the tag
+twopass_ref.build_case rebuilds.
+
+    python tools/fuzz_parity.py --seconds 120 --seed 1 --only twopass
 """
 import argparse
 import os
@@ -55,6 +61,7 @@ import asw_cases  # noqa: E402
 import cross_ref as cr  # noqa: E402
 import matcher_cases as mc  # noqa: E402
 import sgbm_census_ref as scr  # noqa: E402
+import twopass_ref as tpr  # noqa: E402
 
 A = asw.StereoMatchingAlgorithms
 
@@ -76,9 +83,9 @@ class SgbmCensusLeg:
 
 
 # checked against the CPU oracle (oracle/); the legs (mc.FAMILIES) are checked against the restatements under tests/
-LEGS = tuple(mc.FAMILIES) + ("cross", "adcensus", "sgbm_census")
+LEGS = tuple(mc.FAMILIES) + ("cross", "adcensus", "sgbm_census", "twopass")
 # legs whose module has random_case / gpu_result of its own
-REF_LEGS = {"cross": cr, "adcensus": ac, "sgbm_census": SgbmCensusLeg}
+REF_LEGS = {"cross": cr, "adcensus": ac, "sgbm_census": SgbmCensusLeg, "twopass": tpr}
 ORACLE_METHODS = ["classic", "direct8", "geodesic", "guided", "guided2", "guided3", "wmedian", "blo1", "ncc", "ncc_cost",
                   "ad_tad", "similarity", "sad", "geodist", "gfilter", "prep", "bilgrid", "lrcheck", "resident", "batch"]
 
