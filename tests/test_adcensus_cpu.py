@@ -16,6 +16,7 @@ from aswstereomatch_amd import _lib
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import adcensus_ref as ac  # noqa: E402
 import cross_ref as cr  # noqa: E402
+from shim_build import C99, build_demo  # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import asw_oracle as O  # noqa: E402
@@ -144,9 +145,7 @@ def _c_values(tmp_path):
                    '           asw_alg_adcensus(20, 0, 30), asw_alg_adcensus(20, 10, 0), asw_alg_adcensus(-1, 10, 256),\n'
                    '           ASW_ALG_ADCENSUS_PARAMS);\n    return 0;\n}\n')
     exe = tmp_path / "alg"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-I" + os.path.join(ROOT, "include"), str(src),
-                           "-L" + os.path.join(ROOT, "aswstereomatch_amd"), "-lasw_mi355x",
-                           "-Wl,-rpath," + os.path.join(ROOT, "aswstereomatch_amd"), "-Wl,-rpath,/opt/rocm/lib", "-o", str(exe)])
+    build_demo(src, exe, **C99)
     return [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, timeout=60, check=True).stdout.split()]
 
 

@@ -2,9 +2,13 @@
 library, and -- on the GPU -- gives the same disparity as the ctypes path."""
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from shim_build import C99, build_demo  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "tests", "cpp", "shim_demo")
@@ -13,36 +17,17 @@ EXE_CV = os.path.join(ROOT, "tests", "cpp", "shim_demo_cv")
 
 
 def _build():
-    from aswstereomatch_amd import build
-
-    build.build()
-    cmd = ["g++", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "shim_demo.cpp"),
-           "-L" + os.path.join(ROOT, "aswstereomatch_amd"), "-lasw_mi355x", "-Wl,-rpath," + os.path.join(ROOT, "aswstereomatch_amd"),
-           "-Wl,-rpath,/opt/rocm/lib", "-o", EXE]
-    subprocess.check_call(cmd)
+    build_demo("shim_demo.cpp", EXE)
 
 
 def _build_cv():
     """The header's cv::Mat branch (-DASW_WITH_OPENCV) against tests/cpp/cv_stub/opencv2/core.hpp, a compile-only stand-in for the
     few OpenCV declarations the header touches (OpenCV itself is absent here)."""
-    from aswstereomatch_amd import build
-
-    build.build()
-    cmd = ["g++", "-std=c++17", "-Wall", "-Wextra", "-DASW_WITH_OPENCV", "-I" + os.path.join(ROOT, "tests", "cpp", "cv_stub"),
-           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "shim_demo.cpp"),
-           "-L" + os.path.join(ROOT, "aswstereomatch_amd"), "-lasw_mi355x", "-Wl,-rpath," + os.path.join(ROOT, "aswstereomatch_amd"),
-           "-Wl,-rpath,/opt/rocm/lib", "-o", EXE_CV]
-    subprocess.check_call(cmd)
+    build_demo("shim_demo.cpp", EXE_CV, cv=True)
 
 
 def _build_c():
-    from aswstereomatch_amd import build
-
-    build.build()
-    cmd = ["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-I" + os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "abi_demo.c"), "-L" + os.path.join(ROOT, "aswstereomatch_amd"), "-lasw_mi355x",
-           "-Wl,-rpath," + os.path.join(ROOT, "aswstereomatch_amd"), "-Wl,-rpath,/opt/rocm/lib", "-o", CEXE]
-    subprocess.check_call(cmd)
+    build_demo("abi_demo.c", CEXE, **C99)
 
 
 def test_abi_header_is_plain_c99():

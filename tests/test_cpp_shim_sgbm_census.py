@@ -7,27 +7,13 @@ import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-
-
-def _build(exe, cv):
-    from aswstereomatch_amd import build
-
-    if not os.path.exists(build.LIB):
-        build.build()
-    cmd = ["g++", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "sgbm_census_demo.cpp"),
-           "-L" + os.path.join(ROOT, "aswstereomatch_amd"), "-lasw_mi355x", "-Wl,-rpath," + os.path.join(ROOT, "aswstereomatch_amd"),
-           "-Wl,-rpath,/opt/rocm/lib", "-o", exe]
-    if cv:  # the cv::Mat branch against the compile-only stand-in for the OpenCV declarations the header names
-        cmd[3:3] = ["-Wextra", "-DASW_WITH_OPENCV", "-I" + os.path.join(ROOT, "tests", "cpp", "cv_stub")]
-    subprocess.check_call(cmd)
-    return exe
+from shim_build import build_demo  # noqa: E402
 
 
 @pytest.mark.parametrize("cv", [False, True])
 def test_sgbm_census_demo_compiles(tmp_path, cv):
-    assert os.path.exists(_build(str(tmp_path / "sgbm_census_demo"), cv))
+    assert os.path.exists(build_demo("sgbm_census_demo.cpp", tmp_path / "sgbm_census_demo", cv))
 
 
 @pytest.mark.gpu
@@ -36,7 +22,7 @@ def test_shim_get_disparity_sgbm_census(tmp_path, cv):
     import sgbm_census_ref as cref
     import sgbm_paths_ref as pref
 
-    exe = _build(str(tmp_path / "sgbm_census_demo"), cv)
+    exe = build_demo("sgbm_census_demo.cpp", tmp_path / "sgbm_census_demo", cv)
     out = tmp_path / "d.raw"
     for cn in (3, 1):
         L, R = cref.shape_pair(40, 96, 32, cn, seed=53)

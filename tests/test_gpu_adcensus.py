@@ -1,9 +1,11 @@
 """AD-Census matching on the GPU (k_census.hip in front of entry 12's kernels) against the restatement of
 tests/adcensus_ref.py.  Every number before the one correctly rounded division is an integer: every comparison is np.array_equal,
-on the two cost builders, on the aggregated volume and on the map.  What the pairs exercise (Hamming distances from 0 to 62, costs
-above 127, winners the AD term alone would not pick) and the margin of the two tables are asserted on the restatement alone in
-tests/test_adcensus_cpu.py."""
-import ctypes as C
+on the two cost builders, on the aggregated volume and on the map.
+
+This file holds what belongs to the method's own kernels; what every selector method owes its callers (forms and paths, batch,
+sub-pixel, refined calls, statuses, the seeded sweep) is in tests/test_gpu_selector_contract.py.  What the pairs exercise
+(Hamming distances from 0 to 62, costs above 127, winners the AD term alone would not pick) and the margin of the two tables are
+asserted on the restatement alone in tests/test_adcensus_cpu.py."""
 import os
 import sys
 
@@ -11,17 +13,14 @@ import numpy as np
 import pytest
 
 import aswstereomatch_amd as asw
-from aswstereomatch_amd import _lib
 from aswstereomatch_amd._lib import AswError
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import adcensus_ref as ac  # noqa: E402
 import cross_ref as cr  # noqa: E402
-import refine_ref as rr  # noqa: E402
-import subpixel_ref as sp  # noqa: E402
+from selector_methods import region_views as _pair  # noqa: E402
 
 LEFT, RIGHT = asw.DISPARITY_LEFT, asw.DISPARITY_RIGHT
-MODES = (asw.SUBPIXEL_PARABOLA, asw.SUBPIXEL_EQUIANGULAR)
 ADC = asw.adcensus_algorithm
 
 pytestmark = pytest.mark.gpu
@@ -32,13 +31,6 @@ def ctx():
     c = asw.Context(0)
     yield c
     c.close()
-
-
-def _pair(H, W, cn, D, seed=None, pad=0):
-    L, R, _ = cr.region_pair(H, W + pad, max(2, D), H * 1000 + W if seed is None else seed, (5, 7), 0.12, block=8)
-    if cn == 1:
-        L, R = np.ascontiguousarray(L[:, :, 1]), np.ascontiguousarray(R[:, :, 1])
-    return L[:, :W], R[:, :W]  # pad > 0: views whose rows carry padding
 
 
 # ---------------------------------------------------------------- the two cost builders
@@ -166,93 +158,9 @@ def test_padded_row_views(ctx):
     assert np.array_equal(ctx.computeAdaptiveWeight_adcensus(np.ascontiguousarray(L), np.ascontiguousarray(R), RIGHT, 20, 10, 30, 15, 3, 17), disp)
 
 
-# ---------------------------------------------------------------- forms and paths
-def _case1():
+def test_gray_bits(ctx):
     H, W, D, cell, seed, amp, win = cr.REGION_CASES[1]
     L, R, _ = cr.region_pair(H, W, D, seed, cell, amp)
-    return H, W, D, win, L, R
-
-
-def test_selector_forms_and_paths(ctx):
-    H, W, D, win, L, R = _case1()
-    enc = ADC(20, 10, 30)
-    assert enc == ADC()
-    for dt in (LEFT, RIGHT):
-        S, N, E, disp = ac.match(L, R, int(dt), 20, 10, 30, win, 0, D)
-        d, v = ctx.stereoMatching(L, R, dt, enc, win, 0, D, return_cost_volume=True)
-        assert np.array_equal(d, disp) and np.array_equal(v, E)
-        assert np.array_equal(ctx.stereoMatching(L, R, dt, enc, win, 0, D), disp)
-        t = ctx.timing()
-        assert t["aggregate_launches"] == 3 and t["total_ms"] >= t["aggregate_ms"] > 0 and t["cost_ms"] > 0
-        ctx.upload_pair(31, L, R)
-        ctx.match_resident(31, dt, enc, win, 0, D, keep_volume=True)
-        assert np.array_equal(ctx.download_disparity(31, (H, W)), disp)
-        assert np.array_equal(ctx.download_volume(31, (D, H, W)), E)
-        ctx.match_resident(31, dt, enc, win, 0, D, keep_volume=False)
-        assert np.array_equal(ctx.download_disparity(31, (H, W)), disp)
-        with pytest.raises(AswError) as e:
-            ctx.download_volume(31, (D, H, W))
-        assert e.value.status == asw.ERR_NO_FRAME
-        fresh = asw.Context(0)
-        try:
-            d, v = fresh.stereoMatching(L, R, dt, enc, win, 0, D, return_cost_volume=True)
-            assert np.array_equal(d, disp) and np.array_equal(v, E)
-        finally:
-            fresh.close()
-    # other parameters travel in the encoded value; the plain entry 12 is another method
-    S, N, E2, disp2 = ac.match(L, R, 0, 7, 5, 12, win, 0, D)
-    d, v = ctx.stereoMatching(L, R, LEFT, ADC(7, 5, 12), win, 0, D, return_cost_volume=True)
-    assert np.array_equal(d, disp2) and np.array_equal(v, E2) and not np.array_equal(v, E)
-    assert not np.array_equal(ctx.stereoMatching(L, R, LEFT, 12, win, 0, D, return_cost_volume=True)[1], E)
-    # the module-level binding and its defaults (tau 20, lambdas 10 and 30, win 15, min 0, 64 candidates)
-    assert np.array_equal(asw.computeAdaptiveWeight_adcensus(L, R), ctx.stereoMatching(L, R, LEFT, enc, 15, 0, 64))
-
-
-def test_batch_equals_single_calls(ctx):
-    H, W, D, win, L, R = _case1()
-    pairs = [(L, R), cr.region_pair(H, W, D, 201, (9, 13), 0.12)[:2], cr.region_pair(H, W, D, 202, (9, 13), 0.12)[:2]]
-    for alg, par in ((ADC(), (20, 10, 30)), (ADC(3, 17, 45), (3, 17, 45))):
-        for dt in (LEFT, RIGHT):
-            outs = asw.stereoMatchingBatch([p[0] for p in pairs], [p[1] for p in pairs], dt, alg, win, 0, D, device_ids=[0, 0])
-            for (l, r), o in zip(pairs, outs):
-                assert np.array_equal(o, ctx.stereoMatching(l, r, dt, alg, win, 0, D))
-            assert np.array_equal(outs[0], ac.match(L, R, int(dt), par[0], par[1], par[2], win, 0, D)[3])
-
-
-@pytest.mark.parametrize("dt", [LEFT, RIGHT])
-def test_subpixel_flags(ctx, dt):
-    H, W, D, win, L, R = _case1()
-    for alg, tau, la, lc, minD in ((ADC(), 20, 10, 30, 0), (ADC(12, 5, 12), 12, 5, 12, 3)):
-        S, N, E, disp = ac.match(L, R, int(dt), tau, la, lc, win, minD, D)
-        for mode in MODES:
-            want, ok = sp.subpixel_vec(disp, E, minD, mode)
-            assert (want != disp).mean() >= 0.1  # on the restatement: the flag has something to move
-            d1, v1 = ctx.stereoMatching(L, R, dt, alg, win, minD, D, return_cost_volume=True, subpixel=mode)
-            assert np.array_equal(v1, E) and np.array_equal(d1, want), np.argwhere(d1 != want)[:5]
-            assert np.array_equal(ctx.stereoMatching(L, R, int(dt) | mode, alg, win, minD, D), want)  # no kept volume
-            ctx.upload_pair(32, L, R)
-            ctx.match_resident(32, dt, alg, win, minD, D, keep_volume=False, subpixel=mode)
-            assert np.array_equal(ctx.download_disparity(32, (H, W)), want)
-
-
-def test_refined_calls(ctx):
-    H, W, D, win, L, R = _case1()
-    for alg, tau, la, lc, minD, rwin, gc in ((ADC(), 20, 10, 30, 0, 15, 150.0), (ADC(10, 17, 45), 10, 17, 45, 3, 7, 60.0)):
-        dl = ac.match(L, R, 0, tau, la, lc, win, minD, D)[3]
-        dr = ac.match(L, R, 1, tau, la, lc, win, minD, D)[3]
-        want = rr.refine_vec(L, dl, dr, minD, D, 1.0, rwin, gc, 9.0)
-        got, nrej, nunf = ctx.stereoMatchingRefined(L, R, alg, win, minD, D, 1.0, rwin, gc, 9.0)
-        assert np.array_equal(got, want["out"]) and (nrej, nunf) == (want["n_rejected"], want["n_unfillable"])
-        assert nrej > 0
-        ctx.upload_pair(33, L, R)
-        assert ctx.match_refined_resident(33, alg, win, minD, D, 1.0, rwin, gc, 9.0) == (nrej, nunf)
-        assert np.array_equal(ctx.download_disparity(33, (H, W)), want["out"])
-        t = ctx.timing()
-        assert t["aggregate_launches"] == 6 and t["total_ms"] >= t["aggregate_ms"] > 0
-
-
-def test_gray_bits(ctx):
-    H, W, D, win, L, R = _case1()
     assert not np.array_equal(ac.hamming(L, R, 0, 0, D, 14), ac.hamming(L, R, 0, 0, D, 15))
     fresh = asw.Context(0)
     try:
@@ -263,65 +171,6 @@ def test_gray_bits(ctx):
         assert np.array_equal(v, E) and np.array_equal(d, disp)
     finally:
         fresh.close()
-
-
-# ---------------------------------------------------------------- statuses
-def test_statuses(ctx):
-    H, W, D = 20, 70, 12
-    L, R, _ = cr.region_pair(H, W, D, 8, (9, 13), 0.16)
-    ok = ADC(20, 10, 30)
-    ctx.upload_pair(34, L, R)
-
-    def expect(status, alg, win=15, minD=0, numD=D):
-        ctx.match_resident(34, LEFT, ok, 15, 0, D, keep_volume=True)  # a previous result
-        with pytest.raises(AswError) as e:
-            ctx.match_resident(34, LEFT, alg, win, minD, numD, keep_volume=True)
-        assert e.value.status == status, (hex(int(alg)), win, e.value.status)
-        with pytest.raises(AswError) as e:  # a failed match drops the slot's results
-            ctx.download_disparity(34, (H, W))
-        assert e.value.status == asw.ERR_NO_FRAME
-        for dt in (LEFT, RIGHT):
-            if status == asw.ERR_EVEN_WINDOW:  # the reference's silent return
-                assert ctx.stereoMatching(L, R, dt, alg, win, minD, numD) is None and asw.last_status() == status
-                assert asw.stereoMatchingBatch([L], [R], dt, alg, win, minD, numD, device_ids=[0]) is None
-            else:
-                with pytest.raises(AswError) as e:
-                    ctx.stereoMatching(L, R, dt, alg, win, minD, numD)
-                assert e.value.status == status
-                with pytest.raises(AswError) as e:
-                    asw.stereoMatchingBatch([L], [R], dt, alg, win, minD, numD, device_ids=[0])
-                assert e.value.status == status
-        with pytest.raises(AswError) as e:
-            ctx.stereoMatchingRefined(L, R, alg, win, minD, numD)
-        assert e.value.status == status
-        with pytest.raises(AswError) as e:
-            ctx.match_refined_resident(34, alg, win, minD, numD)
-        assert e.value.status == status
-
-    expect(asw.ERR_EVEN_WINDOW, ok, win=14)
-    expect(asw.ERR_BAD_ARGUMENT, ok, win=37)
-    expect(asw.ERR_BAD_ARGUMENT, ok, numD=0)
-    expect(asw.ERR_BAD_ARGUMENT, ok, minD=-1)
-    for bad in (ok & ~(0x1F << 24), ok & ~(0xFF << 16), ADC(20, 32, 30), ADC(256, 10, 30), ok - (1 << 32) + (1 << 31), ok | 0x40000000):
-        expect(asw.ERR_BAD_ARGUMENT, bad)
-    for other in ((ok & ~0xFF) | 11, (ok & ~0xFF) | 13):
-        expect(asw.ERR_UNSUPPORTED_METHOD, other)
-    assert ctx.computeAdaptiveWeight_adcensus(L, R, LEFT, 20, 10, 30, 14, 0, D) is None and asw.last_status() == asw.ERR_EVEN_WINDOW
-    two = np.zeros((H, W, 2), np.uint8)
-    with pytest.raises(AswError) as e:
-        ctx.stereoMatching(two, two, LEFT, ok, 15, 0, D)
-    assert e.value.status == asw.ERR_UNSUPPORTED_LAYOUT
-    # a short volume buffer is refused before anything is computed
-    li, la = asw._image(L)
-    ri, ra = asw._image(R)
-    disp = np.full((H, W), -7, np.float32)
-    di, _ = asw._image(disp, 5)
-    vol = np.zeros(D * H * W - 1, np.float32)
-    rc = _lib.lib().asw_stereo_match(ctx._h, C.byref(li), C.byref(ri), C.byref(di), 0, ok, 15, 0, D, vol.ctypes.data_as(C.c_void_p), vol.size)
-    assert rc == asw.ERR_BAD_ARGUMENT and (disp == -7).all()
-    # and the slot works again afterwards, in the right view too
-    ctx.match_resident(34, RIGHT, ok, 15, 0, D)
-    assert np.array_equal(ctx.download_disparity(34, (H, W)), ac.match(L, R, 1, 20, 10, 30, 15, 0, D)[3])
 
 
 # ---------------------------------------------------------------- one mid-size frame

@@ -20,8 +20,8 @@ from aswstereomatch_amd.synth import make_pair
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import refine_ref as ref  # noqa: E402
+from shim_build import build_demo  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 A = asw.StereoMatchingAlgorithms
 NAN = np.float32(np.nan)
 PAIRS = {"a": (96, 260, 24, 11, 32), "b": (60, 160, 16, 5, 16)}
@@ -369,13 +369,7 @@ def test_refined_resident_status_and_slot_state(ctx):
 # ---- the C++ shim ----
 @pytest.mark.parametrize("cv", [False, True])
 def test_shim_refine(ctx, tmp_path, cv):
-    exe = str(tmp_path / "refine_demo")
-    cmd = ["g++", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "refine_demo.cpp"),
-           "-L" + os.path.join(ROOT, "aswstereomatch_amd"), "-lasw_mi355x", "-Wl,-rpath," + os.path.join(ROOT, "aswstereomatch_amd"),
-           "-Wl,-rpath,/opt/rocm/lib", "-o", exe]
-    if cv:
-        cmd[3:3] = ["-Wextra", "-DASW_WITH_OPENCV", "-I" + os.path.join(ROOT, "tests", "cpp", "cv_stub")]
-    subprocess.check_call(cmd)
+    exe = build_demo("refine_demo.cpp", tmp_path / "refine_demo", cv)
     H, W, D, seed, block = PAIRS["b"]
     L, R, _ = make_pair(H, W, D, seed=seed, block=block)
     L.tofile(tmp_path / "l.raw")

@@ -12,8 +12,8 @@ from aswstereomatch_amd.synth import make_pair, shifted_pair
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import sgbm_ref as ref  # noqa: E402
+from shim_build import build_demo  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 A = asw.StereoMatchingAlgorithms
 LEFT, RIGHT = asw.DISPARITY_LEFT, asw.DISPARITY_RIGHT
 
@@ -238,13 +238,7 @@ def test_sgbm_kitti_shape_with_volume(ctx):
 # ---------------------------------------------------------------- the C++ shim
 @pytest.mark.parametrize("cv", [False, True])
 def test_shim_get_disparity_sgbm(ctx, tmp_path, cv):
-    exe = str(tmp_path / "sgbm_demo")
-    cmd = ["g++", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "sgbm_demo.cpp"),
-           "-L" + os.path.join(ROOT, "aswstereomatch_amd"), "-lasw_mi355x", "-Wl,-rpath," + os.path.join(ROOT, "aswstereomatch_amd"),
-           "-Wl,-rpath,/opt/rocm/lib", "-o", exe]
-    if cv:
-        cmd[3:3] = ["-Wextra", "-DASW_WITH_OPENCV", "-I" + os.path.join(ROOT, "tests", "cpp", "cv_stub")]
-    subprocess.check_call(cmd)
+    exe = build_demo("sgbm_demo.cpp", tmp_path / "sgbm_demo", cv)
     for cn in (3, 1):
         L, R = _pair(40, 120, 32, cn, seed=50 + cn)
         L.tofile(tmp_path / "l.raw")

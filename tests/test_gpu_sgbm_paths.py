@@ -15,6 +15,7 @@ from aswstereomatch_amd.synth import make_pair
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import sgbm_paths_ref as pref  # noqa: E402
 import sgbm_ref as ref  # noqa: E402
+from shim_build import build_demo  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -149,14 +150,7 @@ def test_sgbm_paths_output_layout(ctx):
 # ---------------------------------------------------------------- the C++ shim
 @pytest.mark.parametrize("cv", [False, True])
 def test_shim_get_disparity_sgbm_paths(ctx, tmp_path, cv):
-    exe = str(tmp_path / "sgbm_paths_demo")
-    cmd = ["g++", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "sgbm_paths_demo.cpp"),
-           "-L" + os.path.join(ROOT, "aswstereomatch_amd"), "-lasw_mi355x", "-Wl,-rpath," + os.path.join(ROOT, "aswstereomatch_amd"),
-           "-Wl,-rpath,/opt/rocm/lib", "-o", exe]
-    if cv:
-        cmd[3:3] = ["-Wextra", "-DASW_WITH_OPENCV", "-I" + os.path.join(ROOT, "tests", "cpp", "cv_stub")]
-    subprocess.check_call(cmd)
+    exe = build_demo("sgbm_paths_demo.cpp", tmp_path / "sgbm_paths_demo", cv)
     L, R = _pair(40, 96, 32, 3, seed=53)
     L.tofile(tmp_path / "l.raw")
     R.tofile(tmp_path / "r.raw")

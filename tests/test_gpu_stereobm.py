@@ -15,8 +15,8 @@ from aswstereomatch_amd.synth import make_pair, shifted_pair
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import cvlite  # noqa: E402
 import stereobm_ref as ref  # noqa: E402
+from shim_build import build_demo  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 A = asw.StereoMatchingAlgorithms
 
 pytestmark = pytest.mark.gpu
@@ -199,13 +199,7 @@ def test_get_disparity_bm_defaults_and_module_binding(ctx):
 
 @pytest.mark.parametrize("cv", [False, True])
 def test_shim_get_disparity_bm(ctx, tmp_path, cv):
-    exe = str(tmp_path / "bm_demo")
-    cmd = ["g++", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "bm_demo.cpp"),
-           "-L" + os.path.join(ROOT, "aswstereomatch_amd"), "-lasw_mi355x", "-Wl,-rpath," + os.path.join(ROOT, "aswstereomatch_amd"),
-           "-Wl,-rpath,/opt/rocm/lib", "-o", exe]
-    if cv:
-        cmd[3:3] = ["-Wextra", "-DASW_WITH_OPENCV", "-I" + os.path.join(ROOT, "tests", "cpp", "cv_stub")]
-    subprocess.check_call(cmd)
+    exe = build_demo("bm_demo.cpp", tmp_path / "bm_demo", cv)
     for cn in (3, 1):
         L, R = _pair(48, 160, 32, seed=90 + cn, cn=cn)
         L.tofile(tmp_path / "l.raw")

@@ -18,8 +18,8 @@ from aswstereomatch_amd.synth import make_pair
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import subpixel_ref as sp  # noqa: E402
+from shim_build import build_demo  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 A = asw.StereoMatchingAlgorithms
 LEFT, RIGHT = asw.DISPARITY_LEFT, asw.DISPARITY_RIGHT
 MODES = (asw.SUBPIXEL_PARABOLA, asw.SUBPIXEL_EQUIANGULAR)
@@ -296,13 +296,7 @@ def test_full_frame_bilateral(ctx):
 # ---- the C++ shim ----
 @pytest.mark.parametrize("cv", [False, True])
 def test_shim_subpixel(ctx, tmp_path, cv):
-    exe = str(tmp_path / "subpixel_demo")
-    cmd = ["g++", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "subpixel_demo.cpp"),
-           "-L" + os.path.join(ROOT, "aswstereomatch_amd"), "-lasw_mi355x", "-Wl,-rpath," + os.path.join(ROOT, "aswstereomatch_amd"),
-           "-Wl,-rpath,/opt/rocm/lib", "-o", exe]
-    if cv:
-        cmd[3:3] = ["-Wextra", "-DASW_WITH_OPENCV", "-I" + os.path.join(ROOT, "tests", "cpp", "cv_stub")]
-    subprocess.check_call(cmd)
+    exe = build_demo("subpixel_demo.cpp", tmp_path / "subpixel_demo", cv)
     H, W, D, seed, block = PAIRS["b"]
     L, R, _ = make_pair(H, W, D, seed=seed, block=block)
     L.tofile(tmp_path / "l.raw")

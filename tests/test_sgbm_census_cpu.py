@@ -18,6 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import matcher_cases as mc  # noqa: E402
 import sgbm_census_ref as cref  # noqa: E402
 import sgbm_paths_ref as pref  # noqa: E402
+from shim_build import C99, build_demo  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "asw_mi355x.h")
@@ -129,8 +130,7 @@ def test_header_and_inline_function(tmp_path):
                    '    asw_sgbm_paths(0, 0, 0, 0, 1, 32, 5, 8, 9, 10, 63, 11, 12, 13, 0x37, 0, 14);\n'
                    '    return 0;\n}\n')
     exe = tmp_path / "enc"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-I" + os.path.join(ROOT, "include"), str(src),
-                           "-o", str(exe)])
+    build_demo(src, exe, link=False, **C99)
     rows = [[int(v) for v in line.split()]
             for line in subprocess.run([str(exe)], capture_output=True, text=True, timeout=60, check=True).stdout.splitlines()]
     head = [1, 32, 5, 8, 9, 10]

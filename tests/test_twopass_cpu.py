@@ -15,6 +15,7 @@ from aswstereomatch_amd import _lib
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import twopass_ref as tp  # noqa: E402
+from shim_build import C99, build_demo  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "asw_mi355x.h")
@@ -132,9 +133,7 @@ def _c_values(tmp_path):
                    '           asw_alg_twopass(255, 255), asw_alg_twopass(7, 36), asw_alg_twopass(0, 20), asw_alg_twopass(30, 0),\n'
                    '           asw_alg_twopass(256, 20), asw_alg_twopass(-1, 256), ASW_ALG_TWOPASS_PARAMS);\n    return 0;\n}\n')
     exe = tmp_path / "alg"
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-I" + os.path.join(ROOT, "include"), str(src),
-                           "-L" + os.path.join(ROOT, "aswstereomatch_amd"), "-lasw_mi355x",
-                           "-Wl,-rpath," + os.path.join(ROOT, "aswstereomatch_amd"), "-Wl,-rpath,/opt/rocm/lib", "-o", str(exe)])
+    build_demo(src, exe, **C99)
     return [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, timeout=60, check=True).stdout.split()]
 
 

@@ -56,12 +56,10 @@ from aswstereomatch_amd.synth import make_pair  # noqa: E402
 from oracle import asw_oracle as O  # noqa: E402
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
-import adcensus_ref as ac  # noqa: E402
 import asw_cases  # noqa: E402
-import cross_ref as cr  # noqa: E402
 import matcher_cases as mc  # noqa: E402
 import sgbm_census_ref as scr  # noqa: E402
-import twopass_ref as tpr  # noqa: E402
+from selector_methods import METHODS as SELECTOR_METHODS  # noqa: E402
 
 A = asw.StereoMatchingAlgorithms
 
@@ -83,9 +81,12 @@ class SgbmCensusLeg:
 
 
 # checked against the CPU oracle (oracle/); the legs (mc.FAMILIES) are checked against the restatements under tests/
-LEGS = tuple(mc.FAMILIES) + ("cross", "adcensus", "sgbm_census", "twopass")
-# legs whose module has random_case / gpu_result of its own
-REF_LEGS = {"cross": cr, "adcensus": ac, "sgbm_census": SgbmCensusLeg, "twopass": tpr}
+# legs with random_case / gpu_result of their own: every descriptor of tests/selector_methods.py (cross, adcensus, twopass, and whatever
+# row is added there), with sgbm_census in the third place it has always had, so that a seed keeps drawing the cases it drew
+REF_LEGS = {m.name: m for m in SELECTOR_METHODS[:2]}
+REF_LEGS["sgbm_census"] = SgbmCensusLeg
+REF_LEGS.update((m.name, m) for m in SELECTOR_METHODS[2:])
+LEGS = tuple(mc.FAMILIES) + tuple(REF_LEGS)
 ORACLE_METHODS = ["classic", "direct8", "geodesic", "guided", "guided2", "guided3", "wmedian", "blo1", "ncc", "ncc_cost",
                   "ad_tad", "similarity", "sad", "geodist", "gfilter", "prep", "bilgrid", "lrcheck", "resident", "batch"]
 
