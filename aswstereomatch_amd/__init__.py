@@ -34,6 +34,7 @@ __all__ = [
     "cross_algorithm", "computeAdaptiveWeight_cross",
     "adcensus_algorithm", "computeCensus", "computeADCensus", "computeAdaptiveWeight_adcensus",
     "twopass_algorithm", "computeAdaptiveWeight_twopass",
+    "permeability_algorithm", "computeAdaptiveWeight_permeability",
     "AswError",
 ]
 
@@ -113,6 +114,19 @@ def twopass_algorithm(gamma_c=30, gamma_g=20):
     c = 0 if (gamma_c < 1 or gamma_c > 255) else gamma_c
     g = 0 if (gamma_g < 1 or gamma_g > 255) else gamma_g
     return _ALG_TWOPASS_PARAMS | (g << 16) | (c << 8) | int(StereoMatchingAlgorithms.ADAPTIVE_WEIGHT)
+
+
+_ALG_PERMEABILITY_PARAMS = 0x08000000  # ASW_ALG_PERMEABILITY_PARAMS
+
+
+def permeability_algorithm(sigma=8, trunc=20):
+    """asw_alg_permeability of asw_mi355x.h: the value of `algorithmType` that runs ADAPTIVE_WEIGHT_CROSS as the recursive
+    (permeability) aggregation over the whole image with the integers sigma and trunc (1..255 each) in every
+    call that takes an algorithm; an argument out of range gives a value the library refuses with ERR_BAD_ARGUMENT (that field 0)."""
+    sigma, trunc = int(sigma), int(trunc)
+    s = 0 if (sigma < 1 or sigma > 255) else sigma
+    t = 0 if (trunc < 1 or trunc > 255) else trunc
+    return _ALG_PERMEABILITY_PARAMS | (t << 16) | (s << 8) | int(StereoMatchingAlgorithms.ADAPTIVE_WEIGHT_CROSS)
 
 
 PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL = 0, 1  # StereoBM::PREFILTER_*; asw_stereo_bm serves XSOBEL
@@ -338,6 +352,18 @@ class Context:
             return self._lib.asw_stereo_match(h, l, r, d, int(dispType), alg, winSize, minDisparity, numDisparity, *args)
         return self._aggregate("asw_aggregate_twopass", _A.ADAPTIVE_WEIGHT, numDisparity, leftImg, rightImg, (), return_cost_volume,
                                fn=call)
+
+    def computeAdaptiveWeight_permeability(self, leftImg, rightImg, dispType=DISPARITY_LEFT, sigma=8, trunc=20, minDisparity=0,
+                                           numDisparity=64, return_cost_volume=False):
+        """Recursive (permeability) aggregation over the whole image (asw_aggregate_permeability; not in the
+        reference): the truncated AD cost carried along rows and columns, damped by exp(-colour step / sigma), f64; no window;
+        integers sigma and trunc 1..255; 1- or 3-channel pairs."""
+        alg = permeability_algorithm(sigma, trunc)
+
+        def call(h, l, r, d, *args):
+            return self._lib.asw_stereo_match(h, l, r, d, int(dispType), alg, 0, minDisparity, numDisparity, *args)
+        return self._aggregate("asw_aggregate_permeability", _A.ADAPTIVE_WEIGHT_CROSS, numDisparity, leftImg, rightImg, (),
+                               return_cost_volume, fn=call)
 
     # ---- semi-global block matching (DESIGN.md section 4.8) ----
     def getDisparity_SGBM(self, srcLeft, srcRight, winSize=15, minDisparity=0, numDisparity=64):
@@ -747,6 +773,7 @@ computeCensus = _bind("computeCensus")
 computeADCensus = _bind("computeADCensus")
 computeAdaptiveWeight_adcensus = _bind("computeAdaptiveWeight_adcensus")
 computeAdaptiveWeight_twopass = _bind("computeAdaptiveWeight_twopass")
+computeAdaptiveWeight_permeability = _bind("computeAdaptiveWeight_permeability")
 winnerTakeAll = _bind("winnerTakeAll")
 getDisparity_SGBM = _bind("getDisparity_SGBM")
 sgbm = _bind("sgbm")

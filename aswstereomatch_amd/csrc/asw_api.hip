@@ -40,7 +40,15 @@ int match_host(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_
 int decode_algorithm(int algorithm, int* method, MatchParams* mp)
 {
     *method = algorithm;
-    if (!(algorithm & (ASW_ALG_CROSS_PARAMS | ASW_ALG_ADCENSUS_PARAMS | ASW_ALG_TWOPASS_PARAMS))) return ASW_OK;
+    if (!(algorithm & (ASW_ALG_CROSS_PARAMS | ASW_ALG_ADCENSUS_PARAMS | ASW_ALG_TWOPASS_PARAMS | ASW_ALG_PERMEABILITY_PARAMS))) return ASW_OK;
+    if (!(algorithm & (ASW_ALG_CROSS_PARAMS | ASW_ALG_ADCENSUS_PARAMS | ASW_ALG_TWOPASS_PARAMS))) {  // asw_alg_permeability(): bit 27 alone of the four
+        if ((algorithm & 0xFF) != ASW_ALG_ADAPTIVE_WEIGHT_CROSS) return ASW_ERR_UNSUPPORTED_METHOD;
+        const int sigma = (algorithm >> 8) & 0xFF, trunc = (algorithm >> 16) & 0xFF;  // bits 24..26 and 31 stay clear
+        if (sigma == 0 || trunc == 0 || (algorithm & 0x07000000) || algorithm < 0) return ASW_ERR_BAD_ARGUMENT;
+        if (mp) { mp->permeability = 1; mp->perm_sigma = sigma; mp->perm_trunc = trunc; }
+        *method = ASW_ALG_ADAPTIVE_WEIGHT_CROSS;
+        return ASW_OK;
+    }
     if (!(algorithm & (ASW_ALG_CROSS_PARAMS | ASW_ALG_ADCENSUS_PARAMS))) {  // asw_alg_twopass(): bit 28 is adcensus's lambda_ad otherwise
         if ((algorithm & 0xFF) != ASW_ALG_ADAPTIVE_WEIGHT) return ASW_ERR_UNSUPPORTED_METHOD;
         const int gamma_c = (algorithm >> 8) & 0xFF, gamma_g = (algorithm >> 16) & 0xFF;  // bits 24..27 and 31 stay clear

@@ -85,6 +85,7 @@ void AswTuning::read_environment()
     guided_fused = num("ASW_GUIDED_FUSED", guided_fused);
     q6_pair = num("ASW_Q6_PAIR", q6_pair);
     ab6_pair = num("ASW_AB6_PAIR", ab6_pair);
+    perm_chunk = num(ASW_PERM_CHUNK_NAME, perm_chunk);
 }
 
 extern "C" int asw_create(int device_id, asw_ctx** out)
@@ -134,6 +135,7 @@ extern "C" void asw_destroy(asw_ctx* ctx)
     ctx->refine.tc.release();
     ctx->refine.ts.release();
     ctx->twopass.t.release();
+    ctx->perm.t.release();
     ctx->wm_lut2.release();
     ctx->wm_wd.release();
     for (int i = 0; i < 4; i++)

@@ -41,6 +41,8 @@ struct MatchParams {
     int cross_tau = 20, cross_trunc = 20;       // ASW_ALG_ADAPTIVE_WEIGHT_CROSS; an encoded selector value replaces them
     int cross_cost = 0;                         // the cost entry 12 aggregates: 0 = truncated AD, 1 = AD-Census (asw_alg_adcensus())
     int lambda_ad = 10, lambda_census = 30;     // AD-Census: the two table constants
+    int permeability = 0;                       // entry 12 as the recursive (permeability) aggregation (asw_alg_permeability())
+    int perm_sigma = 8, perm_trunc = 20;        // its two parameters, 1..255 each
 };
 inline MatchParams match_params(int disparity_type, int win, int minD, int numD)
 {
@@ -66,9 +68,9 @@ const MethodInfo* method_info(int method);  // the row of a plain (decoded) sele
 
 // The selector's `algorithm` as a caller passes it -> the plain enum value in *method and, for an asw_alg_cross() or
 // asw_alg_adcensus() value, its parameters in mp's cross_* / lambda_* fields, for an asw_alg_twopass() value mp's twopass flag and
-// gammas (left alone otherwise; mp may be null).
+// gammas, for an asw_alg_permeability() value mp's permeability flag, sigma and trunc (left alone otherwise; mp may be null).
 // ASW_ERR_UNSUPPORTED_METHOD / ASW_ERR_BAD_ARGUMENT for the encodings asw_mi355x.h refuses; a value with none of
-// ASW_ALG_CROSS_PARAMS, ASW_ALG_ADCENSUS_PARAMS and ASW_ALG_TWOPASS_PARAMS passes through as it is.
+// ASW_ALG_CROSS_PARAMS, ASW_ALG_ADCENSUS_PARAMS, ASW_ALG_TWOPASS_PARAMS and ASW_ALG_PERMEABILITY_PARAMS passes through as it is.
 int decode_algorithm(int algorithm, int* method, MatchParams* mp);
 // AD-Census cost of a device pair into cost u8 [numD][H][W]: gray pair, two census transforms, then the
 // Hamming distance alone (lambda_ad = 0) or TA[AD] + TC[Hamming] with the tables of the two lambdas (each 1..255)

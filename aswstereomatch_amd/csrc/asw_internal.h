@@ -75,8 +75,11 @@ struct AswTuning {
     int q_wg_strips = 1;         // ASW_Q_WG_STRIPS: workgroup of the q pass = 4 neighbouring strips (1) / 4 slices of a strip (0)
     int guide_share = 1;         // ASW_GUIDE_SHARE: 6-channel guide [fixed image, other image shifted by d] (GuidedF, GuidedF_3 LEFT / RIGHT):
                                  // 1 = statistics shared across slices (k_guided.hip: StatsSplit), 0 = plain statistics of every slice
+    int perm_chunk = 0;          // ASW_PERM_CHUNK: candidates per chunk of the permeability aggregation (tests: odd chunkings; the result does not depend on it)
     void read_environment();
 };
+// the name of AswTuning::perm_chunk's switch
+constexpr char ASW_PERM_CHUNK_NAME[] = "ASW_PERM_CHUNK";
 
 struct RefineTables {  // cached per (win, gamma_c, gamma_s, channels): integer weights of the refinement's median (k_refine.hip)
     int win = 0, channels = 0;
@@ -89,6 +92,11 @@ struct RefineTables {  // cached per (win, gamma_c, gamma_s, channels): integer 
 struct TwoPassTable {  // cached per (win, gamma_c, gamma_g): the weight table of the two-pass method (k_twopass.hip)
     int win = 0, gamma_c = 0, gamma_g = 0;
     DevBuf t;  // float [win / 2 + 1][256]: (float)exp(-(dc / gamma_c + r / gamma_g))
+};
+
+struct PermTable {  // cached per sigma: the permeability table of k_permeability.hip
+    int sigma = 0;
+    DevBuf t;  // double [256]: (double)(float)exp(-(double)k / sigma)
 };
 
 struct asw_ctx {
@@ -104,6 +112,7 @@ struct asw_ctx {
     BilateralTables bil;
     RefineTables refine;
     TwoPassTable twopass;
+    PermTable perm;
     int census_lambda_ad = 0, census_lambda_census = 0;  // what buf("census_tables") holds (asw_methods.hip: ensure_census_tables)
     // weighted-median tables: exp() LUT of the colour weight per rateR, space kernel per (win, rateS)
     DevBuf wm_lut2, wm_wd;
@@ -190,6 +199,31 @@ int launch_twopass(hipStream_t s, const TwoPassLaunch& a);
 // largest window launch_twopass serves: the last odd one whose LDS layout (sums of a chunk, table, two gray tiles) fits a
 // workgroup's 160 KB (95: 162976 bytes).  The host entry refuses a larger window before it builds a table
 int twopass_max_window();
+
+// ---- recursive (permeability) aggregation (k_permeability.hip), DESIGN.md section 4.17 ----
+// The kernels scan in segments of 16 positions: perm_segments(n) segments along an axis of n positions, and the permeability planes
+// carry perm_padded(n) entries per row (zeros in front of position 1 and behind the last one).  No limit of their own on rows or
+// columns: rows * cols < 2^31 is all they ask.
+int perm_segments(int n);
+int perm_padded(int n);
+// ph [H][perm_padded(W)], pvT [W][perm_padded(H)] (transposed) from the view image (C = 1 or 3) and the table P[256]; two launches
+int launch_perm_weights(hipStream_t s, const uint8_t* img, int H, int W, int C, const double* P, double* ph, double* pvT);
+struct PermLaunch {
+    const uint8_t* cost;  // u8 cost planes of the chunk, [nc][H][W]
+    int H, W, nc, trunc;  // nc candidates in the chunk; e = min(trunc, cost)
+    int cbeg, minD, first;  // vertical: the chunk's first plane in the volume, the map's offset, 1 = the first chunk of the frame
+    const double* ph;
+    const double* pvT;
+    double* ck;           // checkpoints: nc * max(H * perm_segments(W), W * perm_segments(H)) doubles, shared by the two passes
+    double* hs;           // horizontal sums [H][W][nc]: written by the horizontal, read by the vertical pass
+    const double* N;      // vertical: the frame's N, transposed [W][perm_padded(H)]; null: this launch computes it (nc = 1) into Nout
+    double* Nout;
+    float* vol;           // optional [..][H][W]
+    double* bestE;        // [H][W] running minimum across chunks
+    float* disp;          // [H][W]
+};
+int launch_perm_scan_h(hipStream_t s, const PermLaunch& a);
+int launch_perm_scan_v(hipStream_t s, const PermLaunch& a);
 
 // ---- cost kernels (k_cost.hip) ----
 int launch_scharr_x(hipStream_t s, const uint8_t* img, int H, int W, int pad, short* grad /* [H][W+pad][3] */);

@@ -877,8 +877,101 @@ int build_census_cost(asw_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int H,
 // ------------------------------------------------------------------------------------------
 // cross-based support regions (Zhang, Lu, Lafruit 2009): DESIGN.md section 4.12; not in the reference
 // ------------------------------------------------------------------------------------------
+// ------------------------------------------------------------------------------------------
+// recursive (permeability) aggregation over the whole image (Cigla & Alatan 2013): entry 12 with an asw_alg_permeability() value;
+// DESIGN.md section 4.17; not in the reference
+// ------------------------------------------------------------------------------------------
+static int ensure_perm_table(asw_ctx* ctx, int sigma)
+{
+    PermTable& t = ctx->perm;
+    if (t.sigma == sigma && t.t.p) return ASW_OK;
+    t.sigma = 0;
+    double tab[256];
+    for (int k = 0; k < 256; k++) tab[k] = (double)(float)exp(-(double)k / sigma);  // rounded to f32 here: the kernels see doubles only
+    ASW_TRY(t.t.ensure(sizeof(tab)));
+    ASW_HIP_TRY(hipMemcpyAsync(t.t.p, tab, sizeof(tab), hipMemcpyHostToDevice, ctx->stream));
+    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));  // the host array dies at return
+    t.sigma = sigma;
+    return ASW_OK;
+}
+
+// win is not read: the support is the whole image
+static int run_permeability(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_volume)
+{
+    if (f->channels != 3 && f->channels != 1) return ASW_ERR_UNSUPPORTED_LAYOUT;  // what asw_cost_ad takes
+    ASW_TRY(check_direction(mp.disparity_type));
+    if (mp.perm_sigma < 1 || mp.perm_sigma > 255 || mp.perm_trunc < 1 || mp.perm_trunc > 255) return ASW_ERR_BAD_ARGUMENT;
+    const int H = f->rows, W = f->cols, n = mp.numD;
+    if ((size_t)H * W >= ((size_t)1 << 31)) return ASW_ERR_BAD_ARGUMENT;  // as entry 12; the scan kernels ask nothing else of a frame
+    const size_t plane = (size_t)H * W;
+    const size_t ck_per = std::max((size_t)H * perm_segments(W), (size_t)W * perm_segments(H));  // checkpoints of one candidate
+    const size_t ph_doubles = (size_t)H * perm_padded(W), pv_doubles = (size_t)W * perm_padded(H);
+    // candidates per chunk: horizontal sums + checkpoints of a chunk and the per-frame planes stay within 2 GiB; whole wavefronts of
+    // 64 candidates where the range does not fit one chunk.  ASW_PERM_CHUNK forces another size (tests): the result is the same
+    // per frame: best E, N's own horizontal sums and checkpoints, ph, pv and N (transposed, padded like pv), the plane of ones
+    const size_t fixed = (2 * plane + ck_per + ph_doubles + 2 * pv_doubles) * sizeof(double) + plane, per_cand = (plane + ck_per) * sizeof(double);
+    const size_t budget = (size_t)2 << 30;
+    size_t fit = budget > fixed + per_cand ? (budget - fixed) / per_cand : 1;
+    int chunk = (int)std::min<size_t>(fit, (size_t)std::min(n, 4096));
+    if (chunk < n && chunk >= 64) chunk = chunk / 64 * 64;
+    if (ctx->tune.perm_chunk > 0) chunk = std::max(1, std::min(std::min(n, 4096), ctx->tune.perm_chunk));
+    const int chunks = (n + chunk - 1) / chunk;
+    ASW_TRY(ensure_perm_table(ctx, mp.perm_sigma));
+    DevBuf& raw = ctx->buf("cross_cost");  // the u8 AD volume, as entry 12 keeps it
+    DevBuf& ones = ctx->buf("perm_ones");
+    DevBuf& ph = ctx->buf("perm_ph");
+    DevBuf& pv = ctx->buf("perm_pv");
+    DevBuf& ck = ctx->buf("perm_ck");
+    DevBuf& hs = ctx->buf("perm_hs");
+    DevBuf& nrm = ctx->buf("perm_n");
+    DevBuf& nck = ctx->buf("perm_n_ck");  // N's scans run beside the first chunk's horizontal pass: scratch of their own
+    DevBuf& nhs = ctx->buf("perm_n_hs");
+    DevBuf& best = ctx->buf("perm_best");
+    ASW_TRY(raw.ensure(plane * n));
+    ASW_TRY(ones.ensure(plane));
+    ASW_TRY(ph.ensure(ph_doubles * sizeof(double)));
+    ASW_TRY(pv.ensure(pv_doubles * sizeof(double)));
+    ASW_TRY(ck.ensure(ck_per * chunk * sizeof(double)));
+    ASW_TRY(hs.ensure(plane * chunk * sizeof(double)));
+    ASW_TRY(nrm.ensure(pv_doubles * sizeof(double)));
+    ASW_TRY(nck.ensure(ck_per * sizeof(double)));
+    ASW_TRY(nhs.ensure(plane * sizeof(double)));
+    ASW_TRY(best.ensure(plane * sizeof(double)));
+    ASW_TRY(ensure_outputs(f, n, keep_volume));
+    const uint8_t* dL = f->L.as<uint8_t>();
+    const uint8_t* dR = f->R.as<uint8_t>();
+    ASW_TRY(launch_cost_ad(ctx->stream, dL, dR, H, W, f->channels, mp.disparity_type, mp.minD, n, 0, 0, raw.as<uint8_t>()));
+    ASW_HIP_TRY(hipMemsetAsync(ones.p, 1, plane, ctx->stream));
+    ASW_TRY(agg_begin(ctx));
+    ASW_TRY(launch_perm_weights(ctx->stream, mp.disparity_type == ASW_DISPARITY_RIGHT ? dR : dL, H, W, f->channels, ctx->perm.t.as<double>(),
+                                ph.as<double>(), pv.as<double>()));
+    PermLaunch a;
+    a.H = H; a.W = W; a.trunc = mp.perm_trunc; a.minD = mp.minD;
+    a.ph = ph.as<double>(); a.pvT = pv.as<double>(); a.ck = ck.as<double>(); a.hs = hs.as<double>();
+    a.bestE = best.as<double>(); a.disp = f->disp.as<float>();
+    // N: the two passes over a plane of ones, through the kernels every candidate goes through.  One lane of a wavefront works and
+    // the scans are as long as any: on a side stream they run beside the first chunk's horizontal pass, which does not need N
+    PermLaunch nl = a;
+    nl.cost = ones.as<uint8_t>(); nl.nc = 1; nl.cbeg = 0; nl.first = 1; nl.ck = nck.as<double>(); nl.hs = nhs.as<double>();
+    nl.N = nullptr; nl.Nout = nrm.as<double>(); nl.vol = nullptr;
+    ASW_HIP_TRY(hipEventRecord(ctx->aux_ev[0], ctx->stream));  // fork: behind the permeability planes
+    ASW_HIP_TRY(hipStreamWaitEvent(ctx->aux[0], ctx->aux_ev[0], 0));
+    ASW_TRY(launch_perm_scan_h(ctx->aux[0], nl));
+    ASW_TRY(launch_perm_scan_v(ctx->aux[0], nl));
+    ASW_HIP_TRY(hipEventRecord(ctx->aux_ev[1], ctx->aux[0]));
+    a.N = nrm.as<double>(); a.Nout = nullptr; a.vol = keep_volume ? f->vol.as<float>() : nullptr;
+    for (int c0 = 0; c0 < n; c0 += chunk) {  // ascending: the vertical pass merges a chunk's winners into the running minimum
+        a.cost = raw.as<uint8_t>() + (size_t)c0 * plane; a.nc = std::min(chunk, n - c0); a.cbeg = c0; a.first = c0 == 0;
+        ASW_TRY(launch_perm_scan_h(ctx->stream, a));
+        if (c0 == 0) ASW_HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->aux_ev[1], 0));  // join: the vertical pass divides by N
+        ASW_TRY(launch_perm_scan_v(ctx->stream, a));
+    }
+    return agg_end(ctx, 4 + 2 * chunks);  // two permeability planes, N's two passes, two passes per chunk
+}
+
 static int run_cross(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_volume)
 {
+    if (mp.permeability) return run_permeability(ctx, f, mp, keep_volume);  // no window: before the window checks
     if (mp.win % 2 == 0) return ASW_ERR_EVEN_WINDOW;
     if (mp.win < 1 || mp.win > 35) return ASW_ERR_BAD_ARGUMENT;
     if (f->channels != 3 && f->channels != 1) return ASW_ERR_UNSUPPORTED_LAYOUT;  // what asw_cost_ad takes

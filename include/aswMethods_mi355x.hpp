@@ -440,6 +440,16 @@ inline AswMat computeAdaptiveWeight_twopass(AswMat leftImg, AswMat rightImg, int
     }, "computeAdaptiveWeight_twopass");
 }
 
+// Not in the reference: recursive (permeability) aggregation over the whole image (asw_aggregate_permeability) --
+// no window, integers sigma and trunc 1..255 -> the f32 map
+inline AswMat computeAdaptiveWeight_permeability(AswMat leftImg, AswMat rightImg, DisparityType dispType = DISPARITY_LEFT, int sigma = 8,
+                                                 int trunc = 20, int minDisparity = 0, int numDisparity = 64)
+{
+    return asw::detail::aggregate(leftImg, rightImg, [&](asw_ctx* c, asw_image* l, asw_image* r, asw_image* o) {
+        return asw_aggregate_permeability(c, l, r, o, (int)dispType, sigma, trunc, minDisparity, numDisparity, nullptr, 0);
+    }, "computeAdaptiveWeight_permeability");
+}
+
 // Not in the reference: the cross-check that consumes a DISPARITY_LEFT and a DISPARITY_RIGHT map (asw_lr_check)
 inline AswMat leftRightCheck(AswMat dispLeft, AswMat dispRight, float maxDiff = 1.0f, float invalidValue = -1.0f, int* nInvalid = nullptr)
 {

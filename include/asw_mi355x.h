@@ -157,6 +157,41 @@ static inline int asw_alg_twopass(int gamma_c, int gamma_g)
     return ASW_ALG_TWOPASS_PARAMS | (g << 16) | (c << 8) | ASW_ALG_ADAPTIVE_WEIGHT;
 }
 
+/* ---- recursive (information-permeability) aggregation over the whole image (Cigla & Alatan 2013; not in the reference; DESIGN.md
+ * section 4.17) ----
+ * Selector entry 12 with the cross-shaped region replaced by a support that is the whole image: a cost travels from pixel to
+ * neighbouring pixel, damped by exp(-colour step / sigma); two horizontal and two vertical scans, about four multiply-adds per
+ * (pixel, candidate) whatever the object size.  Every call that takes `algorithm` serves it; both directions, 1- or 3-channel 8U
+ * pairs, the sub-pixel flags as for the other methods; planes d = min_d .. min_d + num_d - 1 (asw_volume_planes = num_d, as for 12).
+ * I = the view image (left for DISPARITY_LEFT, right for DISPARITY_RIGHT):
+ *   e(x,y,d) = min(trunc, AD(x,y,d)), AD the u8 value asw_cost_ad returns for the same pair, direction and plane (borders included);
+ *   P[k] = (double)(float)exp(-(double)k / sigma), k = 0..255 (libm, built on the host, handed to the device as doubles); entries with
+ *     k > 103.28 sigma are exactly 0 and act as hard barriers;
+ *   ph(x,y) = P[max_c |I_c(x,y) - I_c(x-1,y)|] for x >= 1, pv(x,y) = P[max_c |I_c(x,y) - I_c(x,y-1)|] for y >= 1;
+ *   horizontal pass, per row and plane, f64, every product rounded before it is added (no contraction):
+ *     LR(0) = e(0), LR(x) = e(x) + ph(x) LR(x-1), ascending x;  RL(W-1) = e(W-1), RL(x) = e(x) + ph(x+1) RL(x+1), descending x;
+ *     Hs(x) = (LR(x) + RL(x)) - e(x), in that order;
+ *   vertical pass: the same three statements down and up every column, with Hs in place of e and pv in place of ph -> S(x,y,d);
+ *   N(x,y) = the same two passes over e == 1 (independent of d, >= 1: no plane holds a NaN); E = S / N (f64, correctly rounded);
+ *   volume plane (float)E; map: min_d + index of the strict-'<' running minimum of the f64 E over ascending d.
+ * The scans are sequential by definition: a parallel-prefix form rounds differently and is not this method.
+ * asw_alg_permeability(sigma, trunc) forms the value of `algorithm`: bits 0-7 = 12, bits 8-15 = sigma (1..255), bits 16-23 = trunc
+ * (1..255), bit 27 set (ASW_ALG_PERMEABILITY_PARAMS), bits 24-26 and 28-31 clear; an argument out of range leaves 0 in its field.  Bit
+ * 27 is read only when bits 28, 29 and 30 are clear (it belongs to lambda_ad under bit 29 and is a refused bit under bits 28 and 30);
+ * then a low byte other than 12 gives ASW_ERR_UNSUPPORTED_METHOD and a zero field or any of bits 24-26 / 31 ASW_ERR_BAD_ARGUMENT
+ * (asw_volume_planes: 0).  The method has no window: win_size is not read, every value of it -- even, zero or negative -- gives the
+ * same result and status.  rows * cols < 2^31 and the column limits of asw_cost_ad, as for 12; the scan kernels have no limit of their
+ * own on rows or columns.  Candidates go through the device in chunks that keep the method's scratch within 2 GiB beside the u8 cost
+ * volume; the result does not depend on the chunking.  asw_get_timing: the AD cost build counts in cost_ms; aggregate_ms /
+ * aggregate_launches cover the two permeability planes, N's two scans and two scans per chunk: aggregate_launches = 4 + 2 * chunks.
+ * asw_aggregate_permeability (inline, after asw_stereo_match below) is the per-method form; neither is a symbol of the library. */
+enum { ASW_ALG_PERMEABILITY_PARAMS = 0x08000000 };
+static inline int asw_alg_permeability(int sigma, int trunc)
+{
+    const int s = (sigma < 1 || sigma > 255) ? 0 : sigma, t = (trunc < 1 || trunc > 255) ? 0 : trunc;
+    return ASW_ALG_PERMEABILITY_PARAMS | (t << 16) | (s << 8) | ASW_ALG_ADAPTIVE_WEIGHT_CROSS;
+}
+
 /* cv::Mat depth codes */
 enum { ASW_8U = 0, ASW_16S = 3, ASW_32F = 5 };
 
@@ -234,6 +269,16 @@ static inline int asw_aggregate_twopass(asw_ctx* ctx, const asw_image* left, con
 {
     return asw_stereo_match(ctx, left, right, disp, disparity_type, asw_alg_twopass(gamma_c, gamma_g), win_size, min_disparity,
                             num_disparity, cost_volume_out, cost_volume_floats);
+}
+
+/* Permeability aggregation with explicit parameters (above): asw_stereo_match with algorithm = asw_alg_permeability(sigma, trunc); the
+ * method has no window, win_size is passed as 0. */
+static inline int asw_aggregate_permeability(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp,
+                                             int disparity_type, int sigma, int trunc, int min_disparity, int num_disparity,
+                                             float* cost_volume_out, size_t cost_volume_floats)
+{
+    return asw_stereo_match(ctx, left, right, disp, disparity_type, asw_alg_permeability(sigma, trunc), 0, min_disparity, num_disparity,
+                            cost_volume_out, cost_volume_floats);
 }
 
 /* Planes of the cost volume `algorithm` produces for num_disparity candidates (what cost_volume_out must hold);

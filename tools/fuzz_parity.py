@@ -42,6 +42,12 @@ volume and map, with and without the kept volume; its cases come from twopass_re
 twopass_ref.build_case rebuilds.
 
     python tools/fuzz_parity.py --seconds 120 --seed 1 --only twopass
+
+The leg permeability is the recursive (permeability) aggregation (asw_alg_permeability over entry 12) against
+tests/permeability_ref.py, volume and map, with and without the kept volume; its cases come from permeability_ref.random_case and a
+mismatch prints the tag permeability_ref.build_case rebuilds.
+
+    python tools/fuzz_parity.py --seconds 120 --seed 1 --only permeability
 """
 import argparse
 import os
@@ -58,6 +64,7 @@ from oracle import asw_oracle as O  # noqa: E402
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import asw_cases  # noqa: E402
 import matcher_cases as mc  # noqa: E402
+import permeability_ref  # noqa: E402
 import sgbm_census_ref as scr  # noqa: E402
 from selector_methods import METHODS as SELECTOR_METHODS  # noqa: E402
 
@@ -86,6 +93,7 @@ class SgbmCensusLeg:
 REF_LEGS = {m.name: m for m in SELECTOR_METHODS[:2]}
 REF_LEGS["sgbm_census"] = SgbmCensusLeg
 REF_LEGS.update((m.name, m) for m in SELECTOR_METHODS[2:])
+REF_LEGS["permeability"] = permeability_ref  # last: the legs before it keep the cases a seed drew for them
 LEGS = tuple(mc.FAMILIES) + tuple(REF_LEGS)
 ORACLE_METHODS = ["classic", "direct8", "geodesic", "guided", "guided2", "guided3", "wmedian", "blo1", "ncc", "ncc_cost",
                   "ad_tad", "similarity", "sad", "geodist", "gfilter", "prep", "bilgrid", "lrcheck", "resident", "batch"]
