@@ -35,6 +35,7 @@ __all__ = [
     "adcensus_algorithm", "computeCensus", "computeADCensus", "computeAdaptiveWeight_adcensus",
     "twopass_algorithm", "computeAdaptiveWeight_twopass",
     "permeability_algorithm", "computeAdaptiveWeight_permeability",
+    "CROSS_SCALE", "cross_scale",
     "AswError",
 ]
 
@@ -129,6 +130,19 @@ def permeability_algorithm(sigma=8, trunc=20):
     return _ALG_PERMEABILITY_PARAMS | (t << 16) | (s << 8) | int(StereoMatchingAlgorithms.ADAPTIVE_WEIGHT_CROSS)
 
 
+CROSS_SCALE = 0x1000  # ASW_DISPARITY_CROSS_SCALE
+
+
+def cross_scale(scales=3, lambda_q=19):
+    """asw_disparity_cross_scale of asw_mi355x.h: the value to OR into a disparity type (or to pass as cross_scale= where that keyword
+    exists) that runs the method on `scales` (2..5) levels of a 2x2-mean pyramid and takes the winner of the regularised finest-scale
+    volume, lambda = lambda_q / 64 with lambda_q in 1..255; an argument out of range gives a value the
+    library refuses with ERR_BAD_ARGUMENT (scales field 0)."""
+    scales, lambda_q = int(scales), int(lambda_q)
+    bad = scales < 2 or scales > 5 or lambda_q < 1 or lambda_q > 255
+    return CROSS_SCALE | ((0 if bad else scales) << 13) | ((lambda_q & 0xFF) << 16)
+
+
 PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL = 0, 1  # StereoBM::PREFILTER_*; asw_stereo_bm serves XSOBEL
 REFINE_GAMMA_C, REFINE_GAMMA_S = 60.0, 9.0  # default colour / distance gammas of the refinement's weighted median (asw_mi355x.h)
 # statuses for which the reference returns silently / an empty Mat
@@ -216,8 +230,9 @@ class Context:
 
     # ---- whole-method entry point (M.h:91-92) ----
     def stereoMatching(self, srcLeft, srcRight, disparityType, algorithmType, winSize=15, minDisparity=0,
-                       numDisparity=64, return_cost_volume=False, subpixel=None):
-        """subpixel: None, SUBPIXEL_PARABOLA or SUBPIXEL_EQUIANGULAR, OR-ed into disparityType."""
+                       numDisparity=64, return_cost_volume=False, subpixel=None, cross_scale=None):
+        """subpixel: None, SUBPIXEL_PARABOLA or SUBPIXEL_EQUIANGULAR; cross_scale: None or a cross_scale() value; both are OR-ed
+        into disparityType."""
         li, la = _image(srcLeft)
         ri, ra = _image(srcRight)
         disp = np.zeros((la.shape[0], la.shape[1]), np.float32)
@@ -227,7 +242,7 @@ class Context:
         if return_cost_volume:
             vol = np.zeros((self._candidates(int(algorithmType), numDisparity), la.shape[0], la.shape[1]), np.float32)
             pv = vol.ctypes.data_as(C.c_void_p)
-        rc = self._lib.asw_stereo_match(self._h, C.byref(li), C.byref(ri), C.byref(di), int(disparityType) | int(subpixel or 0),
+        rc = self._lib.asw_stereo_match(self._h, C.byref(li), C.byref(ri), C.byref(di), int(disparityType) | int(subpixel or 0) | int(cross_scale or 0),
                                         int(algorithmType), winSize, minDisparity, numDisparity, pv, 0 if vol is None else vol.size)
         if not self._finish(rc, "asw_stereo_match"):
             return (None, None) if return_cost_volume else None
@@ -626,8 +641,8 @@ class Context:
         self._strict(self._lib.asw_upload_pair(self._h, slot, C.byref(li), C.byref(ri)), "asw_upload_pair")
 
     def match_resident(self, slot, disparityType, algorithmType, winSize, minDisparity, numDisparity, keep_volume=False,
-                       subpixel=None):
-        rc = self._lib.asw_match_resident(self._h, slot, int(disparityType) | int(subpixel or 0), int(algorithmType), winSize,
+                       subpixel=None, cross_scale=None):
+        rc = self._lib.asw_match_resident(self._h, slot, int(disparityType) | int(subpixel or 0) | int(cross_scale or 0), int(algorithmType), winSize,
                                           minDisparity, numDisparity, 1 if keep_volume else 0)
         self._strict(rc, "asw_match_resident")
 
@@ -689,9 +704,10 @@ class Context:
 
 
 def stereoMatchingBatch(lefts, rights, disparityType, algorithmType, winSize=15, minDisparity=0, numDisparity=64,
-                        device_ids=None, out=None, subpixel=None):
+                        device_ids=None, out=None, subpixel=None, cross_scale=None):
     """asw_stereo_match_batch: frame i -> device device_ids[i % len(device_ids)], one host thread per device.
-    subpixel: None, SUBPIXEL_PARABOLA or SUBPIXEL_EQUIANGULAR, OR-ed into disparityType.
+    subpixel: None, SUBPIXEL_PARABOLA or SUBPIXEL_EQUIANGULAR; cross_scale: None or a cross_scale() value; both are OR-ed into
+    disparityType.
 
     out: optional list of C-contiguous float32 (H, W) arrays to receive the disparities (a frame loop that reuses its
     output buffers avoids first-touch page faults on 8 MB per 1080p frame)."""
@@ -718,7 +734,7 @@ def stereoMatchingBatch(lefts, rights, disparityType, algorithmType, winSize=15,
         keep.append((la, ra))
         outs.append(o)
     devs = (C.c_int * len(device_ids))(*device_ids)
-    rc = lib.asw_stereo_match_batch(n, L, R, D, int(disparityType) | int(subpixel or 0), int(algorithmType), winSize, minDisparity, numDisparity,
+    rc = lib.asw_stereo_match_batch(n, L, R, D, int(disparityType) | int(subpixel or 0) | int(cross_scale or 0), int(algorithmType), winSize, minDisparity, numDisparity,
                                     len(device_ids), devs)
     _state.status = rc
     if rc in _SILENT:

@@ -128,6 +128,9 @@ extern "C" void asw_destroy(asw_ctx* ctx)
         f.L.release(); f.R.release(); f.disp.release(); f.vol.release();
     }
     ctx->host_frame.L.release(); ctx->host_frame.R.release(); ctx->host_frame.disp.release(); ctx->host_frame.vol.release();
+    for (auto& f : ctx->coarse) {
+        f.L.release(); f.R.release(); f.disp.release(); f.vol.release();
+    }
     for (auto& kv : ctx->scratch) kv.second.release();
     ctx->bil.taps.release();
     ctx->bil.lut.release();

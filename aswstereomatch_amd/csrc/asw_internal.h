@@ -99,6 +99,8 @@ struct PermTable {  // cached per sigma: the permeability table of k_permeabilit
     DevBuf t;  // double [256]: (double)(float)exp(-(double)k / sigma)
 };
 
+constexpr int CROSS_SCALE_MAX = 5;  // most pyramid levels of a cross-scale call, the finest included
+
 struct asw_ctx {
     int device = 0;
     AswTuning tune;
@@ -107,6 +109,7 @@ struct asw_ctx {
     hipStream_t stream = nullptr;
     std::vector<Frame> frames;  // resident slots of asw_upload_pair / asw_match_resident (caller-numbered)
     Frame host_frame;           // private frame of the host-buffer entry points (asw_stereo_match, asw_aggregate_*): never a slot
+    Frame coarse[CROSS_SCALE_MAX - 1];  // private pyramid levels 1.. of a cross-scale call (pair and volume of each level): never slots
     std::vector<unsigned char> host_pack;  // dense staging for host images whose rows carry padding (asw_context.hip: copy_rows)
     std::map<std::string, DevBuf> scratch;  // named grow-only scratch buffers
     BilateralTables bil;
@@ -141,6 +144,21 @@ int launch_wta(hipStream_t s, const float* vol, int n, int H, int W, int minD, f
 // mode: ASW_DISPARITY_SUBPIXEL_PARABOLA | ASW_DISPARITY_SUBPIXEL_EQUIANGULAR; vol [n][H][W] (plane k <-> disparity minD + k);
 // disp [H][W]: the integer winner-take-all map, refined in place
 int launch_subpixel(hipStream_t s, int mode, const float* vol, int n, int H, int W, int minD, float* disp);
+
+// ---- cross-scale aggregation (k_cross_scale.hip), DESIGN.md section 4.18 ----
+// one pyramid step: dst [ceil(H/2)][ceil(W/2)][C] from src [H][W][C], the rounded 2x2 mean with the last row / column repeated
+int launch_pyramid_down(hipStream_t s, const uint8_t* src, int H, int W, int C, uint8_t* dst);
+// w[0..S-1]: the first column of the inverse of the paper's tridiagonal matrix for lambda = q / 64, solved in f64, rounded to f32
+void cross_scale_weights(int S, int q, float* w);
+struct CrossScaleLaunch {
+    float* vol;   // V_0 [n][H][W]: read, and overwritten with the combined volume when `store`
+    float* disp;  // [H][W]
+    int H, W, n, minD, S, store;
+    float w[CROSS_SCALE_MAX];
+    const float* cv[CROSS_SCALE_MAX - 1];  // V_s of level s = index + 1: [planes_s][Hs][Ws]
+    int cH[CROSS_SCALE_MAX - 1], cW[CROSS_SCALE_MAX - 1], cminD[CROSS_SCALE_MAX - 1];
+};
+int launch_cross_scale_combine(hipStream_t s, const CrossScaleLaunch& a);
 
 struct BilateralLaunch {
     const uint8_t* gL;

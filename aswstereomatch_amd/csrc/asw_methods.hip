@@ -1048,6 +1048,64 @@ static int decode_subpixel(const MethodInfo* m, MatchParams& mp)
     return ASW_OK;
 }
 
+// Cross-scale fields of a caller's disparity_type -> mp.cross_scales / mp.cross_lambda_q, mp.disparity_type
+// without them (decode_subpixel sees the rest).  A value with bit 12 clear passes through as it is, whatever its other bits hold.
+static int decode_cross_scale(const MethodInfo* m, MatchParams& mp)
+{
+    const int sub = ASW_DISPARITY_SUBPIXEL_PARABOLA | ASW_DISPARITY_SUBPIXEL_EQUIANGULAR, fields = 0x00FFF000;
+    mp.cross_scales = mp.cross_lambda_q = 0;
+    if ((m && m->ignores_disparity_type) || !(mp.disparity_type & ASW_DISPARITY_CROSS_SCALE)) return ASW_OK;
+    const int S = (mp.disparity_type >> 13) & 7, q = (mp.disparity_type >> 16) & 0xFF;
+    if (mp.disparity_type & ~(fields | sub | ASW_DISPARITY_RIGHT)) return ASW_ERR_BAD_ARGUMENT;
+    if (S < 2 || S > CROSS_SCALE_MAX || q == 0 || (mp.disparity_type & sub) == sub) return ASW_ERR_BAD_ARGUMENT;
+    if (m && m->no_subpixel) return ASW_ERR_UNSUPPORTED_METHOD;  // NCC: its candidate range is its own
+    mp.cross_scales = S; mp.cross_lambda_q = q;
+    mp.disparity_type &= ~fields;
+    return ASW_OK;
+}
+
+// level s of a cross-scale call: candidates (minD >> s) .. ((minD + n - 1) >> s), n the finest level's plane count
+static void cross_scale_range(const MethodInfo* m, const MatchParams& mp, int s, int* minD, int* numD)
+{
+    const long long last = (long long)mp.minD + mp.numD + m->extra_planes - 1;  // minD + n - 1, n = m->planes(numD); no int overflow
+    *minD = mp.minD >> s;
+    *numD = (int)((last >> s) - *minD + 1 - m->extra_planes);
+}
+
+// The method on every level of the pair's 2x2-mean pyramid, coarsest first, then the combination of the levels' volumes and its
+// winner (k_cross_scale.hip).  Everything goes on the context's stream; the coarse pairs and volumes live in ctx->coarse, the
+// runners' named scratch is reused level after level.  The finest level runs last: ev[2] / ev[3] stay on it.
+static int run_cross_scale(asw_ctx* ctx, Frame* f, const MethodInfo* m, const MatchParams& mp, bool store)
+{
+    const int S = mp.cross_scales;
+    CrossScaleLaunch a;
+    const Frame* src = f;
+    for (int s = 1; s < S; s++) {
+        Frame* c = &ctx->coarse[s - 1];
+        c->valid = false;
+        c->rows = (src->rows + 1) / 2; c->cols = (src->cols + 1) / 2; c->channels = src->channels;
+        const size_t bytes = (size_t)c->rows * c->cols * c->channels;
+        ASW_TRY(c->L.ensure(bytes));
+        ASW_TRY(c->R.ensure(bytes));
+        ASW_TRY(launch_pyramid_down(ctx->stream, src->L.as<uint8_t>(), src->rows, src->cols, src->channels, c->L.as<uint8_t>()));
+        ASW_TRY(launch_pyramid_down(ctx->stream, src->R.as<uint8_t>(), src->rows, src->cols, src->channels, c->R.as<uint8_t>()));
+        c->valid = true;
+        src = c;
+    }
+    for (int s = S - 1; s >= 1; s--) {
+        Frame* c = &ctx->coarse[s - 1];
+        MatchParams ms = mp;
+        cross_scale_range(m, mp, s, &ms.minD, &ms.numD);
+        ASW_TRY(m->run(ctx, c, ms, true));
+        a.cv[s - 1] = c->vol.as<float>(); a.cH[s - 1] = c->rows; a.cW[s - 1] = c->cols; a.cminD[s - 1] = ms.minD;
+    }
+    ASW_TRY(m->run(ctx, f, mp, true));
+    a.vol = f->vol.as<float>(); a.disp = f->disp.as<float>();
+    a.H = f->rows; a.W = f->cols; a.n = m->planes(mp.numD); a.minD = mp.minD; a.S = S; a.store = store ? 1 : 0;
+    cross_scale_weights(S, mp.cross_lambda_q, a.w);
+    return launch_cross_scale_combine(ctx->stream, a);
+}
+
 int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp_in, bool keep_volume, bool sync)
 {
     f->invalidate_results();  // whatever the slot's disparity / volume were, they are not this call's
@@ -1055,13 +1113,26 @@ int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp_in, 
     if (mp.numD <= 0 || mp.minD < 0) return ASW_ERR_BAD_ARGUMENT;
     ASW_TRY(decode_algorithm(algorithm, &algorithm, &mp));  // asw_alg_cross() / asw_alg_adcensus() values -> 12 + parameters
     const MethodInfo* m = method_info(algorithm);
+    ASW_TRY(decode_cross_scale(m, mp));
     ASW_TRY(decode_subpixel(m, mp));
+    if (mp.cross_scales) {  // the flag's last rule, still before any work: every level keeps at least one candidate for the runner
+        if (!m || !m->run || m->no_volume) return ASW_ERR_UNSUPPORTED_METHOD;
+        for (int s = 1; s < mp.cross_scales; s++) {
+            int minD_s, numD_s;
+            cross_scale_range(m, mp, s, &minD_s, &numD_s);
+            if (numD_s < 1) return ASW_ERR_BAD_ARGUMENT;
+        }
+    }
     // the sub-pixel kernel reads the aggregated volume: the methods that can skip it (bilateral / direct8, geodesic, BLO1, the
     // bilateral grid) are asked for it; what the CALLER keeps is decided below
     const bool want_volume = keep_volume || mp.subpixel != 0;
     ASW_HIP_TRY(hipSetDevice(ctx->device));
     ASW_HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
-    int rc = m && m->run ? m->run(ctx, f, mp, want_volume) : ASW_ERR_UNSUPPORTED_METHOD;
+    int rc;
+    if (mp.cross_scales)  // every level's volume is wanted; the combined one is stored over the finest only for a reader
+        rc = run_cross_scale(ctx, f, m, mp, want_volume);
+    else
+        rc = m && m->run ? m->run(ctx, f, mp, want_volume) : ASW_ERR_UNSUPPORTED_METHOD;
     if (rc == ASW_OK && mp.subpixel)  // after the aggregation events: counts in total_ms and cost_ms, not in aggregate_ms
         rc = launch_subpixel(ctx->stream, mp.subpixel, f->vol.as<float>(), m->planes(mp.numD), f->rows, f->cols,
                              mp.minD, f->disp.as<float>());

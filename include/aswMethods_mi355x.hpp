@@ -287,6 +287,23 @@ inline void stereoMatchingSubpixel(AswMat srcLeft, AswMat srcRight, AswMat& disp
     disparityMap = d;
 }
 
+// Not in the reference: stereoMatching with cross-scale cost aggregation (Zhang et al. 2014) -- the method runs
+// on `scales` (2..5) levels of a 2x2-mean pyramid of the pair, and the map is the winner of the regularised finest-scale volume,
+// lambda = lambdaQ / 64 (lambdaQ 1..255).  subpixel: 0, SUBPIXEL_PARABOLA or SUBPIXEL_EQUIANGULAR, applied to that volume.  Silent
+// errors leave an empty Mat like stereoMatching; arguments out of range, a candidate range too short for the scales, SGBM (it has no
+// selector volume), BM and NCC throw.
+inline void stereoMatchingCrossScale(AswMat srcLeft, AswMat srcRight, AswMat& disparityMap, DisparityType disparityType,
+                                     StereoMatchingAlgorithms algorithmType, int winSize = 15, int minDisparity = 0, int numDisparity = 64,
+                                     int scales = 3, int lambdaQ = 19, int subpixel = 0)
+{
+    if (algorithmType == SGBM) throw std::runtime_error("stereoMatchingCrossScale: SGBM has no cost volume to combine");
+    AswMat d = asw::detail::aggregate(srcLeft, srcRight, [&](asw_ctx* c, asw_image* l, asw_image* r, asw_image* o) {
+        return asw_stereo_match(c, l, r, o, (int)disparityType | subpixel | asw_disparity_cross_scale(scales, lambdaQ), (int)algorithmType,
+                                winSize, minDisparity, numDisparity, nullptr, 0);
+    }, "stereoMatchingCrossScale");
+    disparityMap = d;
+}
+
 // M.h:101-102
 inline void computeAD(AswMat leftImg, AswMat rightImg, std::vector<AswMat>& cost_ds, DisparityType dispType = DISPARITY_LEFT,
                       int minDisparity = 0, int numDisparity = 30)

@@ -61,6 +61,32 @@ enum { ASW_DISPARITY_LEFT = 0, ASW_DISPARITY_RIGHT = 1 };
  * and the refined calls do not take the flags.  asw_get_timing: the extra kernel counts in total_ms and cost_ms. */
 enum { ASW_DISPARITY_SUBPIXEL_PARABOLA = 0x100, ASW_DISPARITY_SUBPIXEL_EQUIANGULAR = 0x200 };
 
+/* Cross-scale cost aggregation (Zhang et al., CVPR 2014; not in the reference): asw_disparity_cross_scale(S, q)
+ * OR-ed into the disparity_type of asw_stereo_match, asw_match_resident, every asw_aggregate_* and asw_stereo_match_batch.  The method
+ * (same window, same parameters) aggregates on S levels of a 2x2-mean pyramid of the pair; the regularised finest-scale volume is
+ * the closed-form combination of the levels' volumes, and the map is its winner.  Bit 12 = the flag, bits 13-15 = S (2..5), bits
+ * 16-23 = q (1..255, lambda = q / 64); bits 0, 8 and 9 keep their meaning; every other bit must be 0.  Defaults everywhere: S = 3,
+ * q = 19.  All integer / IEEE, one operation each:
+ *   pyramid: level s+1 has ceil(h/2) x ceil(w/2) pixels, per channel (a + b + c + d + 2) >> 2 of the level-s pixels at
+ *     (min(2Y+j, h-1), min(2X+i, w-1)), i, j in {0, 1};
+ *   range: n = asw_volume_planes() at level 0; level s runs min_d_s = min_d >> s and planes_s = ((min_d + n - 1) >> s) - min_d_s + 1
+ *     planes, i.e. num_d_s = planes_s - (n - num_d); a level with num_d_s < 1 refuses the call;
+ *   weights: A = tridiag(-lambda; 1+lambda, 1+2 lambda, .., 1+lambda; -lambda) (S x S), w = A^-1 e_0 by the Thomas algorithm in
+ *     f64, each w_s rounded to f32;
+ *   combine: acc = 0.0 (f64); s = 0..S-1 in order: acc += (double)w_s * (double)V_s[((min_d + k) >> s) - min_d_s][y >> s][x >> s];
+ *     out[k][y][x] = (float)acc; map = winner of out, strict '<' in ascending k, NaN never wins, min_d + k.
+ * The volume a flagged call returns is `out`; a sub-pixel flag in the same value refines the map on `out`.  With bit 12 set:
+ * S outside 2..5, q = 0, any other bit, both sub-pixel flags or a level with num_d_s < 1 give ASW_ERR_BAD_ARGUMENT before any work;
+ * ASW_ALG_NCC (and asw_ncc_disparity) ASW_ERR_UNSUPPORTED_METHOD; ASW_ALG_SGBM ignores the bits as it ignores disparity_type; what
+ * the method's runner refuses at any level is the call's status.  With bit 12 clear nothing changes.  asw_get_timing: aggregate_ms /
+ * aggregate_launches are those of the finest level, total_ms covers the whole call.  The refined calls do not take the flag. */
+enum { ASW_DISPARITY_CROSS_SCALE = 0x1000 };
+static inline int asw_disparity_cross_scale(int scales, int lambda_q)
+{
+    const int bad = scales < 2 || scales > 5 || lambda_q < 1 || lambda_q > 255;
+    return ASW_DISPARITY_CROSS_SCALE | ((bad ? 0 : scales) << 13) | ((lambda_q & 0xFF) << 16);
+}
+
 /* parametersStereo.h:10-24 (StereoMatchingAlgorithms) */
 enum {
     ASW_ALG_BM = 0,

@@ -48,6 +48,13 @@ tests/permeability_ref.py, volume and map, with and without the kept volume; its
 mismatch prints the tag permeability_ref.build_case rebuilds.
 
     python tools/fuzz_parity.py --seconds 120 --seed 1 --only permeability
+
+The leg cross_scale is cross-scale cost aggregation (asw_disparity_cross_scale in disparity_type) over every
+method tests/cross_scale_ref.py lists, against that file's restatement applied to the per-scale volumes a second context returns for
+the pyramid levels: volume and map (sub-pixel flags included), with and without the kept volume; its cases come from
+cross_scale_ref.random_case and a mismatch prints the tag cross_scale_ref.build_case rebuilds.
+
+    python tools/fuzz_parity.py --seconds 120 --seed 1 --only cross_scale
 """
 import argparse
 import os
@@ -63,6 +70,7 @@ from oracle import asw_oracle as O  # noqa: E402
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import asw_cases  # noqa: E402
+import cross_scale_ref  # noqa: E402
 import matcher_cases as mc  # noqa: E402
 import permeability_ref  # noqa: E402
 import sgbm_census_ref as scr  # noqa: E402
@@ -93,7 +101,8 @@ class SgbmCensusLeg:
 REF_LEGS = {m.name: m for m in SELECTOR_METHODS[:2]}
 REF_LEGS["sgbm_census"] = SgbmCensusLeg
 REF_LEGS.update((m.name, m) for m in SELECTOR_METHODS[2:])
-REF_LEGS["permeability"] = permeability_ref  # last: the legs before it keep the cases a seed drew for them
+REF_LEGS["permeability"] = permeability_ref  # behind the others: the legs before it keep the cases a seed drew for them
+REF_LEGS["cross_scale"] = cross_scale_ref    # last, for the same reason
 LEGS = tuple(mc.FAMILIES) + tuple(REF_LEGS)
 ORACLE_METHODS = ["classic", "direct8", "geodesic", "guided", "guided2", "guided3", "wmedian", "blo1", "ncc", "ncc_cost",
                   "ad_tad", "similarity", "sad", "geodist", "gfilter", "prep", "bilgrid", "lrcheck", "resident", "batch"]
