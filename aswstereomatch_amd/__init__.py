@@ -36,6 +36,7 @@ __all__ = [
     "twopass_algorithm", "computeAdaptiveWeight_twopass",
     "permeability_algorithm", "computeAdaptiveWeight_permeability",
     "CROSS_SCALE", "cross_scale",
+    "SCANLINE", "scanline", "scanline_penalties",
     "AswError",
 ]
 
@@ -143,6 +144,36 @@ def cross_scale(scales=3, lambda_q=19):
     return CROSS_SCALE | ((0 if bad else scales) << 13) | ((lambda_q & 0xFF) << 16)
 
 
+SCANLINE = 0x01000000  # ASW_DISPARITY_SCANLINE
+
+
+def scanline(p1_code=8, unit_code=5, p2_ratio=4):
+    """asw_disparity_scanline of asw_mi355x.h: the value to OR into a disparity type (or to pass as scanline= where that keyword
+    exists) that regularises the method's aggregated volume along four scan paths and takes the winner of the result (DESIGN.md
+    section 4.19): P1 = p1_code * 4 ** (unit_code - 5), P2 = p2_ratio * P1, p1_code in 1..127, unit_code in 0..7, p2_ratio in 1..8;
+    an argument out of range gives the flag alone, which the library refuses with ERR_BAD_ARGUMENT."""
+    a, u, r = int(p1_code), int(unit_code), int(p2_ratio)
+    if a < 1 or a > 127 or u < 0 or u > 7 or r < 1 or r > 8:
+        return SCANLINE
+    return SCANLINE | (a << 1) | (u << 25) | ((r - 1) << 28)
+
+
+def scanline_penalties(value):
+    """(P1, P2) of a scanline() value, as the f32 numbers the library adds"""
+    value = int(value)
+    a, u, r = (value >> 1) & 0x7F, (value >> 25) & 7, ((value >> 28) & 7) + 1
+    unit = 4.0 ** (u - 5)
+    return np.float32(a * unit), np.float32(r * a * unit)
+
+
+def _disparity_type(disparityType, subpixel, cross_scale, scanline):
+    """disparityType with the keywords' values OR-ed in; cross_scale= together with scanline= is refused as the library refuses it"""
+    if cross_scale and scanline:
+        _state.status = ERR_BAD_ARGUMENT
+        raise AswError(ERR_BAD_ARGUMENT, "cross_scale= with scanline=")
+    return int(disparityType) | int(subpixel or 0) | int(cross_scale or 0) | int(scanline or 0)
+
+
 PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL = 0, 1  # StereoBM::PREFILTER_*; asw_stereo_bm serves XSOBEL
 REFINE_GAMMA_C, REFINE_GAMMA_S = 60.0, 9.0  # default colour / distance gammas of the refinement's weighted median (asw_mi355x.h)
 # statuses for which the reference returns silently / an empty Mat
@@ -230,9 +261,10 @@ class Context:
 
     # ---- whole-method entry point (M.h:91-92) ----
     def stereoMatching(self, srcLeft, srcRight, disparityType, algorithmType, winSize=15, minDisparity=0,
-                       numDisparity=64, return_cost_volume=False, subpixel=None, cross_scale=None):
-        """subpixel: None, SUBPIXEL_PARABOLA or SUBPIXEL_EQUIANGULAR; cross_scale: None or a cross_scale() value; both are OR-ed
-        into disparityType."""
+                       numDisparity=64, return_cost_volume=False, subpixel=None, cross_scale=None, scanline=None):
+        """subpixel: None, SUBPIXEL_PARABOLA or SUBPIXEL_EQUIANGULAR; cross_scale: None or a cross_scale() value; scanline: None or
+        a scanline() value (not together with cross_scale); all are OR-ed into disparityType."""
+        disparityType = _disparity_type(disparityType, subpixel, cross_scale, scanline)
         li, la = _image(srcLeft)
         ri, ra = _image(srcRight)
         disp = np.zeros((la.shape[0], la.shape[1]), np.float32)
@@ -242,7 +274,7 @@ class Context:
         if return_cost_volume:
             vol = np.zeros((self._candidates(int(algorithmType), numDisparity), la.shape[0], la.shape[1]), np.float32)
             pv = vol.ctypes.data_as(C.c_void_p)
-        rc = self._lib.asw_stereo_match(self._h, C.byref(li), C.byref(ri), C.byref(di), int(disparityType) | int(subpixel or 0) | int(cross_scale or 0),
+        rc = self._lib.asw_stereo_match(self._h, C.byref(li), C.byref(ri), C.byref(di), disparityType,
                                         int(algorithmType), winSize, minDisparity, numDisparity, pv, 0 if vol is None else vol.size)
         if not self._finish(rc, "asw_stereo_match"):
             return (None, None) if return_cost_volume else None
@@ -641,8 +673,8 @@ class Context:
         self._strict(self._lib.asw_upload_pair(self._h, slot, C.byref(li), C.byref(ri)), "asw_upload_pair")
 
     def match_resident(self, slot, disparityType, algorithmType, winSize, minDisparity, numDisparity, keep_volume=False,
-                       subpixel=None, cross_scale=None):
-        rc = self._lib.asw_match_resident(self._h, slot, int(disparityType) | int(subpixel or 0) | int(cross_scale or 0), int(algorithmType), winSize,
+                       subpixel=None, cross_scale=None, scanline=None):
+        rc = self._lib.asw_match_resident(self._h, slot, _disparity_type(disparityType, subpixel, cross_scale, scanline), int(algorithmType), winSize,
                                           minDisparity, numDisparity, 1 if keep_volume else 0)
         self._strict(rc, "asw_match_resident")
 
@@ -704,14 +736,15 @@ class Context:
 
 
 def stereoMatchingBatch(lefts, rights, disparityType, algorithmType, winSize=15, minDisparity=0, numDisparity=64,
-                        device_ids=None, out=None, subpixel=None, cross_scale=None):
+                        device_ids=None, out=None, subpixel=None, cross_scale=None, scanline=None):
     """asw_stereo_match_batch: frame i -> device device_ids[i % len(device_ids)], one host thread per device.
-    subpixel: None, SUBPIXEL_PARABOLA or SUBPIXEL_EQUIANGULAR; cross_scale: None or a cross_scale() value; both are OR-ed into
-    disparityType.
+    subpixel: None, SUBPIXEL_PARABOLA or SUBPIXEL_EQUIANGULAR; cross_scale: None or a cross_scale() value; scanline: None or a
+    scanline() value (not together with cross_scale); all are OR-ed into disparityType.
 
     out: optional list of C-contiguous float32 (H, W) arrays to receive the disparities (a frame loop that reuses its
     output buffers avoids first-touch page faults on 8 MB per 1080p frame)."""
     lib = _lib.lib()
+    disparityType = _disparity_type(disparityType, subpixel, cross_scale, scanline)
     n = len(lefts)
     if device_ids is None:
         device_ids = list(range(max(1, lib.asw_device_count())))
@@ -734,7 +767,7 @@ def stereoMatchingBatch(lefts, rights, disparityType, algorithmType, winSize=15,
         keep.append((la, ra))
         outs.append(o)
     devs = (C.c_int * len(device_ids))(*device_ids)
-    rc = lib.asw_stereo_match_batch(n, L, R, D, int(disparityType) | int(subpixel or 0) | int(cross_scale or 0), int(algorithmType), winSize, minDisparity, numDisparity,
+    rc = lib.asw_stereo_match_batch(n, L, R, D, disparityType, int(algorithmType), winSize, minDisparity, numDisparity,
                                     len(device_ids), devs)
     _state.status = rc
     if rc in _SILENT:

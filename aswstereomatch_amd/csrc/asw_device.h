@@ -52,6 +52,26 @@ __device__ __forceinline__ int wave_min(int v)
     return v;
 }
 
+// The same for f32, for a dependent chain that cannot wait for six LDS-crossbar round trips: a running minimum by DPP moves (a lane
+// without a source keeps its own value, which min() ignores) leaves the total in lane 63, read from there.  No lane may hold a NaN;
+// the sign of a zero result is whichever lane's the reduction meets.
+template <int CTRL, int ROWMASK>
+__device__ __forceinline__ float dpp_min_f32(float v)
+{
+    const int b = __float_as_int(v);
+    return fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(b, b, CTRL, ROWMASK, 0xf, false)));
+}
+__device__ __forceinline__ float wave_min(float v)
+{
+    v = dpp_min_f32<0x111, 0xf>(v);  // row_shr:1
+    v = dpp_min_f32<0x112, 0xf>(v);  // row_shr:2
+    v = dpp_min_f32<0x114, 0xf>(v);  // row_shr:4
+    v = dpp_min_f32<0x118, 0xf>(v);  // row_shr:8   -> lane 15 of each row of 16 holds the row's minimum
+    v = dpp_min_f32<0x142, 0xa>(v);  // row_bcast:15 into rows 1 and 3
+    v = dpp_min_f32<0x143, 0xc>(v);  // row_bcast:31 into rows 2 and 3
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+
 // minimum of lo and maximum of hi over the 64 lanes, in every lane (int or uint32_t).  By value: through references the
 // accumulators of the caller's loop come out in other registers.
 template <class T>

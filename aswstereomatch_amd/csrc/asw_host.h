@@ -33,6 +33,7 @@ struct MatchParams {
     int disparity_type, win, minD, numD;  // disparity_type as the caller passed it; run_method strips the sub-pixel flag into `subpixel`
     int subpixel = 0;                   // 0 | ASW_DISPARITY_SUBPIXEL_PARABOLA | ASW_DISPARITY_SUBPIXEL_EQUIANGULAR
     int cross_scales = 0, cross_lambda_q = 0;  // asw_disparity_cross_scale() fields, stripped like the sub-pixel flag: 0 = one scale, else 2..5 and 1..255
+    float scan_p1 = 0, scan_p2 = 0;     // asw_disparity_scanline() penalties, stripped like the cross-scale fields: scan_p1 == 0 = no scanline optimisation
     double gamma_c = 30, gamma_g = 20;  // M.cpp:58
     int twopass = 0;                    // entry 2 as the two-pass approximation (asw_alg_twopass()): the gammas above are its integers
     double eps = 1e-6;                  // M.cpp:73,76

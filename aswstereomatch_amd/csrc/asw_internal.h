@@ -160,6 +160,19 @@ struct CrossScaleLaunch {
 };
 int launch_cross_scale_combine(hipStream_t s, const CrossScaleLaunch& a);
 
+// ---- scanline optimisation of an aggregated volume (k_scanline.hip), DESIGN.md section 4.19 ----
+struct ScanlineLaunch {
+    float* vol;   // V [n][H][W]: read, and overwritten with the optimised volume
+    float* sum;   // scratch, n * H * W floats: the paths' running sum, [y][x][k]
+    float* ck;    // scratch, scanline_checkpoint_floats(H, W, n) floats
+    float* disp;  // [H][W]: the optimised volume's winner
+    int H, W, n, minD;
+    float P1, P2;
+};
+int scanline_max_planes();  // 1025
+size_t scanline_checkpoint_floats(int H, int W, int n);
+int launch_scanline(hipStream_t s, const ScanlineLaunch& a);  // horizontal pass, TB, BT + winner: three kernels
+
 struct BilateralLaunch {
     const uint8_t* gL;
     const uint8_t* gR;

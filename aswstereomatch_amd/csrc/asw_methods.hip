@@ -1064,6 +1064,38 @@ static int decode_cross_scale(const MethodInfo* m, MatchParams& mp)
     return ASW_OK;
 }
 
+// Scanline fields of a caller's disparity_type -> mp.scan_p1 / mp.scan_p2, mp.disparity_type without them.  A
+// value with bit 24 clear passes through as it is: decode_cross_scale and the methods refuse what they refused before.
+static int decode_scanline(const MethodInfo* m, MatchParams& mp)
+{
+    const int sub = ASW_DISPARITY_SUBPIXEL_PARABOLA | ASW_DISPARITY_SUBPIXEL_EQUIANGULAR, fields = 0x7F0000FE;
+    mp.scan_p1 = mp.scan_p2 = 0;
+    if ((m && m->ignores_disparity_type) || !(mp.disparity_type & ASW_DISPARITY_SCANLINE)) return ASW_OK;
+    if (mp.disparity_type & ASW_DISPARITY_CROSS_SCALE) return ASW_ERR_BAD_ARGUMENT;  // the two together: not served
+    const int a = (mp.disparity_type >> 1) & 0x7F, u = (mp.disparity_type >> 25) & 7, ratio = ((mp.disparity_type >> 28) & 7) + 1;
+    if (mp.disparity_type & ~(fields | sub | ASW_DISPARITY_RIGHT)) return ASW_ERR_BAD_ARGUMENT;
+    if (a == 0 || (mp.disparity_type & sub) == sub) return ASW_ERR_BAD_ARGUMENT;
+    if (!m || !m->run || m->no_volume || m->no_subpixel) return ASW_ERR_UNSUPPORTED_METHOD;  // NCC: its candidate range is its own
+    if (m->planes(mp.numD) > scanline_max_planes()) return ASW_ERR_BAD_ARGUMENT;
+    const float unit = ldexpf(1.0f, 2 * (u - 5));  // 4^(u - 5): a * unit and ratio * a * unit are exact
+    mp.scan_p1 = (float)a * unit; mp.scan_p2 = (float)(ratio * a) * unit;
+    mp.disparity_type &= ~fields;
+    return ASW_OK;
+}
+
+// The four paths over the runner's volume, their sum over it, and its winner (k_scanline.hip)
+static int run_scanline(asw_ctx* ctx, Frame* f, const MethodInfo* m, const MatchParams& mp)
+{
+    ScanlineLaunch a;
+    a.H = f->rows; a.W = f->cols; a.n = m->planes(mp.numD); a.minD = mp.minD; a.P1 = mp.scan_p1; a.P2 = mp.scan_p2;
+    DevBuf& sum = ctx->buf("scan_sum");
+    DevBuf& ck = ctx->buf("scan_ck");
+    ASW_TRY(sum.ensure((size_t)a.n * a.H * a.W * sizeof(float)));
+    ASW_TRY(ck.ensure(std::max<size_t>(scanline_checkpoint_floats(a.H, a.W, a.n), 1) * sizeof(float)));
+    a.vol = f->vol.as<float>(); a.sum = sum.as<float>(); a.ck = ck.as<float>(); a.disp = f->disp.as<float>();
+    return launch_scanline(ctx->stream, a);
+}
+
 // level s of a cross-scale call: candidates (minD >> s) .. ((minD + n - 1) >> s), n the finest level's plane count
 static void cross_scale_range(const MethodInfo* m, const MatchParams& mp, int s, int* minD, int* numD)
 {
@@ -1113,6 +1145,7 @@ int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp_in, 
     if (mp.numD <= 0 || mp.minD < 0) return ASW_ERR_BAD_ARGUMENT;
     ASW_TRY(decode_algorithm(algorithm, &algorithm, &mp));  // asw_alg_cross() / asw_alg_adcensus() values -> 12 + parameters
     const MethodInfo* m = method_info(algorithm);
+    ASW_TRY(decode_scanline(m, mp));
     ASW_TRY(decode_cross_scale(m, mp));
     ASW_TRY(decode_subpixel(m, mp));
     if (mp.cross_scales) {  // the flag's last rule, still before any work: every level keeps at least one candidate for the runner
@@ -1125,7 +1158,7 @@ int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp_in, 
     }
     // the sub-pixel kernel reads the aggregated volume: the methods that can skip it (bilateral / direct8, geodesic, BLO1, the
     // bilateral grid) are asked for it; what the CALLER keeps is decided below
-    const bool want_volume = keep_volume || mp.subpixel != 0;
+    const bool want_volume = keep_volume || mp.subpixel != 0 || mp.scan_p1 != 0;
     ASW_HIP_TRY(hipSetDevice(ctx->device));
     ASW_HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
     int rc;
@@ -1133,6 +1166,8 @@ int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp_in, 
         rc = run_cross_scale(ctx, f, m, mp, want_volume);
     else
         rc = m && m->run ? m->run(ctx, f, mp, want_volume) : ASW_ERR_UNSUPPORTED_METHOD;
+    if (rc == ASW_OK && mp.scan_p1 != 0)  // like the sub-pixel step: behind the aggregation events
+        rc = run_scanline(ctx, f, m, mp);
     if (rc == ASW_OK && mp.subpixel)  // after the aggregation events: counts in total_ms and cost_ms, not in aggregate_ms
         rc = launch_subpixel(ctx->stream, mp.subpixel, f->vol.as<float>(), m->planes(mp.numD), f->rows, f->cols,
                              mp.minD, f->disp.as<float>());

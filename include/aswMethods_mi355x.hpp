@@ -304,6 +304,23 @@ inline void stereoMatchingCrossScale(AswMat srcLeft, AswMat srcRight, AswMat& di
     disparityMap = d;
 }
 
+// Not in the reference: stereoMatching with scanline optimisation of the aggregated volume (Mei et al. 2011) --
+// the method's volume is regularised along four scan paths with P1 = p1Code * 4^(unitCode - 5) and P2 = p2Ratio * P1 (p1Code 1..127,
+// unitCode 0..7, p2Ratio 1..8), and the map is the winner of the result.  subpixel: 0, SUBPIXEL_PARABOLA or SUBPIXEL_EQUIANGULAR,
+// applied to that volume.  Silent errors leave an empty Mat like stereoMatching; arguments out of range, SGBM (it has no selector
+// volume), BM and NCC throw.
+inline void stereoMatchingScanline(AswMat srcLeft, AswMat srcRight, AswMat& disparityMap, DisparityType disparityType,
+                                   StereoMatchingAlgorithms algorithmType, int winSize = 15, int minDisparity = 0, int numDisparity = 64,
+                                   int p1Code = 8, int unitCode = 5, int p2Ratio = 4, int subpixel = 0)
+{
+    if (algorithmType == SGBM) throw std::runtime_error("stereoMatchingScanline: SGBM has no cost volume to optimise");
+    AswMat d = asw::detail::aggregate(srcLeft, srcRight, [&](asw_ctx* c, asw_image* l, asw_image* r, asw_image* o) {
+        return asw_stereo_match(c, l, r, o, (int)disparityType | subpixel | asw_disparity_scanline(p1Code, unitCode, p2Ratio),
+                                (int)algorithmType, winSize, minDisparity, numDisparity, nullptr, 0);
+    }, "stereoMatchingScanline");
+    disparityMap = d;
+}
+
 // M.h:101-102
 inline void computeAD(AswMat leftImg, AswMat rightImg, std::vector<AswMat>& cost_ds, DisparityType dispType = DISPARITY_LEFT,
                       int minDisparity = 0, int numDisparity = 30)

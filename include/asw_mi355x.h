@@ -87,6 +87,33 @@ static inline int asw_disparity_cross_scale(int scales, int lambda_q)
     return ASW_DISPARITY_CROSS_SCALE | ((bad ? 0 : scales) << 13) | ((lambda_q & 0xFF) << 16);
 }
 
+/* Scanline optimisation of the aggregated volume (Mei et al., ICCV Workshops 2011; not in the reference):
+ * asw_disparity_scanline(p1_code, unit_code, p2_ratio) OR-ed into the disparity_type of asw_stereo_match, asw_match_resident, every
+ * asw_aggregate_* and asw_stereo_match_batch.  The method's volume V (n = asw_volume_planes() planes) is regularised along four paths
+ * and the map is the winner of the result.  Bit 24 = the flag, bits 1-7 = a (P1 code, 1..127), bits 25-27 = u (unit = 4^(u - 5),
+ * 1/1024 .. 16), bits 28-30 = p2_ratio - 1 (p2_ratio 1..8); bits 0, 8 and 9 keep their meaning; every other bit, bit 31 included,
+ * must be 0.  P1 = (float)(a * unit), P2 = (float)(p2_ratio * a * unit), both exact.  Defaults everywhere: a = 8, u = 5, ratio 4
+ * (P1 = 8, P2 = 32); an argument out of range gives the flag alone (a = 0), which the library refuses.  All f32, one IEEE operation each:
+ *   c = V where V is finite, else +inf (NaN, +inf and -inf alike);
+ *   paths r in this order: LR (predecessor q = x-1), RL (x+1), TB (y-1), BT (y+1); minq = min over k of L_r(q,k);
+ *   q outside the frame or minq == +inf (q has no finite candidate): L_r(p,k) = c(p,k); otherwise
+ *     t0 = L_r(q,k); t1 = L_r(q,k-1) + P1 (absent for k = 0); t2 = L_r(q,k+1) + P1 (absent for k = n-1); t3 = minq + P2;
+ *     m = min(t0, t1, t2, t3); L_r(p,k) = c(p,k) + (m - minq);
+ *   S = ((L_LR + L_RL) + L_TB) + L_BT; out = V finite ? S : V; map = winner of out, strict '<' in ascending k, NaN and +inf never
+ *   win, a pixel without a winner is 0, else min_d + k.
+ * The volume a flagged call returns is `out`; a sub-pixel flag in the same value refines the map on `out`.  With bit 24 set, in
+ * this order and before any work: bit 12 (cross-scale) as well ASW_ERR_BAD_ARGUMENT; any other bit, a = 0 or both sub-pixel flags
+ * ASW_ERR_BAD_ARGUMENT; ASW_ALG_NCC (and asw_ncc_disparity), ASW_ALG_BM and values outside the selector ASW_ERR_UNSUPPORTED_METHOD;
+ * more than 1025 planes ASW_ERR_BAD_ARGUMENT.  ASW_ALG_SGBM ignores the bits as it ignores disparity_type; what the method's runner
+ * refuses is the call's status.  With bit 24 clear nothing changes.  asw_get_timing: the step counts in total_ms and cost_ms, like
+ * the sub-pixel step.  The refined calls do not take the flag. */
+enum { ASW_DISPARITY_SCANLINE = 0x01000000 };
+static inline int asw_disparity_scanline(int p1_code, int unit_code, int p2_ratio)
+{
+    const int bad = p1_code < 1 || p1_code > 127 || unit_code < 0 || unit_code > 7 || p2_ratio < 1 || p2_ratio > 8;
+    return bad ? ASW_DISPARITY_SCANLINE : ASW_DISPARITY_SCANLINE | (p1_code << 1) | (unit_code << 25) | ((p2_ratio - 1) << 28);
+}
+
 /* parametersStereo.h:10-24 (StereoMatchingAlgorithms) */
 enum {
     ASW_ALG_BM = 0,

@@ -55,6 +55,13 @@ the pyramid levels: volume and map (sub-pixel flags included), with and without 
 cross_scale_ref.random_case and a mismatch prints the tag cross_scale_ref.build_case rebuilds.
 
     python tools/fuzz_parity.py --seconds 120 --seed 1 --only cross_scale
+
+The leg scanline is scanline optimisation (asw_disparity_scanline in disparity_type) over the same methods,
+against the restatement of tests/scanline_ref.py applied to the plain volume a second context returns: volume and map (sub-pixel flags
+included), with and without the kept volume; its cases come from scanline_ref.random_case and a mismatch prints the tag
+scanline_ref.build_case rebuilds.
+
+    python tools/fuzz_parity.py --seconds 120 --seed 1 --only scanline
 """
 import argparse
 import os
@@ -73,6 +80,7 @@ import asw_cases  # noqa: E402
 import cross_scale_ref  # noqa: E402
 import matcher_cases as mc  # noqa: E402
 import permeability_ref  # noqa: E402
+import scanline_ref  # noqa: E402
 import sgbm_census_ref as scr  # noqa: E402
 from selector_methods import METHODS as SELECTOR_METHODS  # noqa: E402
 
@@ -102,7 +110,8 @@ REF_LEGS = {m.name: m for m in SELECTOR_METHODS[:2]}
 REF_LEGS["sgbm_census"] = SgbmCensusLeg
 REF_LEGS.update((m.name, m) for m in SELECTOR_METHODS[2:])
 REF_LEGS["permeability"] = permeability_ref  # behind the others: the legs before it keep the cases a seed drew for them
-REF_LEGS["cross_scale"] = cross_scale_ref    # last, for the same reason
+REF_LEGS["cross_scale"] = cross_scale_ref    # behind those, for the same reason
+REF_LEGS["scanline"] = scanline_ref          # last, for the same reason
 LEGS = tuple(mc.FAMILIES) + tuple(REF_LEGS)
 ORACLE_METHODS = ["classic", "direct8", "geodesic", "guided", "guided2", "guided3", "wmedian", "blo1", "ncc", "ncc_cost",
                   "ad_tad", "similarity", "sad", "geodist", "gfilter", "prep", "bilgrid", "lrcheck", "resident", "batch"]
