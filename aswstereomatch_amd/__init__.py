@@ -78,20 +78,43 @@ MODE_SGBM_3WAY = 2  # StereoSGBM::MODE_SGBM_3WAY, the one mode asw_sgbm serves
 SGBM_PATHS_3WAY, SGBM_PATHS_HH4, SGBM_PATHS_SGBM, SGBM_PATHS_HH = 0x07, 0x0F, 0x37, 0xFF
 _SGBM_MODE_PATHS = 0x40000000  # ASW_SGBM_MODE_PATHS: asw_sgbm's mode carrying a path mask, as the header's inline asw_sgbm_paths forms it
 _SGBM_MODE_CENSUS = 0x10000  # ASW_SGBM_MODE_CENSUS: beside _SGBM_MODE_PATHS, the census cost of the header's inline asw_sgbm_census
-_ALG_CROSS_PARAMS = 0x40000000  # ASW_ALG_CROSS_PARAMS
+_ALG_CROSS_PARAMS, _ALG_ADCENSUS_PARAMS, _ALG_TWOPASS_PARAMS, _ALG_PERMEABILITY_PARAMS = 1 << 30, 1 << 29, 1 << 28, 1 << 27  # ASW_ALG_*_PARAMS
+_COST_CENSUS_PARAMS = 0x40000000  # ASW_COST_CENSUS_PARAMS: asw_cost_tad's threshold carrying the census cost builders, as the header's inline asw_cost_census / asw_cost_adcensus form it
+CROSS_SCALE, SCANLINE = 1 << 12, 1 << 24  # ASW_DISPARITY_CROSS_SCALE, ASW_DISPARITY_SCANLINE
+# The parameter fields of the selector's two packed words, `algorithmType` and `disparityType`, as asw_mi355x.h lays them out
+# (csrc/asw_selector.h holds the decoders' side): name -> (shift, width, lowest, highest admissible value)
+_FIELDS = {
+    "tau": (8, 8, 0, 255), "trunc": (16, 8, 1, 255), "lambda_census": (16, 8, 1, 255), "lambda_ad": (24, 5, 1, 31),
+    "gamma_c": (8, 8, 1, 255), "gamma_g": (16, 8, 1, 255), "sigma": (8, 8, 1, 255),
+    "scales": (13, 3, 2, 5), "lambda_q": (16, 8, 1, 255),
+    "p1_code": (1, 7, 1, 127), "unit_code": (25, 3, 0, 7), "p2_ratio - 1": (28, 3, 0, 7),
+}
+
+
+def _pack(base, values, spoil=None, spoil_bits=0):
+    """base with every value in its field.  A value outside its field's range makes the word one the library refuses, the way
+    asw_mi355x.h's encoder of the word does: spoil=None leaves 0 in that field; otherwise spoil_bits are set, the fields named in
+    spoil hold 0 and the others their value cut to the field's width."""
+    values = {name: int(v) for name, v in values.items()}
+    bad = [name for name, v in values.items() if not _FIELDS[name][2] <= v <= _FIELDS[name][3]]
+    zeroed = bad if spoil is None else spoil if bad else ()
+    word = base | (spoil_bits if bad and spoil is not None else 0)
+    for name, v in values.items():
+        shift, width = _FIELDS[name][:2]
+        word |= ((0 if name in zeroed else v) & ((1 << width) - 1)) << shift
+    return word
+
+
+def _unpack(word, *names):
+    """the fields `names` of a packed word"""
+    return tuple((int(word) >> _FIELDS[n][0]) & ((1 << _FIELDS[n][1]) - 1) for n in names)
 
 
 def cross_algorithm(tau=20, trunc=20):
     """asw_alg_cross of asw_mi355x.h: the value of `algorithmType` that runs ADAPTIVE_WEIGHT_CROSS with colour threshold tau (0..255)
     and cost truncation trunc (1..255) in every call that takes an algorithm; an argument out of range gives a value the library
     refuses with ERR_BAD_ARGUMENT (bit 24)."""
-    tau, trunc = int(tau), int(trunc)
-    bad = 0x01000000 if (tau < 0 or tau > 255 or trunc < 1 or trunc > 255) else 0
-    return _ALG_CROSS_PARAMS | bad | ((trunc & 0xFF) << 16) | ((tau & 0xFF) << 8) | int(StereoMatchingAlgorithms.ADAPTIVE_WEIGHT_CROSS)
-
-
-_ALG_ADCENSUS_PARAMS = 0x20000000  # ASW_ALG_ADCENSUS_PARAMS
-_COST_CENSUS_PARAMS = 0x40000000  # ASW_COST_CENSUS_PARAMS: asw_cost_tad's threshold carrying the census cost builders, as the header's inline asw_cost_census / asw_cost_adcensus form it
+    return _pack(_ALG_CROSS_PARAMS | int(_A.ADAPTIVE_WEIGHT_CROSS), {"tau": tau, "trunc": trunc}, spoil=(), spoil_bits=1 << 24)
 
 
 def adcensus_algorithm(tau=20, lambda_ad=10, lambda_census=30):
@@ -99,39 +122,22 @@ def adcensus_algorithm(tau=20, lambda_ad=10, lambda_census=30):
     12's cross-based aggregation over the census + AD cost -- with colour threshold tau (0..255) and the table constants lambda_ad
     (1..31) and lambda_census (1..255) in every call that takes an algorithm; an argument out of range gives a value the library
     refuses with ERR_BAD_ARGUMENT (lambda_ad field 0)."""
-    tau, lambda_ad, lambda_census = int(tau), int(lambda_ad), int(lambda_census)
-    bad = tau < 0 or tau > 255 or lambda_ad < 1 or lambda_ad > 31 or lambda_census < 1 or lambda_census > 255
-    return (_ALG_ADCENSUS_PARAMS | ((0 if bad else lambda_ad) << 24) | ((lambda_census & 0xFF) << 16) | ((tau & 0xFF) << 8) |
-            int(StereoMatchingAlgorithms.ADAPTIVE_WEIGHT_CROSS))
-
-
-_ALG_TWOPASS_PARAMS = 0x10000000  # ASW_ALG_TWOPASS_PARAMS
+    return _pack(_ALG_ADCENSUS_PARAMS | int(_A.ADAPTIVE_WEIGHT_CROSS), {"tau": tau, "lambda_ad": lambda_ad, "lambda_census": lambda_census},
+                 spoil=("lambda_ad",))
 
 
 def twopass_algorithm(gamma_c=30, gamma_g=20):
     """asw_alg_twopass of asw_mi355x.h: the value of `algorithmType` that runs ADAPTIVE_WEIGHT as the two-pass (separable)
     approximation with the integer gammas gamma_c and gamma_g (1..255 each) in every call that takes an
     algorithm; an argument out of range gives a value the library refuses with ERR_BAD_ARGUMENT (that gamma's field 0)."""
-    gamma_c, gamma_g = int(gamma_c), int(gamma_g)
-    c = 0 if (gamma_c < 1 or gamma_c > 255) else gamma_c
-    g = 0 if (gamma_g < 1 or gamma_g > 255) else gamma_g
-    return _ALG_TWOPASS_PARAMS | (g << 16) | (c << 8) | int(StereoMatchingAlgorithms.ADAPTIVE_WEIGHT)
-
-
-_ALG_PERMEABILITY_PARAMS = 0x08000000  # ASW_ALG_PERMEABILITY_PARAMS
+    return _pack(_ALG_TWOPASS_PARAMS | int(_A.ADAPTIVE_WEIGHT), {"gamma_c": gamma_c, "gamma_g": gamma_g})
 
 
 def permeability_algorithm(sigma=8, trunc=20):
     """asw_alg_permeability of asw_mi355x.h: the value of `algorithmType` that runs ADAPTIVE_WEIGHT_CROSS as the recursive
     (permeability) aggregation over the whole image with the integers sigma and trunc (1..255 each) in every
     call that takes an algorithm; an argument out of range gives a value the library refuses with ERR_BAD_ARGUMENT (that field 0)."""
-    sigma, trunc = int(sigma), int(trunc)
-    s = 0 if (sigma < 1 or sigma > 255) else sigma
-    t = 0 if (trunc < 1 or trunc > 255) else trunc
-    return _ALG_PERMEABILITY_PARAMS | (t << 16) | (s << 8) | int(StereoMatchingAlgorithms.ADAPTIVE_WEIGHT_CROSS)
-
-
-CROSS_SCALE = 0x1000  # ASW_DISPARITY_CROSS_SCALE
+    return _pack(_ALG_PERMEABILITY_PARAMS | int(_A.ADAPTIVE_WEIGHT_CROSS), {"sigma": sigma, "trunc": trunc})
 
 
 def cross_scale(scales=3, lambda_q=19):
@@ -139,12 +145,7 @@ def cross_scale(scales=3, lambda_q=19):
     exists) that runs the method on `scales` (2..5) levels of a 2x2-mean pyramid and takes the winner of the regularised finest-scale
     volume, lambda = lambda_q / 64 with lambda_q in 1..255; an argument out of range gives a value the
     library refuses with ERR_BAD_ARGUMENT (scales field 0)."""
-    scales, lambda_q = int(scales), int(lambda_q)
-    bad = scales < 2 or scales > 5 or lambda_q < 1 or lambda_q > 255
-    return CROSS_SCALE | ((0 if bad else scales) << 13) | ((lambda_q & 0xFF) << 16)
-
-
-SCANLINE = 0x01000000  # ASW_DISPARITY_SCANLINE
+    return _pack(CROSS_SCALE, {"scales": scales, "lambda_q": lambda_q}, spoil=("scales",))
 
 
 def scanline(p1_code=8, unit_code=5, p2_ratio=4):
@@ -152,18 +153,15 @@ def scanline(p1_code=8, unit_code=5, p2_ratio=4):
     exists) that regularises the method's aggregated volume along four scan paths and takes the winner of the result (DESIGN.md
     section 4.19): P1 = p1_code * 4 ** (unit_code - 5), P2 = p2_ratio * P1, p1_code in 1..127, unit_code in 0..7, p2_ratio in 1..8;
     an argument out of range gives the flag alone, which the library refuses with ERR_BAD_ARGUMENT."""
-    a, u, r = int(p1_code), int(unit_code), int(p2_ratio)
-    if a < 1 or a > 127 or u < 0 or u > 7 or r < 1 or r > 8:
-        return SCANLINE
-    return SCANLINE | (a << 1) | (u << 25) | ((r - 1) << 28)
+    return _pack(SCANLINE, {"p1_code": p1_code, "unit_code": unit_code, "p2_ratio - 1": int(p2_ratio) - 1},
+                 spoil=("p1_code", "unit_code", "p2_ratio - 1"))
 
 
 def scanline_penalties(value):
     """(P1, P2) of a scanline() value, as the f32 numbers the library adds"""
-    value = int(value)
-    a, u, r = (value >> 1) & 0x7F, (value >> 25) & 7, ((value >> 28) & 7) + 1
+    a, u, r1 = _unpack(value, "p1_code", "unit_code", "p2_ratio - 1")
     unit = 4.0 ** (u - 5)
-    return np.float32(a * unit), np.float32(r * a * unit)
+    return np.float32(a * unit), np.float32((r1 + 1) * a * unit)
 
 
 def _disparity_type(disparityType, subpixel, cross_scale, scanline):

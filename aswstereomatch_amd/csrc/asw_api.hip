@@ -37,44 +37,9 @@ int match_host(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_
     return ASW_OK;
 }
 
-int decode_algorithm(int algorithm, int* method, MatchParams* mp)
-{
-    *method = algorithm;
-    if (!(algorithm & (ASW_ALG_CROSS_PARAMS | ASW_ALG_ADCENSUS_PARAMS | ASW_ALG_TWOPASS_PARAMS | ASW_ALG_PERMEABILITY_PARAMS))) return ASW_OK;
-    if (!(algorithm & (ASW_ALG_CROSS_PARAMS | ASW_ALG_ADCENSUS_PARAMS | ASW_ALG_TWOPASS_PARAMS))) {  // asw_alg_permeability(): bit 27 alone of the four
-        if ((algorithm & 0xFF) != ASW_ALG_ADAPTIVE_WEIGHT_CROSS) return ASW_ERR_UNSUPPORTED_METHOD;
-        const int sigma = (algorithm >> 8) & 0xFF, trunc = (algorithm >> 16) & 0xFF;  // bits 24..26 and 31 stay clear
-        if (sigma == 0 || trunc == 0 || (algorithm & 0x07000000) || algorithm < 0) return ASW_ERR_BAD_ARGUMENT;
-        if (mp) { mp->permeability = 1; mp->perm_sigma = sigma; mp->perm_trunc = trunc; }
-        *method = ASW_ALG_ADAPTIVE_WEIGHT_CROSS;
-        return ASW_OK;
-    }
-    if (!(algorithm & (ASW_ALG_CROSS_PARAMS | ASW_ALG_ADCENSUS_PARAMS))) {  // asw_alg_twopass(): bit 28 is adcensus's lambda_ad otherwise
-        if ((algorithm & 0xFF) != ASW_ALG_ADAPTIVE_WEIGHT) return ASW_ERR_UNSUPPORTED_METHOD;
-        const int gamma_c = (algorithm >> 8) & 0xFF, gamma_g = (algorithm >> 16) & 0xFF;  // bits 24..27 and 31 stay clear
-        if (gamma_c == 0 || gamma_g == 0 || (algorithm & 0x0F000000) || algorithm < 0) return ASW_ERR_BAD_ARGUMENT;
-        if (mp) { mp->twopass = 1; mp->gamma_c = gamma_c; mp->gamma_g = gamma_g; }
-        *method = ASW_ALG_ADAPTIVE_WEIGHT;
-        return ASW_OK;
-    }
-    const MethodInfo* m = method_info(algorithm & 0xFF);
-    if (!m || !m->packed_params) return ASW_ERR_UNSUPPORTED_METHOD;
-    const int tau = (algorithm >> 8) & 0xFF, f16 = (algorithm >> 16) & 0xFF;
-    if (algorithm & ASW_ALG_CROSS_PARAMS) {  // asw_alg_cross(): bits 16..23 = trunc, bits 24..29 and 31 stay clear
-        if (f16 == 0 || (algorithm & 0x3F000000) || algorithm < 0) return ASW_ERR_BAD_ARGUMENT;
-        if (mp) { mp->cross_tau = tau; mp->cross_trunc = f16; }
-    } else {  // asw_alg_adcensus(): bits 16..23 = lambda_census, bits 24..28 = lambda_ad, bit 31 stays clear
-        const int lambda_ad = (algorithm >> 24) & 0x1F;
-        if (f16 == 0 || lambda_ad == 0 || algorithm < 0) return ASW_ERR_BAD_ARGUMENT;
-        if (mp) { mp->cross_cost = 1; mp->cross_tau = tau; mp->cross_trunc = 255; mp->lambda_ad = lambda_ad; mp->lambda_census = f16; }
-    }
-    *method = m->algorithm;
-    return ASW_OK;
-}
-
 extern "C" int asw_volume_planes(int algorithm, int num_disparity)
 {
-    if (decode_algorithm(algorithm, &algorithm, nullptr) != ASW_OK) return 0;
+    if (decode_algorithm(algorithm, &algorithm, nullptr, method_info) != ASW_OK) return 0;
     const MethodInfo* m = method_info(algorithm);
     return m ? m->planes(num_disparity) : 0;
 }

@@ -2,10 +2,12 @@
 //   asw_context.hip  context, frame slots, host <-> HBM plumbing, pre/post-processing entry points
 //   asw_methods.hip  the method table, the method runners (tables, scratch, launch sequences) and the selector
 //   asw_api.hip      the per-method / cost-builder / building-block entry points of include/asw_mi355x.h
+// MatchParams, MethodTraits and the decoding of the selector's two packed words live in asw_selector.h, which needs no HIP.
 #pragma once
 #include <type_traits>
 
 #include "asw_internal.h"
+#include "asw_selector.h"
 
 #define ASW_TRY(expr)                  \
     do {                               \
@@ -29,51 +31,15 @@ int dispatch_npl(int D, F&& f)
     return ASW_ERR_BAD_ARGUMENT;
 }
 
-struct MatchParams {
-    int disparity_type, win, minD, numD;  // disparity_type as the caller passed it; run_method strips the sub-pixel flag into `subpixel`
-    int subpixel = 0;                   // 0 | ASW_DISPARITY_SUBPIXEL_PARABOLA | ASW_DISPARITY_SUBPIXEL_EQUIANGULAR
-    int cross_scales = 0, cross_lambda_q = 0;  // asw_disparity_cross_scale() fields, stripped like the sub-pixel flag: 0 = one scale, else 2..5 and 1..255
-    float scan_p1 = 0, scan_p2 = 0;     // asw_disparity_scanline() penalties, stripped like the cross-scale fields: scan_p1 == 0 = no scanline optimisation
-    double gamma_c = 30, gamma_g = 20;  // M.cpp:58
-    int twopass = 0;                    // entry 2 as the two-pass approximation (asw_alg_twopass()): the gammas above are its integers
-    double eps = 1e-6;                  // M.cpp:73,76
-    double rate_s = 10, rate_r = 10;    // M.cpp:82
-    double blo_rate_r = 0.015;          // M.cpp:70
-    double grid_rate_s = 10, grid_rate_r = 10;  // M.cpp:67
-    int cross_tau = 20, cross_trunc = 20;       // ASW_ALG_ADAPTIVE_WEIGHT_CROSS; an encoded selector value replaces them
-    int cross_cost = 0;                         // the cost entry 12 aggregates: 0 = truncated AD, 1 = AD-Census (asw_alg_adcensus())
-    int lambda_ad = 10, lambda_census = 30;     // AD-Census: the two table constants
-    int permeability = 0;                       // entry 12 as the recursive (permeability) aggregation (asw_alg_permeability())
-    int perm_sigma = 8, perm_trunc = 20;        // its two parameters, 1..255 each
-};
-inline MatchParams match_params(int disparity_type, int win, int minD, int numD)
-{
-    MatchParams mp;
-    mp.disparity_type = disparity_type; mp.win = win; mp.minD = minD; mp.numD = numD;
-    return mp;
-}
-
 // One row per selector value (asw_methods.hip: k_methods).  Everything the host layer knows about a method beyond its runner is a
-// field here: asw_volume_planes, run_method, match_host, the sub-pixel decoding and match_refined read the row, the runners of the
-// inclusive ranges take their candidate count from it.
-struct MethodInfo {
-    int algorithm;     // the ASW_ALG_* value == the row's index
-    int extra_planes;  // candidates / volume planes = numD + extra_planes: 1 where the reference's range is inclusive (offset <= max_offset)
+// field of MethodTraits: asw_volume_planes, run_method, match_host, the word decoders and match_refined read the row, the runners
+// of the inclusive ranges take their candidate count from it.
+struct MethodInfo : MethodTraits {
+    int algorithm;  // the ASW_ALG_* value == the row's index
     int (*run)(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_volume);  // null: the selector does not serve the value
-    bool no_volume;               // no selector volume (0 planes), hence no sub-pixel step and no refinement either
-    bool ignores_disparity_type;  // whatever disparity_type holds, sub-pixel flags included, is not looked at
-    bool no_subpixel;             // a sub-pixel flag is refused with ASW_ERR_UNSUPPORTED_METHOD
-    bool packed_params;           // the selector value may carry the method's parameters (asw_alg_cross(), asw_alg_adcensus())
-    int planes(int numD) const { return no_volume ? 0 : numD + extra_planes; }
 };
 const MethodInfo* method_info(int method);  // the row of a plain (decoded) selector value; null for a value outside the table
 
-// The selector's `algorithm` as a caller passes it -> the plain enum value in *method and, for an asw_alg_cross() or
-// asw_alg_adcensus() value, its parameters in mp's cross_* / lambda_* fields, for an asw_alg_twopass() value mp's twopass flag and
-// gammas, for an asw_alg_permeability() value mp's permeability flag, sigma and trunc (left alone otherwise; mp may be null).
-// ASW_ERR_UNSUPPORTED_METHOD / ASW_ERR_BAD_ARGUMENT for the encodings asw_mi355x.h refuses; a value with none of
-// ASW_ALG_CROSS_PARAMS, ASW_ALG_ADCENSUS_PARAMS, ASW_ALG_TWOPASS_PARAMS and ASW_ALG_PERMEABILITY_PARAMS passes through as it is.
-int decode_algorithm(int algorithm, int* method, MatchParams* mp);
 // AD-Census cost of a device pair into cost u8 [numD][H][W]: gray pair, two census transforms, then the
 // Hamming distance alone (lambda_ad = 0) or TA[AD] + TC[Hamming] with the tables of the two lambdas (each 1..255)
 int build_census_cost(asw_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int H, int W, int channels, int disparity_type, int minD,

@@ -1010,77 +1010,27 @@ static int run_cross(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_vo
 // runner above and its enum value in asw_mi355x.h.
 // ------------------------------------------------------------------------------------------
 static const MethodInfo k_methods[] = {
-    // algorithm, extra planes, runner, no volume, ignores disparity_type, no sub-pixel, packed parameters
-    {ASW_ALG_BM, 0, nullptr, true, true, false, false},     // served by asw_stereo_bm / asw_get_disparity_bm only
-    {ASW_ALG_SGBM, 0, run_sgbm, true, true, false, false},  // asw_sgbm has the volume S
-    {ASW_ALG_ADAPTIVE_WEIGHT, 1, run_bilateral_classic, false, false, false, false},  // offset <= max_offset, M.cpp:1021,1074
-    {ASW_ALG_ADAPTIVE_WEIGHT_8DIRECT, 1, run_direct8, false, false, false, false},    // M.cpp:1171
-    {ASW_ALG_ADAPTIVE_WEIGHT_GEODESIC, 1, run_geodesic, false, false, false, false},  // M.cpp:1447,1467
-    {ASW_ALG_ADAPTIVE_WEIGHT_BILATERAL_GRID, 1, run_bilgrid, false, false, false, false},  // M.cpp:2256,2280
-    {ASW_ALG_ADAPTIVE_WEIGHT_BLO1, 0, run_blo1, false, false, false, false},
-    {ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER, 0, run_guided_sad6, false, false, false, false},
-    {ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER_2, 0, run_guided_sim3, false, false, false, false},
-    {ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER_3, 0, run_guided_ncc, false, false, false, false},
-    {ASW_ALG_ADAPTIVE_WEIGHT_MEDIAN, 0, run_wmedian, false, false, false, false},
+    // {extra planes, no volume, ignores disparity_type, no sub-pixel, packed parameters}, algorithm, runner
+    {{0, true, true, false, false}, ASW_ALG_BM, nullptr},     // served by asw_stereo_bm / asw_get_disparity_bm only
+    {{0, true, true, false, false}, ASW_ALG_SGBM, run_sgbm},  // asw_sgbm has the volume S
+    {{1, false, false, false, false}, ASW_ALG_ADAPTIVE_WEIGHT, run_bilateral_classic},  // offset <= max_offset, M.cpp:1021,1074
+    {{1, false, false, false, false}, ASW_ALG_ADAPTIVE_WEIGHT_8DIRECT, run_direct8},    // M.cpp:1171
+    {{1, false, false, false, false}, ASW_ALG_ADAPTIVE_WEIGHT_GEODESIC, run_geodesic},  // M.cpp:1447,1467
+    {{1, false, false, false, false}, ASW_ALG_ADAPTIVE_WEIGHT_BILATERAL_GRID, run_bilgrid},  // M.cpp:2256,2280
+    {{0, false, false, false, false}, ASW_ALG_ADAPTIVE_WEIGHT_BLO1, run_blo1},
+    {{0, false, false, false, false}, ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER, run_guided_sad6},
+    {{0, false, false, false, false}, ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER_2, run_guided_sim3},
+    {{0, false, false, false, false}, ASW_ALG_ADAPTIVE_WEIGHT_GUIDED_FILTER_3, run_guided_ncc},
+    {{0, false, false, false, false}, ASW_ALG_ADAPTIVE_WEIGHT_MEDIAN, run_wmedian},
     // computeNCC's disparity overload has its own candidate range and no selector volume in the RIGHT view
-    {ASW_ALG_NCC, 0, run_ncc, false, false, true, false},
-    {ASW_ALG_ADAPTIVE_WEIGHT_CROSS, 0, run_cross, false, false, false, true},
+    {{0, false, false, true, false}, ASW_ALG_NCC, run_ncc},
+    {{0, false, false, false, true}, ASW_ALG_ADAPTIVE_WEIGHT_CROSS, run_cross},
 };
 
 const MethodInfo* method_info(int method)
 {
     const int n = (int)(sizeof(k_methods) / sizeof(k_methods[0]));
     return method >= 0 && method < n && k_methods[method].algorithm == method ? &k_methods[method] : nullptr;
-}
-
-// Sub-pixel flags of a caller's disparity_type -> mp.subpixel, mp.disparity_type without them.  A value
-// without a flag bit passes through as it is: the methods refuse what they refused before, with the statuses they had.
-static int decode_subpixel(const MethodInfo* m, MatchParams& mp)
-{
-    const int flags = ASW_DISPARITY_SUBPIXEL_PARABOLA | ASW_DISPARITY_SUBPIXEL_EQUIANGULAR;
-    mp.subpixel = 0;
-    if ((m && m->ignores_disparity_type) || !(mp.disparity_type & flags)) return ASW_OK;
-    if ((mp.disparity_type & flags) == flags) return ASW_ERR_BAD_ARGUMENT;
-    if (mp.disparity_type & ~(flags | ASW_DISPARITY_RIGHT)) return ASW_ERR_BAD_ARGUMENT;
-    if (m && m->no_subpixel) return ASW_ERR_UNSUPPORTED_METHOD;
-    mp.subpixel = mp.disparity_type & flags;
-    mp.disparity_type &= ~flags;
-    return ASW_OK;
-}
-
-// Cross-scale fields of a caller's disparity_type -> mp.cross_scales / mp.cross_lambda_q, mp.disparity_type
-// without them (decode_subpixel sees the rest).  A value with bit 12 clear passes through as it is, whatever its other bits hold.
-static int decode_cross_scale(const MethodInfo* m, MatchParams& mp)
-{
-    const int sub = ASW_DISPARITY_SUBPIXEL_PARABOLA | ASW_DISPARITY_SUBPIXEL_EQUIANGULAR, fields = 0x00FFF000;
-    mp.cross_scales = mp.cross_lambda_q = 0;
-    if ((m && m->ignores_disparity_type) || !(mp.disparity_type & ASW_DISPARITY_CROSS_SCALE)) return ASW_OK;
-    const int S = (mp.disparity_type >> 13) & 7, q = (mp.disparity_type >> 16) & 0xFF;
-    if (mp.disparity_type & ~(fields | sub | ASW_DISPARITY_RIGHT)) return ASW_ERR_BAD_ARGUMENT;
-    if (S < 2 || S > CROSS_SCALE_MAX || q == 0 || (mp.disparity_type & sub) == sub) return ASW_ERR_BAD_ARGUMENT;
-    if (m && m->no_subpixel) return ASW_ERR_UNSUPPORTED_METHOD;  // NCC: its candidate range is its own
-    mp.cross_scales = S; mp.cross_lambda_q = q;
-    mp.disparity_type &= ~fields;
-    return ASW_OK;
-}
-
-// Scanline fields of a caller's disparity_type -> mp.scan_p1 / mp.scan_p2, mp.disparity_type without them.  A
-// value with bit 24 clear passes through as it is: decode_cross_scale and the methods refuse what they refused before.
-static int decode_scanline(const MethodInfo* m, MatchParams& mp)
-{
-    const int sub = ASW_DISPARITY_SUBPIXEL_PARABOLA | ASW_DISPARITY_SUBPIXEL_EQUIANGULAR, fields = 0x7F0000FE;
-    mp.scan_p1 = mp.scan_p2 = 0;
-    if ((m && m->ignores_disparity_type) || !(mp.disparity_type & ASW_DISPARITY_SCANLINE)) return ASW_OK;
-    if (mp.disparity_type & ASW_DISPARITY_CROSS_SCALE) return ASW_ERR_BAD_ARGUMENT;  // the two together: not served
-    const int a = (mp.disparity_type >> 1) & 0x7F, u = (mp.disparity_type >> 25) & 7, ratio = ((mp.disparity_type >> 28) & 7) + 1;
-    if (mp.disparity_type & ~(fields | sub | ASW_DISPARITY_RIGHT)) return ASW_ERR_BAD_ARGUMENT;
-    if (a == 0 || (mp.disparity_type & sub) == sub) return ASW_ERR_BAD_ARGUMENT;
-    if (!m || !m->run || m->no_volume || m->no_subpixel) return ASW_ERR_UNSUPPORTED_METHOD;  // NCC: its candidate range is its own
-    if (m->planes(mp.numD) > scanline_max_planes()) return ASW_ERR_BAD_ARGUMENT;
-    const float unit = ldexpf(1.0f, 2 * (u - 5));  // 4^(u - 5): a * unit and ratio * a * unit are exact
-    mp.scan_p1 = (float)a * unit; mp.scan_p2 = (float)(ratio * a) * unit;
-    mp.disparity_type &= ~fields;
-    return ASW_OK;
 }
 
 // The four paths over the runner's volume, their sum over it, and its winner (k_scanline.hip)
@@ -1096,19 +1046,12 @@ static int run_scanline(asw_ctx* ctx, Frame* f, const MethodInfo* m, const Match
     return launch_scanline(ctx->stream, a);
 }
 
-// level s of a cross-scale call: candidates (minD >> s) .. ((minD + n - 1) >> s), n the finest level's plane count
-static void cross_scale_range(const MethodInfo* m, const MatchParams& mp, int s, int* minD, int* numD)
-{
-    const long long last = (long long)mp.minD + mp.numD + m->extra_planes - 1;  // minD + n - 1, n = m->planes(numD); no int overflow
-    *minD = mp.minD >> s;
-    *numD = (int)((last >> s) - *minD + 1 - m->extra_planes);
-}
-
 // The method on every level of the pair's 2x2-mean pyramid, coarsest first, then the combination of the levels' volumes and its
 // winner (k_cross_scale.hip).  Everything goes on the context's stream; the coarse pairs and volumes live in ctx->coarse, the
 // runners' named scratch is reused level after level.  The finest level runs last: ev[2] / ev[3] stay on it.
 static int run_cross_scale(asw_ctx* ctx, Frame* f, const MethodInfo* m, const MatchParams& mp, bool store)
 {
+    static_assert(DT_CROSS_SCALES.hi == CROSS_SCALE_MAX, "the levels decode_disparity_type accepts are those ctx->coarse holds");
     const int S = mp.cross_scales;
     CrossScaleLaunch a;
     const Frame* src = f;
@@ -1143,19 +1086,9 @@ int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp_in, 
     f->invalidate_results();  // whatever the slot's disparity / volume were, they are not this call's
     MatchParams mp = mp_in;
     if (mp.numD <= 0 || mp.minD < 0) return ASW_ERR_BAD_ARGUMENT;
-    ASW_TRY(decode_algorithm(algorithm, &algorithm, &mp));  // asw_alg_cross() / asw_alg_adcensus() values -> 12 + parameters
+    ASW_TRY(decode_algorithm(algorithm, &algorithm, &mp, method_info));  // an asw_alg_*() value -> the plain one + its parameters
     const MethodInfo* m = method_info(algorithm);
-    ASW_TRY(decode_scanline(m, mp));
-    ASW_TRY(decode_cross_scale(m, mp));
-    ASW_TRY(decode_subpixel(m, mp));
-    if (mp.cross_scales) {  // the flag's last rule, still before any work: every level keeps at least one candidate for the runner
-        if (!m || !m->run || m->no_volume) return ASW_ERR_UNSUPPORTED_METHOD;
-        for (int s = 1; s < mp.cross_scales; s++) {
-            int minD_s, numD_s;
-            cross_scale_range(m, mp, s, &minD_s, &numD_s);
-            if (numD_s < 1) return ASW_ERR_BAD_ARGUMENT;
-        }
-    }
+    ASW_TRY(decode_disparity_type(m, m && m->run, scanline_max_planes(), mp));  // the flags: every refusal before any work
     // the sub-pixel kernel reads the aggregated volume: the methods that can skip it (bilateral / direct8, geodesic, BLO1, the
     // bilateral grid) are asked for it; what the CALLER keeps is decided below
     const bool want_volume = keep_volume || mp.subpixel != 0 || mp.scan_p1 != 0;
@@ -1263,7 +1196,7 @@ int match_refined(asw_ctx* ctx, Frame* f, int algorithm, int win_size, int min_d
     if (m && m->no_volume) return ASW_ERR_UNSUPPORTED_METHOD;  // SGBM / BM carry their own disp12MaxDiff
     if (num_disparity <= 0 || min_disparity < 0) return ASW_ERR_BAD_ARGUMENT;  // as a plain match (run_method)
     int plain;  // unused: a bad asw_alg_cross() / asw_alg_adcensus() value is refused here with its own status, as a plain match refuses it
-    ASW_TRY(decode_algorithm(algorithm, &plain, nullptr));
+    ASW_TRY(decode_algorithm(algorithm, &plain, nullptr, method_info));
     RefineParams rp;
     rp.minD = min_disparity; rp.n = asw_volume_planes(algorithm, num_disparity); rp.max_diff = max_diff; rp.win = refine_win;
     rp.gamma_c = gamma_c; rp.gamma_s = gamma_s;
