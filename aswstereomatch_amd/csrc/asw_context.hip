@@ -20,31 +20,6 @@ void asw_note_hip_error(hipError_t e, const char* what, const char* file, int li
         fprintf(stderr, "[asw_mi355x] HIP error %d (%s) at %s:%d in %s\n", (int)e, hipGetErrorString(e), file, line, what);
 }
 
-int DevBuf::ensure(size_t bytes)
-{
-    if (bytes <= cap && p) return ASW_OK;
-    if (p) {
-        (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    size_t want = bytes < 256 ? 256 : bytes;
-    if (hipMalloc(&p, want) != hipSuccess) {
-        p = nullptr;
-        return ASW_ERR_ALLOC;
-    }
-    cap = want;
-    return ASW_OK;
-}
-
-void DevBuf::release()
-{
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-}
-
-
 extern "C" const char* asw_status_string(int status)
 {
     switch (status) {
@@ -112,7 +87,7 @@ extern "C" int asw_create(int device_id, asw_ctx** out)
     for (int i = 0; i < 2; i++) ok = ok && hipStreamCreateWithFlags(&c->aux[i], hipStreamNonBlocking) == hipSuccess;
     for (int i = 0; i < 3; i++) ok = ok && hipEventCreateWithFlags(&c->aux_ev[i], hipEventDisableTiming) == hipSuccess;
     if (!ok) {
-        asw_destroy(c);
+        delete c;
         return ASW_ERR_HIP;
     }
     *out = c;
@@ -121,36 +96,6 @@ extern "C" int asw_create(int device_id, asw_ctx** out)
 
 extern "C" void asw_destroy(asw_ctx* ctx)
 {
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    for (auto& f : ctx->frames) {
-        f.L.release(); f.R.release(); f.disp.release(); f.vol.release();
-    }
-    ctx->host_frame.L.release(); ctx->host_frame.R.release(); ctx->host_frame.disp.release(); ctx->host_frame.vol.release();
-    for (auto& f : ctx->coarse) {
-        f.L.release(); f.R.release(); f.disp.release(); f.vol.release();
-    }
-    for (auto& kv : ctx->scratch) kv.second.release();
-    ctx->bil.taps.release();
-    ctx->bil.lut.release();
-    ctx->bil.cells.release();
-    ctx->refine.tc.release();
-    ctx->refine.ts.release();
-    ctx->twopass.t.release();
-    ctx->perm.t.release();
-    ctx->wm_lut2.release();
-    ctx->wm_wd.release();
-    for (int i = 0; i < 4; i++)
-        if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
-    for (int i = 0; i < 3; i++)
-        if (ctx->aux_ev[i]) (void)hipEventDestroy(ctx->aux_ev[i]);
-    for (int i = 0; i < 2; i++)
-        if (ctx->aux[i]) {
-            (void)hipStreamSynchronize(ctx->aux[i]);
-            (void)hipStreamDestroy(ctx->aux[i]);
-        }
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
 
@@ -281,8 +226,8 @@ extern "C" int asw_upload_pair(asw_ctx* ctx, int slot, const asw_image* left, co
 // ------------------------------------------------------------------------------------------
 static int ensure_prep_tables(asw_ctx* ctx)
 {
-    DevBuf& t = ctx->buf("prep_tables");
-    if (t.p) return ASW_OK;
+    PrepTables& t = ctx->prep;
+    if (t.cache.hit(0, ctx->stream)) return ASW_OK;
     // [0..255] sdiv, [256..511] hdiv (RGB2HSV_b, hsv_shift = 12), then the bilateralFilter(d=7, sigmaColor=10,
     // sigmaSpace=3) tables of main.cpp:76: 256 colour weights (f32 bits), tap count, taps {dy, dx, weight bits}
     std::vector<int> h(512 + 256 + 1 + 3 * 64, 0);
@@ -308,11 +253,9 @@ static int ensure_prep_tables(asw_ctx* ctx)
             n++;
         }
     h[768] = n;
-    ctx->prep_ntaps = n;
-    ASW_TRY(t.ensure(h.size() * sizeof(int)));
-    ASW_HIP_TRY(hipMemcpyAsync(t.p, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return ASW_OK;
+    t.ntaps = n;
+    ASW_TRY(t.cache.upload(t.t, h.data(), h.size() * sizeof(int)));
+    return t.cache.commit(0);
 }
 
 static int prep_one(asw_ctx* ctx, const asw_image* full, int out_w, int out_h, int boost, DevBuf& dst)
@@ -327,10 +270,10 @@ static int prep_one(asw_ctx* ctx, const asw_image* full, int out_w, int out_h, i
     uint8_t* resized = boost ? small.as<uint8_t>() : dst.as<uint8_t>();
     ASW_TRY(launch_resize_linear(ctx->stream, stage.as<uint8_t>(), full->rows, full->cols, resized, out_h, out_w));
     if (boost) {
-        const int* tab = ctx->buf("prep_tables").as<int>();
+        const int* tab = ctx->prep.t.as<int>();
         ASW_TRY(hsv.ensure(n * 3));
         ASW_TRY(launch_bgr2hsv(ctx->stream, resized, n, tab, tab + 256, hsv.as<uint8_t>()));
-        ASW_TRY(launch_boost_hsv2bgr(ctx->stream, hsv.as<uint8_t>(), out_h, out_w, tab + 769, ctx->prep_ntaps,
+        ASW_TRY(launch_boost_hsv2bgr(ctx->stream, hsv.as<uint8_t>(), out_h, out_w, tab + 769, ctx->prep.ntaps,
                                      reinterpret_cast<const float*>(tab + 512), dst.as<uint8_t>()));
     }
     return ASW_OK;

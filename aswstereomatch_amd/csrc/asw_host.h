@@ -9,12 +9,6 @@
 #include "asw_internal.h"
 #include "asw_selector.h"
 
-#define ASW_TRY(expr)                  \
-    do {                               \
-        int _rc = (expr);              \
-        if (_rc != ASW_OK) return _rc; \
-    } while (0)
-
 inline unsigned blocks(size_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 
 // Kernels that keep D candidates in the lanes of one wavefront (k = c * 64 + lane) are templates on the candidates per lane:

@@ -6,29 +6,34 @@
 
 #include <map>
 #include <string>
+#include <tuple>
 #include <vector>
 
-#include "../../include/asw_mi355x.h"
+#include "asw_devmem.h"
 
-#define ASW_HIP_TRY(expr)                                  \
-    do {                                                   \
-        hipError_t _e = (expr);                            \
-        if (_e != hipSuccess) {                            \
-            asw_note_hip_error(_e, #expr, __FILE__, __LINE__); \
-            return ASW_ERR_HIP;                            \
-        }                                                  \
-    } while (0)
-
-void asw_note_hip_error(hipError_t e, const char* what, const char* file, int line);
-
-// Grow-only device buffer.
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes);
-    void release();
-    template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
-};
+// The one way a kernel is launched: ASW_LAUNCH(kernel, grid, block, dynamic LDS bytes, stream, arguments...) gives an asw_status.
+//   - more than 160 KB of dynamic LDS (a workgroup's whole share on gfx950): ASW_ERR_BAD_ARGUMENT, nothing is launched;
+//   - more than 64 KB: the kernel is opted in first, on every such launch -- the attribute is per device, a process may hold
+//     contexts on several devices, and a function-local flag would leave every device after the first at the 64 KB default;
+//   - then the launch, then hipGetLastError: a refused launch is reported at its own site and nothing is enqueued behind it.
+// A kernel name with a comma in it goes in parentheses, as for any macro.
+template <typename K, typename... Args>
+int asw_launch_at(const char* what, const char* file, int line, K kern, dim3 grid, dim3 block, size_t lds, hipStream_t s,
+                  const Args&... args)
+{
+    if (lds > 160 * 1024) return ASW_ERR_BAD_ARGUMENT;
+    hipError_t e = hipSuccess;
+    if (lds > 64 * 1024)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(kern, grid, block, lds, s, args...);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) return ASW_OK;
+    asw_note_hip_error(e, what, file, line);
+    return ASW_ERR_HIP;
+}
+#define ASW_LAUNCH(kern, ...) asw_launch_at(#kern, __FILE__, __LINE__, kern, __VA_ARGS__)
 
 struct Frame {
     DevBuf L, R;  // dense interleaved 8U images as uploaded
@@ -45,11 +50,10 @@ struct Frame {
     void invalidate_results() { has_disp = false; disp_rows = disp_cols = 0; vol_floats = 0; }
 };
 
-struct BilateralTables {  // cached per (kind, win, gamma_c, gamma_g, mirror)
-    int kind = -1;  // 0: classic (all win*win-1 taps, transposed consume order), 1: direct8 (row + column + diagonal)
-    int win = 0;
-    int mirror = -1;
-    double gamma_c = 0, gamma_g = 0;
+struct BilateralTables {
+    // (kind, win, gamma_c, gamma_g, mirror); kind 0: classic (all win*win-1 taps, transposed consume order), 1: direct8 (row +
+    // column + diagonal)
+    TableCache<std::tuple<int, int, double, double, int>> cache;
     int ntaps = 0, ncls = 0;
     DevBuf taps;  // int4 per tap
     DevBuf lut;   // float [ncls][256]
@@ -81,22 +85,39 @@ struct AswTuning {
 // the name of AswTuning::perm_chunk's switch
 constexpr char ASW_PERM_CHUNK_NAME[] = "ASW_PERM_CHUNK";
 
-struct RefineTables {  // cached per (win, gamma_c, gamma_s, channels): integer weights of the refinement's median (k_refine.hip)
-    int win = 0, channels = 0;
-    double gamma_c = 0, gamma_s = 0;
+struct RefineTables {  // integer weights of the refinement's median (k_refine.hip)
+    TableCache<std::tuple<int, double, double, int>> cache;  // (win, gamma_c, gamma_s, channels)
     int ntc = 0;
     DevBuf tc;  // u32 [255 * channels + 1]: floor(4096 * exp(-c / gamma_c) + 0.5)
     DevBuf ts;  // u32 [win/2 + 1][win/2 + 1]: floor(256 * exp(-sqrt(i*i + j*j) / gamma_s) + 0.5)
 };
 
-struct TwoPassTable {  // cached per (win, gamma_c, gamma_g): the weight table of the two-pass method (k_twopass.hip)
-    int win = 0, gamma_c = 0, gamma_g = 0;
+struct TwoPassTable {  // the weight table of the two-pass method (k_twopass.hip)
+    TableCache<std::tuple<int, int, int>> cache;  // (win, gamma_c, gamma_g)
     DevBuf t;  // float [win / 2 + 1][256]: (float)exp(-(dc / gamma_c + r / gamma_g))
 };
 
-struct PermTable {  // cached per sigma: the permeability table of k_permeability.hip
-    int sigma = 0;
+struct PermTable {  // the permeability table of k_permeability.hip
+    TableCache<int> cache;  // sigma
     DevBuf t;  // double [256]: (double)(float)exp(-(double)k / sigma)
+};
+
+struct CensusTables {  // the AD-Census cost tables (asw_methods.hip: ensure_census_tables)
+    TableCache<std::tuple<int, int>> cache;  // (lambda_ad, lambda_census)
+    DevBuf t;  // u8 TA[256] | TC[64]
+};
+
+struct WMedianTables {  // weighted-median tables, two independent entries
+    TableCache<double> lut2_cache;  // rateR
+    DevBuf lut2;  // exp() LUT of the colour weight
+    TableCache<std::tuple<double, int>> wd_cache;  // (rateS, win)
+    DevBuf wd;    // space kernel
+};
+
+struct PrepTables {  // tables of the pre-processing entry points (asw_context.hip: ensure_prep_tables): they have no parameter
+    TableCache<int> cache;
+    int ntaps = 0;  // taps of the bilateral filter
+    DevBuf t;
 };
 
 constexpr int CROSS_SCALE_MAX = 5;  // most pyramid levels of a cross-scale call, the finest included
@@ -104,7 +125,6 @@ constexpr int CROSS_SCALE_MAX = 5;  // most pyramid levels of a cross-scale call
 struct asw_ctx {
     int device = 0;
     AswTuning tune;
-    int prep_ntaps = 0;  // taps of the pre-processing bilateral filter (tables in buf("prep_tables"))
     int gray_bits = 14;  // cvtColor(BGR2GRAY) constant set (asw_set_gray_bits): 14 = OpenCV 4.1.0, 15 = later 4.x
     hipStream_t stream = nullptr;
     std::vector<Frame> frames;  // resident slots of asw_upload_pair / asw_match_resident (caller-numbered)
@@ -116,11 +136,9 @@ struct asw_ctx {
     RefineTables refine;
     TwoPassTable twopass;
     PermTable perm;
-    int census_lambda_ad = 0, census_lambda_census = 0;  // what buf("census_tables") holds (asw_methods.hip: ensure_census_tables)
-    // weighted-median tables: exp() LUT of the colour weight per rateR, space kernel per (win, rateS)
-    DevBuf wm_lut2, wm_wd;
-    double wm_rate_r = -1, wm_rate_s = -1;
-    int wm_win = 0;
+    CensusTables census;
+    WMedianTables wm;
+    PrepTables prep;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // total start/stop, aggregate start/stop
     // side streams for small launches that are independent of a method's main kernel (border tiles and the one-candidate tail
     // of the classic bilateral method: 0.5 ms each when serialised, latency-bound) + fork / join events
@@ -128,6 +146,22 @@ struct asw_ctx {
     hipEvent_t aux_ev[3] = {nullptr, nullptr, nullptr};
     asw_timing timing = {0, 0, 0, 0};
     DevBuf& buf(const char* name) { return scratch[name]; }
+    asw_ctx() = default;
+    asw_ctx(const asw_ctx&) = delete;
+    asw_ctx& operator=(const asw_ctx&) = delete;
+    // waits for the work in flight and gives back the streams and events, however few asw_create got to; the buffers free themselves
+    ~asw_ctx()
+    {
+        (void)hipSetDevice(device);
+        for (hipStream_t s : {stream, aux[0], aux[1]})
+            if (s) (void)hipStreamSynchronize(s);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : aux_ev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipStream_t s : {stream, aux[0], aux[1]})
+            if (s) (void)hipStreamDestroy(s);
+    }
 };
 
 // ---- kernel launchers (each returns an asw_status; all work is enqueued on `s`) ----

@@ -96,8 +96,8 @@ int timed_finish(asw_ctx* ctx)
 static int ensure_bilateral_tables(asw_ctx* ctx, int kind, int win, double gamma_c, double gamma_g, int mirror)
 {
     BilateralTables& t = ctx->bil;
-    if (t.kind == kind && t.win == win && t.gamma_c == gamma_c && t.gamma_g == gamma_g && t.mirror == mirror && t.taps.p)
-        return ASW_OK;
+    const auto key = std::make_tuple(kind, win, gamma_c, gamma_g, mirror);
+    if (t.cache.hit(key, ctx->stream)) return ASW_OK;
     const int ks = win, h = ks / 2;
     std::vector<int> dxw, dyw, dxs, dys;  // weight direction (build order) / sample offset (consume order)
     if (kind == 0) {
@@ -163,28 +163,25 @@ static int ensure_bilateral_tables(asw_ctx* ctx, int kind, int win, double gamma
             cells[(kx + 3) * 15 + ky] = make_int4(dxw[i], dyw[i], cls_of_r2[dxw[i] * dxw[i] + dyw[i] * dyw[i]] * 256, 1);
         }
     }
-    ASW_TRY(t.taps.ensure((taps.size() > 4 ? taps.size() : 4) * sizeof(int4)));  // never a null table, even for win = 1 (no taps)
-    ASW_TRY(t.lut.ensure(lut.size() * sizeof(float)));
-    if (!taps.empty())  // win = 1 has no taps at all (every E is 0/0)
-        ASW_HIP_TRY(hipMemcpyAsync(t.taps.p, taps.data(), taps.size() * sizeof(int4), hipMemcpyHostToDevice, ctx->stream));
-    ASW_HIP_TRY(hipMemcpyAsync(t.lut.p, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    if (taps.empty())  // win = 1 has no taps at all (every E is 0/0): never a null table all the same
+        ASW_TRY(t.taps.ensure(4 * sizeof(int4)));
+    else
+        ASW_TRY(t.cache.upload(t.taps, taps.data(), taps.size() * sizeof(int4)));
+    ASW_TRY(t.cache.upload(t.lut, lut.data(), lut.size() * sizeof(float)));
     std::vector<float> lut_xq;
     t.xq_lut_ok = false;
     if (!cells.empty()) {
-        ASW_TRY(t.cells.ensure(cells.size() * sizeof(int4)));
-        ASW_HIP_TRY(hipMemcpyAsync(t.cells.p, cells.data(), cells.size() * sizeof(int4), hipMemcpyHostToDevice, ctx->stream));
+        ASW_TRY(t.cache.upload(t.cells, cells.data(), cells.size() * sizeof(int4)));
         t.xq_lut_ok = bilateral_xq_lut_ok(lut.data(), lut.size());
         if (t.xq_lut_ok) {  // a power-of-two scale: exact for every entry (none overflows, none is lost)
             lut_xq.resize(lut.size());
             for (size_t i = 0; i < lut.size(); i++) lut_xq[i] = ldexpf(lut[i], XQ_LUT_SCALE_LOG2);
-            ASW_TRY(t.lut_xq.ensure(lut_xq.size() * sizeof(float)));
-            ASW_HIP_TRY(hipMemcpyAsync(t.lut_xq.p, lut_xq.data(), lut_xq.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+            ASW_TRY(t.cache.upload(t.lut_xq, lut_xq.data(), lut_xq.size() * sizeof(float)));
         }
     }
-    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));  // host vectors die at return
-    t.kind = kind; t.win = win; t.gamma_c = gamma_c; t.gamma_g = gamma_g; t.mirror = mirror; t.ntaps = nt_pad;
+    t.ntaps = nt_pad;
     t.ncls = (int)r2s.size() + 1;
-    return ASW_OK;
+    return t.cache.commit(key);
 }
 
 
@@ -279,17 +276,14 @@ static int run_bilateral(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool kee
 static int ensure_twopass_table(asw_ctx* ctx, int win, int gamma_c, int gamma_g)
 {
     TwoPassTable& t = ctx->twopass;
-    if (t.win == win && t.gamma_c == gamma_c && t.gamma_g == gamma_g && t.t.p) return ASW_OK;
-    t.win = 0;
+    const auto key = std::make_tuple(win, gamma_c, gamma_g);
+    if (t.cache.hit(key, ctx->stream)) return ASW_OK;
     const int h = win / 2;
     std::vector<float> tab((size_t)(h + 1) * 256);
     for (int r = 0; r <= h; r++)
         for (int dc = 0; dc < 256; dc++) tab[(size_t)r * 256 + dc] = (float)exp(-((double)dc / gamma_c + (double)r / gamma_g));
-    ASW_TRY(t.t.ensure(tab.size() * sizeof(float)));
-    ASW_HIP_TRY(hipMemcpyAsync(t.t.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));  // the host vector dies at return
-    t.win = win; t.gamma_c = gamma_c; t.gamma_g = gamma_g;
-    return ASW_OK;
+    ASW_TRY(t.cache.upload(t.t, tab.data(), tab.size() * sizeof(float)));
+    return t.cache.commit(key);
 }
 
 static int run_twopass(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_volume)
@@ -594,7 +588,8 @@ static int run_geodesic(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep
 // ------------------------------------------------------------------------------------------
 static int ensure_wmedian_tables(asw_ctx* ctx, int win, double rate_s, double rate_r)
 {
-    if (ctx->wm_rate_r != rate_r || !ctx->wm_lut2.p) {
+    WMedianTables& t = ctx->wm;
+    if (!t.lut2_cache.hit(rate_r, ctx->stream)) {
         // computeColorWeightGau: exp((d0+d1+d2)/rateR*(-1)) == exp(addWeighted(d0+d1, a, d2, a)) with
         // a = (float)(-1/rateR) (M.cpp:3177-3179); cv::exp restated as expf
         std::vector<float> lut((size_t)511 * 256);
@@ -604,12 +599,11 @@ static int ensure_wmedian_tables(asw_ctx* ctx, int win, double rate_s, double ra
                 float arg = (float)m * al + (float)c * al;
                 lut[(size_t)m * 256 + c] = expf(arg);
             }
-        ASW_TRY(ctx->wm_lut2.ensure(lut.size() * 4));
-        ASW_HIP_TRY(hipMemcpyAsync(ctx->wm_lut2.p, lut.data(), lut.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        ctx->wm_rate_r = rate_r;
+        ASW_TRY(t.lut2_cache.upload(t.lut2, lut.data(), lut.size() * 4));
+        ASW_TRY(t.lut2_cache.commit(rate_r));
     }
-    if (ctx->wm_rate_s != rate_s || ctx->wm_win != win || !ctx->wm_wd.p) {
+    const auto wd_key = std::make_tuple(rate_s, win);
+    if (!t.wd_cache.hit(wd_key, ctx->stream)) {
         // computeSpaceWeightGau (M.cpp:3207-3226)
         const int h = win / 2;
         std::vector<float> wd((size_t)win * win);
@@ -619,11 +613,8 @@ static int ensure_wmedian_tables(asw_ctx* ctx, int win, double rate_s, double ra
                 float v = (float)((x - h) * (x - h)) + (float)((y - h) * (y - h));
                 wd[(size_t)x * win + y] = expf(v * al);
             }
-        ASW_TRY(ctx->wm_wd.ensure(wd.size() * 4));
-        ASW_HIP_TRY(hipMemcpyAsync(ctx->wm_wd.p, wd.data(), wd.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        ctx->wm_rate_s = rate_s;
-        ctx->wm_win = win;
+        ASW_TRY(t.wd_cache.upload(t.wd, wd.data(), wd.size() * 4));
+        ASW_TRY(t.wd_cache.commit(wd_key));
     }
     return ASW_OK;
 }
@@ -649,8 +640,8 @@ static int run_wmedian(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_
     const uint8_t* dR = f->R.as<uint8_t>();
     ASW_TRY(build_similarity_volume(ctx, dL, dR, H, W, mp.minD, n, 0.4, 10, 50, raw.as<float>()));  // M.cpp:3250
     ASW_TRY(agg_begin(ctx));
-    ASW_TRY(launch_wm_weights(ctx->stream, dL, H, W, 0, mp.win, ctx->wm_lut2.as<float>(), ctx->wm_wd.as<float>(), wl.as<float>()));
-    ASW_TRY(launch_wm_weights(ctx->stream, dR, H, W, max_off, mp.win, ctx->wm_lut2.as<float>(), nullptr, wr.as<float>()));
+    ASW_TRY(launch_wm_weights(ctx->stream, dL, H, W, 0, mp.win, ctx->wm.lut2.as<float>(), ctx->wm.wd.as<float>(), wl.as<float>()));
+    ASW_TRY(launch_wm_weights(ctx->stream, dR, H, W, max_off, mp.win, ctx->wm.lut2.as<float>(), nullptr, wr.as<float>()));
     // 15x15 (the reference's call site): the neighbourhood of an 8x8 pixel block is sorted once per slice and every pixel walks
     // it (k_wmedian_tile.hip), 3 KB of list per block and slice; 3x3 .. 13x13, 17x17 .. 37x37: the same scheme with the window a
     // run-time parameter (k_wmedian_tile_gen.hip), 1.5 .. 12 KB; 1x1 and 39x39 .. 45x45 sort per pixel (k_wmedian.hip).  Slices go in
@@ -840,21 +831,18 @@ int bm_prepare(asw_ctx* ctx, const BmParams& p, int H, int W, BmLaunch* out)
 // ------------------------------------------------------------------------------------------
 // AD-Census cost (Mei et al. 2011): DESIGN.md section 4.13; not in the reference
 // ------------------------------------------------------------------------------------------
-// TA[v] = floor(127 (1 - exp(-v / lambda_ad)) + 0.5), v = 0..255, and TC[h] the same with lambda_census, h = 0..62, in
-// buf("census_tables") as TA[256] | TC[64]
+// TA[v] = floor(127 (1 - exp(-v / lambda_ad)) + 0.5), v = 0..255, and TC[h] the same with lambda_census, h = 0..62, as
+// TA[256] | TC[64]
 static int ensure_census_tables(asw_ctx* ctx, int lambda_ad, int lambda_census)
 {
-    DevBuf& t = ctx->buf("census_tables");
-    if (t.p && ctx->census_lambda_ad == lambda_ad && ctx->census_lambda_census == lambda_census) return ASW_OK;
-    ctx->census_lambda_ad = 0;
+    CensusTables& t = ctx->census;
+    const auto key = std::make_tuple(lambda_ad, lambda_census);
+    if (t.cache.hit(key, ctx->stream)) return ASW_OK;
     uint8_t tab[320] = {0};
     for (int v = 0; v < 256; v++) tab[v] = (uint8_t)floor(127.0 * (1.0 - exp(-(double)v / lambda_ad)) + 0.5);
     for (int h = 0; h < 63; h++) tab[256 + h] = (uint8_t)floor(127.0 * (1.0 - exp(-(double)h / lambda_census)) + 0.5);
-    ASW_TRY(t.ensure(sizeof(tab)));
-    ASW_HIP_TRY(hipMemcpyAsync(t.p, tab, sizeof(tab), hipMemcpyHostToDevice, ctx->stream));
-    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));  // the host array dies at return
-    ctx->census_lambda_ad = lambda_ad; ctx->census_lambda_census = lambda_census;
-    return ASW_OK;
+    ASW_TRY(t.cache.upload(t.t, tab, sizeof(tab)));
+    return t.cache.commit(key);
 }
 
 int build_census_cost(asw_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int H, int W, int channels, int disparity_type, int minD,
@@ -871,12 +859,9 @@ int build_census_cost(asw_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int H,
     ASW_TRY(launch_census_transform(ctx->stream, gl, H, W, cl.as<uint2>()));
     ASW_TRY(launch_census_transform(ctx->stream, gr, H, W, cr.as<uint2>()));
     return launch_cost_census(ctx->stream, dL, dR, cl.as<uint2>(), cr.as<uint2>(), H, W, channels, disparity_type, minD, numD,
-                              lambda_ad > 0 ? ctx->buf("census_tables").as<uint8_t>() : nullptr, cost);
+                              lambda_ad > 0 ? ctx->census.t.as<uint8_t>() : nullptr, cost);
 }
 
-// ------------------------------------------------------------------------------------------
-// cross-based support regions (Zhang, Lu, Lafruit 2009): DESIGN.md section 4.12; not in the reference
-// ------------------------------------------------------------------------------------------
 // ------------------------------------------------------------------------------------------
 // recursive (permeability) aggregation over the whole image (Cigla & Alatan 2013): entry 12 with an asw_alg_permeability() value;
 // DESIGN.md section 4.17; not in the reference
@@ -884,15 +869,11 @@ int build_census_cost(asw_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int H,
 static int ensure_perm_table(asw_ctx* ctx, int sigma)
 {
     PermTable& t = ctx->perm;
-    if (t.sigma == sigma && t.t.p) return ASW_OK;
-    t.sigma = 0;
+    if (t.cache.hit(sigma, ctx->stream)) return ASW_OK;
     double tab[256];
     for (int k = 0; k < 256; k++) tab[k] = (double)(float)exp(-(double)k / sigma);  // rounded to f32 here: the kernels see doubles only
-    ASW_TRY(t.t.ensure(sizeof(tab)));
-    ASW_HIP_TRY(hipMemcpyAsync(t.t.p, tab, sizeof(tab), hipMemcpyHostToDevice, ctx->stream));
-    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));  // the host array dies at return
-    t.sigma = sigma;
-    return ASW_OK;
+    ASW_TRY(t.cache.upload(t.t, tab, sizeof(tab)));
+    return t.cache.commit(sigma);
 }
 
 // win is not read: the support is the whole image
@@ -969,6 +950,9 @@ static int run_permeability(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool 
     return agg_end(ctx, 4 + 2 * chunks);  // two permeability planes, N's two passes, two passes per chunk
 }
 
+// ------------------------------------------------------------------------------------------
+// cross-based support regions (Zhang, Lu, Lafruit 2009): DESIGN.md section 4.12; not in the reference
+// ------------------------------------------------------------------------------------------
 static int run_cross(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_volume)
 {
     if (mp.permeability) return run_permeability(ctx, f, mp, keep_volume);  // no window: before the window checks
@@ -1144,20 +1128,17 @@ int check_refine_params(const RefineParams& p, int rows, int cols, int channels)
 static int ensure_refine_tables(asw_ctx* ctx, int win, double gamma_c, double gamma_s, int channels)
 {
     RefineTables& t = ctx->refine;
-    if (t.win == win && t.gamma_c == gamma_c && t.gamma_s == gamma_s && t.channels == channels && t.tc.p && t.ts.p) return ASW_OK;
-    t.win = 0;
+    const auto key = std::make_tuple(win, gamma_c, gamma_s, channels);
+    if (t.cache.hit(key, ctx->stream)) return ASW_OK;
     const int k = win / 2, ntc = 255 * channels + 1;
     std::vector<unsigned> tc(ntc), ts((size_t)(k + 1) * (k + 1));
     for (int c = 0; c < ntc; c++) tc[c] = (unsigned)floor(4096.0 * exp(-(double)c / gamma_c) + 0.5);
     for (int j = 0; j <= k; j++)
         for (int i = 0; i <= k; i++) ts[(size_t)j * (k + 1) + i] = (unsigned)floor(256.0 * exp(-sqrt((double)(i * i + j * j)) / gamma_s) + 0.5);
-    ASW_TRY(t.tc.ensure(tc.size() * sizeof(unsigned)));
-    ASW_TRY(t.ts.ensure(ts.size() * sizeof(unsigned)));
-    ASW_HIP_TRY(hipMemcpyAsync(t.tc.p, tc.data(), tc.size() * sizeof(unsigned), hipMemcpyHostToDevice, ctx->stream));
-    ASW_HIP_TRY(hipMemcpyAsync(t.ts.p, ts.data(), ts.size() * sizeof(unsigned), hipMemcpyHostToDevice, ctx->stream));
-    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));  // the host vectors go out of scope
-    t.win = win; t.gamma_c = gamma_c; t.gamma_s = gamma_s; t.channels = channels; t.ntc = ntc;
-    return ASW_OK;
+    ASW_TRY(t.cache.upload(t.tc, tc.data(), tc.size() * sizeof(unsigned)));
+    ASW_TRY(t.cache.upload(t.ts, ts.data(), ts.size() * sizeof(unsigned)));
+    t.ntc = ntc;
+    return t.cache.commit(key);
 }
 
 int run_refine(asw_ctx* ctx, const uint8_t* guide, int channels, const float* dl, const float* dr, int H, int W, const RefineParams& p,

@@ -135,10 +135,9 @@ int launch_bgr2gray(hipStream_t s, const uint8_t* bgr, int H, int W, uint8_t* gr
     int n = H * W;
     int threads = 256, blocks = (n / 4 + 1 + threads - 1) / threads;
     if (bits == 15)
-        hipLaunchKernelGGL(k_bgr2gray, dim3(blocks), dim3(threads), 0, s, bgr, n, gray, 3735u, 19235u, 9798u, 15u);
+        ASW_TRY(ASW_LAUNCH(k_bgr2gray, dim3(blocks), dim3(threads), 0, s, bgr, n, gray, 3735u, 19235u, 9798u, 15u));
     else
-        hipLaunchKernelGGL(k_bgr2gray, dim3(blocks), dim3(threads), 0, s, bgr, n, gray, 1868u, 9617u, 4899u, 14u);
-    ASW_HIP_TRY(hipGetLastError());
+        ASW_TRY(ASW_LAUNCH(k_bgr2gray, dim3(blocks), dim3(threads), 0, s, bgr, n, gray, 1868u, 9617u, 4899u, 14u));
     return ASW_OK;
 }
 
@@ -147,10 +146,9 @@ int launch_rgb2gray(hipStream_t s, const uint8_t* bgr, int H, int W, uint8_t* gr
     int n = H * W;
     int threads = 256, blocks = (n / 4 + 1 + threads - 1) / threads;
     if (bits == 15)
-        hipLaunchKernelGGL(k_bgr2gray, dim3(blocks), dim3(threads), 0, s, bgr, n, gray, 9798u, 19235u, 3735u, 15u);
+        ASW_TRY(ASW_LAUNCH(k_bgr2gray, dim3(blocks), dim3(threads), 0, s, bgr, n, gray, 9798u, 19235u, 3735u, 15u));
     else
-        hipLaunchKernelGGL(k_bgr2gray, dim3(blocks), dim3(threads), 0, s, bgr, n, gray, 4899u, 9617u, 1868u, 14u);
-    ASW_HIP_TRY(hipGetLastError());
+        ASW_TRY(ASW_LAUNCH(k_bgr2gray, dim3(blocks), dim3(threads), 0, s, bgr, n, gray, 4899u, 9617u, 1868u, 14u));
     return ASW_OK;
 }
 
@@ -160,12 +158,10 @@ int launch_cost_ad(hipStream_t s, const uint8_t* L, const uint8_t* R, int H, int
     const int dPerBlock = 16;
     dim3 grid(H, (numD + dPerBlock - 1) / dPerBlock);
     size_t lds = (size_t)2 * W * C;
-    if (lds > 160 * 1024) return ASW_ERR_BAD_ARGUMENT;
     if (C == 3)
-        hipLaunchKernelGGL(k_cost_ad<3>, grid, dim3(256), lds, s, L, R, H, W, disp_type, minD, numD, dPerBlock, do_thresh, threshold, cost);
+        ASW_TRY(ASW_LAUNCH(k_cost_ad<3>, grid, dim3(256), lds, s, L, R, H, W, disp_type, minD, numD, dPerBlock, do_thresh, threshold, cost));
     else
-        hipLaunchKernelGGL(k_cost_ad<1>, grid, dim3(256), lds, s, L, R, H, W, disp_type, minD, numD, dPerBlock, do_thresh, threshold, cost);
-    ASW_HIP_TRY(hipGetLastError());
+        ASW_TRY(ASW_LAUNCH(k_cost_ad<1>, grid, dim3(256), lds, s, L, R, H, W, disp_type, minD, numD, dPerBlock, do_thresh, threshold, cost));
     return ASW_OK;
 }
 
@@ -191,20 +187,17 @@ int launch_lr_check(hipStream_t s, const float* dl, const float* dr, int H, int 
                     unsigned* n_invalid)
 {
     ASW_HIP_TRY(hipMemsetAsync(n_invalid, 0, sizeof(unsigned), s));
-    hipLaunchKernelGGL(k_lr_check, dim3((W + 63) / 64, (H + 3) / 4), dim3(256), 0, s, dl, dr, H, W, max_diff, invalid, out, n_invalid);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_lr_check, dim3((W + 63) / 64, (H + 3) / 4), dim3(256), 0, s, dl, dr, H, W, max_diff, invalid, out, n_invalid);
 }
 
 int launch_wta(hipStream_t s, const float* vol, int n, int H, int W, int minD, float* disp)
 {
     size_t plane = (size_t)H * W;
     if (plane < ((size_t)1 << 20)) {
-        hipLaunchKernelGGL(k_wta<1>, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, s, vol, n, plane, minD, disp);
+        ASW_TRY(ASW_LAUNCH(k_wta<1>, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, s, vol, n, plane, minD, disp));
     } else {
         int blocks = (int)((plane / 4 + 1 + 255) / 256);
-        hipLaunchKernelGGL(k_wta<4>, dim3(blocks), dim3(256), 0, s, vol, n, plane, minD, disp);
+        ASW_TRY(ASW_LAUNCH(k_wta<4>, dim3(blocks), dim3(256), 0, s, vol, n, plane, minD, disp));
     }
-    ASW_HIP_TRY(hipGetLastError());
     return ASW_OK;
 }

@@ -365,8 +365,6 @@ int launch_t(hipStream_t s, const BilateralLaunch& a)
     const Layout lay(p.h, G);
     if (!lds_fits(a.win)) return ASW_ERR_BAD_ARGUMENT;
     auto kern = k_asw_bilateral<HH, G, WPE>;
-    if (lay.total > 64 * 1024)
-        ASW_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lay.total));
     dim3 grid((p.x_hi - 1) / TW - p.tile0 + 1, (a.H + TH - 1) / TH);
     if (a.ntaps % G != 0) return ASW_ERR_BAD_ARGUMENT;  // cannot happen for odd windows
     // Small images do not fill 256 CUs with tiles alone (C2: 450x375 -> 752 tiles): split the candidate range over
@@ -378,12 +376,11 @@ int launch_t(hipStream_t s, const BilateralLaunch& a)
     nz = (chunks16 + chunks_per_z - 1) / chunks_per_z;
     p.cand_per_z = chunks_per_z * 16;
     grid.z = nz;
-    hipLaunchKernelGGL(kern, grid, dim3(256), lay.total, s, p, a.gL, a.gR, a.taps, a.lut, a.vol, a.disp, a.partE, a.partD);
+    ASW_TRY(ASW_LAUNCH(kern, grid, dim3(256), lay.total, s, p, a.gL, a.gR, a.taps, a.lut, a.vol, a.disp, a.partE, a.partD));
     if (nz > 1) {
         const size_t plane = (size_t)a.H * a.W;
-        hipLaunchKernelGGL(k_merge_slices, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, s, a.partE, a.partD, nz, plane, a.disp);
+        ASW_TRY(ASW_LAUNCH(k_merge_slices, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, s, a.partE, a.partD, nz, plane, a.disp));
     }
-    ASW_HIP_TRY(hipGetLastError());
     return ASW_OK;
 }
 
@@ -403,9 +400,7 @@ int bilateral_max_window()
 
 int launch_merge_slices(hipStream_t s, const double* partE, const float* partD, int nz, size_t plane, float* disp)
 {
-    hipLaunchKernelGGL(k_merge_slices, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, s, partE, partD, nz, plane, disp);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_merge_slices, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, s, partE, partD, nz, plane, disp);
 }
 
 int launch_merge_slices_cols(hipStream_t s, const double* partE, const float* partD, int nz, int H, int W, int col_lo, int col_hi,
@@ -413,9 +408,7 @@ int launch_merge_slices_cols(hipStream_t s, const double* partE, const float* pa
 {
     if (col_lo < 0 || col_hi > W || col_lo >= col_hi) return ASW_ERR_BAD_ARGUMENT;
     const int wc = col_hi - col_lo;
-    hipLaunchKernelGGL(k_merge_slices_cols, dim3((wc + 63) / 64, H), dim3(64), 0, s, partE, partD, nz, H, W, col_lo, wc, disp);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_merge_slices_cols, dim3((wc + 63) / 64, H), dim3(64), 0, s, partE, partD, nz, H, W, col_lo, wc, disp);
 }
 
 int launch_bilateral(hipStream_t s, const BilateralLaunch& a)

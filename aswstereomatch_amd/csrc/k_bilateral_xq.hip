@@ -860,18 +860,17 @@ int launch_xq_t(hipStream_t s, hipStream_t s_border, const uint8_t* gL, const ui
         // (columns W-8 .. W-1) must lie in the last tile's right-gray tile: x0_last + minD <= W - 1
         if ((ntiles - 1) * PXW + minD > W - 1) return ASW_ERR_BAD_ARGUMENT;
         XqParams pe{H, W, minD, 0};
-        hipLaunchKernelGGL((k_asw_bilateral_xq<NW, true, true>), dim3(1, H), blk, 0, s_border, pe, gL, gR, cells, lut, vol,
-                           bestE, bestD, last ? nullptr : disp);
+        ASW_TRY(ASW_LAUNCH((k_asw_bilateral_xq<NW, true, true>), dim3(1, H), blk, 0, s_border, pe, gL, gR, cells, lut, vol,
+                           bestE, bestD, last ? nullptr : disp));
         if (ntiles > 1) {
             XqParams pi{H, W, minD, 1};
             if (last)
-                hipLaunchKernelGGL((k_asw_bilateral_xq<NW, false, true, true>), dim3(ntiles - 1, H), blk, 0, s, pi, gL, gR, cells,
-                                   lut, vol, bestE, bestD, disp);
+                ASW_TRY(ASW_LAUNCH((k_asw_bilateral_xq<NW, false, true, true>), dim3(ntiles - 1, H), blk, 0, s, pi, gL, gR, cells,
+                                   lut, vol, bestE, bestD, disp));
             else
-                hipLaunchKernelGGL((k_asw_bilateral_xq<NW, false, true>), dim3(ntiles - 1, H), blk, 0, s, pi, gL, gR, cells, lut,
-                                   vol, bestE, bestD, disp);
+                ASW_TRY(ASW_LAUNCH((k_asw_bilateral_xq<NW, false, true>), dim3(ntiles - 1, H), blk, 0, s, pi, gL, gR, cells, lut,
+                                   vol, bestE, bestD, disp));
         }
-        ASW_HIP_TRY(hipGetLastError());
         return ASW_OK;
     }
     // tiles whose windows (of in-image pixels) stay left of the right border: x0 + 63 + 7 <= W - 1
@@ -881,17 +880,16 @@ int launch_xq_t(hipStream_t s, hipStream_t s_border, const uint8_t* gL, const ui
     if (n_int > 0) {
         XqParams p{H, W, minD, 0};
         if (last)
-            hipLaunchKernelGGL((k_asw_bilateral_xq<NW, false, false, true>), dim3(n_int, H), blk, 0, s, p, gL, gR, cells, lut, vol,
-                               bestE, bestD, disp);
+            ASW_TRY(ASW_LAUNCH((k_asw_bilateral_xq<NW, false, false, true>), dim3(n_int, H), blk, 0, s, p, gL, gR, cells, lut, vol,
+                               bestE, bestD, disp));
         else
-            hipLaunchKernelGGL(ki, dim3(n_int, H), blk, 0, s, p, gL, gR, cells, lut, vol, bestE, bestD, disp);
+            ASW_TRY(ASW_LAUNCH(ki, dim3(n_int, H), blk, 0, s, p, gL, gR, cells, lut, vol, bestE, bestD, disp));
     }
     if (ntiles > n_int) {
         XqParams p{H, W, minD, n_int};
-        hipLaunchKernelGGL(ke, dim3(ntiles - n_int, H), blk, 0, s_border, p, gL, gR, cells, lut, vol, bestE, bestD,
-                           last ? nullptr : disp);
+        ASW_TRY(ASW_LAUNCH(ke, dim3(ntiles - n_int, H), blk, 0, s_border, p, gL, gR, cells, lut, vol, bestE, bestD,
+                           last ? nullptr : disp));
     }
-    ASW_HIP_TRY(hipGetLastError());
     return ASW_OK;
 }
 }  // namespace

@@ -203,19 +203,16 @@ int launch_bilgrid(hipStream_t s, const uint8_t* gl, const uint8_t* gr, int H, i
     g.nr = g.nl; g.H = H; g.W = W; g.rate_s = rate_s; g.rate_r = rate_r;
     const size_t plane = (size_t)H * W, ZW = (size_t)(g.nl + 1) * (g.nr + 1);
     const size_t lds = ZW * 16;
-    if (lds > 64 * 1024)
-        ASW_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_grid_cell), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_grid_init, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, s, best, disp, plane);
+    ASW_TRY(ASW_LAUNCH(k_grid_init, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, s, best, disp, plane));
     const size_t sy = ZW, sx = ZW * (g.ny + 1);
     const size_t lines_y = (size_t)(g.nx + 1) * ZW, lines_x = sx;
     for (int k = 0; k <= numD; k++) {  // offsets minD .. minD+numD inclusive, M.cpp:2280
         const int offset = minD + k;
-        hipLaunchKernelGGL(k_grid_cell, dim3(g.nx + 1, g.ny + 1), dim3(64), lds, s, g, gl, gr, offset, F, S);
-        hipLaunchKernelGGL(k_grid_pass, dim3((unsigned)((lines_y + 255) / 256)), dim3(256), 0, s, F, S, lines_y, ZW, sx, sy, g.ny);  // M.cpp:2056-2118
-        hipLaunchKernelGGL(k_grid_pass, dim3((unsigned)((lines_x + 255) / 256)), dim3(256), 0, s, F, S, lines_x, sx, (size_t)0, sx, g.nx);  // M.cpp:2120-2183
-        hipLaunchKernelGGL(k_grid_slice, dim3((W + 63) / 64, (H + 3) / 4), dim3(256), 0, s, g, gl, gr, offset, F, S, best, disp,
-                           vol ? vol + (size_t)k * plane : nullptr);
+        ASW_TRY(ASW_LAUNCH(k_grid_cell, dim3(g.nx + 1, g.ny + 1), dim3(64), lds, s, g, gl, gr, offset, F, S));
+        ASW_TRY(ASW_LAUNCH(k_grid_pass, dim3((unsigned)((lines_y + 255) / 256)), dim3(256), 0, s, F, S, lines_y, ZW, sx, sy, g.ny));  // M.cpp:2056-2118
+        ASW_TRY(ASW_LAUNCH(k_grid_pass, dim3((unsigned)((lines_x + 255) / 256)), dim3(256), 0, s, F, S, lines_x, sx, (size_t)0, sx, g.nx));  // M.cpp:2120-2183
+        ASW_TRY(ASW_LAUNCH(k_grid_slice, dim3((W + 63) / 64, (H + 3) / 4), dim3(256), 0, s, g, gl, gr, offset, F, S, best, disp,
+                           vol ? vol + (size_t)k * plane : nullptr));
     }
-    ASW_HIP_TRY(hipGetLastError());
     return ASW_OK;
 }

@@ -153,12 +153,8 @@ int launch_t(hipStream_t s, const BloParams& p, const uint8_t* gF, const uint8_t
 {
     const size_t lds = blo1_lds_bytes(p.win, DC);
     auto kern = k_blo1<DC>;
-    if (lds > 64 * 1024)
-        ASW_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     dim3 grid((p.W + BTW - 1) / BTW, (p.H + BTH - 1) / BTH);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, p, gF, gS, cost, vol, disp);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(kern, grid, dim3(256), lds, s, p, gF, gS, cost, vol, disp);
 }
 
 }  // namespace

@@ -243,10 +243,8 @@ int launch_match(hipStream_t s, const BmLaunch& a, const uint8_t* pf, short* raw
     const int strips_wanted = std::max(1, 4096 / tiles);
     const int rows_per = std::max((Hv + strips_wanted - 1) / strips_wanted, 8);
     const int strips = (Hv + rows_per - 1) / rows_per;
-    hipLaunchKernelGGL(k_bm_match<NPL>, dim3(tiles, strips), dim3(64), (size_t)TX * NPL * 64 * sizeof(int), s, pf, H, W, a.minD, D, h,
-                       a.cap, a.texture, a.U, TX, rows_per, raw, cost, a.vol);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_bm_match<NPL>, dim3(tiles, strips), dim3(64), (size_t)TX * NPL * 64 * sizeof(int), s, pf, H, W, a.minD, D, h,
+                      a.cap, a.texture, a.U, TX, rows_per, raw, cost, a.vol);
 }
 
 }  // namespace
@@ -279,22 +277,19 @@ int launch_bm(hipStream_t s, const BmLaunch& a)
     int* spk = (int*)p; p += plane * 8;
     int* cost = (int*)p; p += plane * 4;
     short* raw = (short*)p;
-    hipLaunchKernelGGL(k_bm_prefilter, dim3(blocks(plane, 256), 2), dim3(256), 0, s, a.L, a.R, H, W, a.cap, pf);
-    ASW_HIP_TRY(hipGetLastError());
+    ASW_TRY(ASW_LAUNCH(k_bm_prefilter, dim3(blocks(plane, 256), 2), dim3(256), 0, s, a.L, a.R, H, W, a.cap, pf));
     if (a.ev_agg0) ASW_HIP_TRY(hipEventRecord(a.ev_agg0, s));
     ASW_TRY(dispatch_npl(D, [&](auto npl) { return launch_match<decltype(npl)::value>(s, a, pf, raw, cost); }));
     if (a.ev_agg1) ASW_HIP_TRY(hipEventRecord(a.ev_agg1, s));
     const int minX1 = minD + D;
     if (a.M >= 0 && minX1 < W) {
         ASW_HIP_TRY(hipMemsetAsync(key, 0xff, plane * 8, s));
-        hipLaunchKernelGGL(k_bm_lrkey, dim3(blocks((size_t)(y1 - y0) * (W - minX1), 256)), dim3(256), 0, s, raw, cost, W, y0, y1,
-                           minX1, FILTERED, key);
-        ASW_HIP_TRY(hipGetLastError());
+        ASW_TRY(ASW_LAUNCH(k_bm_lrkey, dim3(blocks((size_t)(y1 - y0) * (W - minX1), 256)), dim3(256), 0, s, raw, cost, W, y0, y1,
+                           minX1, FILTERED, key));
     }
     const int M16 = a.M < 0 ? -1 : (int)std::min<long long>(16LL * a.M, INT_MAX / 2);
-    hipLaunchKernelGGL(k_bm_finish, dim3(blocks(plane, 256)), dim3(256), 0, s, raw, key, H, W, y0, y1, x0, x1, FILTERED, M16,
-                       a.disp16);
-    ASW_HIP_TRY(hipGetLastError());
+    ASW_TRY(ASW_LAUNCH(k_bm_finish, dim3(blocks(plane, 256)), dim3(256), 0, s, raw, key, H, W, y0, y1, x0, x1, FILTERED, M16,
+                       a.disp16));
     if (a.speckle_range >= 0 && a.speckle_window > 0)
         ASW_TRY(launch_filter_speckles(s, a.disp16, H, W, FILTERED, a.speckle_window, a.speckle_range, spk));
     return ASW_OK;

@@ -145,9 +145,7 @@ int launch_census_transform(hipStream_t s, const uint8_t* gray, int H, int W, ui
 {
     const dim3 grid((W + CW - 1) / CW, (H + CH - 1) / CH);
     if (grid.y > 65535) return ASW_ERR_BAD_ARGUMENT;
-    hipLaunchKernelGGL(k_census_transform, grid, dim3(256), 0, s, gray, H, W, code);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_census_transform, grid, dim3(256), 0, s, gray, H, W, code);
 }
 
 int launch_cost_census(hipStream_t s, const uint8_t* L, const uint8_t* R, const uint2* codeL, const uint2* codeR, int H, int W, int C,
@@ -158,13 +156,11 @@ int launch_cost_census(hipStream_t s, const uint8_t* L, const uint8_t* R, const 
     const dim3 grid(H, (numD + dPerBlock - 1) / dPerBlock);
     // staged rows: 16 W bytes of codes, and for the combined form 2 C W bytes of colours + the tables
     const size_t lds = (size_t)2 * W * sizeof(uint2) + (tables ? (size_t)2 * W * C + TAB_BYTES : 0);
-    if (lds > 160 * 1024) return ASW_ERR_BAD_ARGUMENT;
     if (!tables)
-        hipLaunchKernelGGL(k_cost_census<0>, grid, dim3(256), lds, s, L, R, codeL, codeR, tables, H, W, disp_type, minD, numD, dPerBlock, cost);
+        ASW_TRY(ASW_LAUNCH(k_cost_census<0>, grid, dim3(256), lds, s, L, R, codeL, codeR, tables, H, W, disp_type, minD, numD, dPerBlock, cost));
     else if (C == 3)
-        hipLaunchKernelGGL(k_cost_census<3>, grid, dim3(256), lds, s, L, R, codeL, codeR, tables, H, W, disp_type, minD, numD, dPerBlock, cost);
+        ASW_TRY(ASW_LAUNCH(k_cost_census<3>, grid, dim3(256), lds, s, L, R, codeL, codeR, tables, H, W, disp_type, minD, numD, dPerBlock, cost));
     else
-        hipLaunchKernelGGL(k_cost_census<1>, grid, dim3(256), lds, s, L, R, codeL, codeR, tables, H, W, disp_type, minD, numD, dPerBlock, cost);
-    ASW_HIP_TRY(hipGetLastError());
+        ASW_TRY(ASW_LAUNCH(k_cost_census<1>, grid, dim3(256), lds, s, L, R, codeL, codeR, tables, H, W, disp_type, minD, numD, dPerBlock, cost));
     return ASW_OK;
 }

@@ -342,9 +342,7 @@ __global__ void k_fill_u32(uint32_t* p, int n, uint32_t a, uint32_t b)
 int launch_scharr_x(hipStream_t s, const uint8_t* img, int H, int W, int pad, short* grad)
 {
     dim3 grid((W + pad + 255) / 256, H);
-    hipLaunchKernelGGL(k_scharr_x, grid, dim3(256), 0, s, img, H, W, pad, grad);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_scharr_x, grid, dim3(256), 0, s, img, H, W, pad, grad);
 }
 
 int launch_similarity(hipStream_t s, const uint8_t* L, const uint8_t* R, const short* gL, const short* gR, int H, int W,
@@ -370,11 +368,10 @@ int launch_similarity(hipStream_t s, const uint8_t* L, const uint8_t* R, const s
     int tCi = fc < -1.0 ? -1 : (fc > 1e6 ? 1000000 : (int)fc);
     float tGdn = (float)thresG;
     if ((double)tGdn > thresG) tGdn = nextafterf(tGdn, -INFINITY);
-    hipLaunchKernelGGL(k_similarity, grid, dim3(256), lds, s, L, R, gL, gR, H, W, minD, numD, rr, rg, thresCf, tCi, tGdn,
-                       (float)thresG, dch, cost, ord_scratch);
+    ASW_TRY(ASW_LAUNCH(k_similarity, grid, dim3(256), lds, s, L, R, gL, gR, H, W, minD, numD, rr, rg, thresCf, tCi, tGdn,
+                       (float)thresG, dch, cost, ord_scratch));
     if (ord_scratch && scales)
-        hipLaunchKernelGGL(k_scales_from_parts, dim3(numD), dim3(256), 0, s, ord_scratch, (int)(grid.x * grid.y * 4), scales);
-    ASW_HIP_TRY(hipGetLastError());
+        ASW_TRY(ASW_LAUNCH(k_scales_from_parts, dim3(numD), dim3(256), 0, s, ord_scratch, (int)(grid.x * grid.y * 4), scales));
     return ASW_OK;
 }
 
@@ -386,32 +383,27 @@ size_t similarity_parts_words(int H, int W, int numD)
 int launch_pad_reflect(hipStream_t s, const float* src, int n, int H, int W, int h, float* dst)
 {
     dim3 grid((W + 2 * h + 255) / 256, H + 2 * h, n);
-    hipLaunchKernelGGL(k_pad_reflect, grid, dim3(256), 0, s, src, H, W, h, dst);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_pad_reflect, grid, dim3(256), 0, s, src, H, W, h, dst);
 }
 
 int launch_slice_scales(hipStream_t s, const float* vol, int n, size_t plane, uint32_t* ord_scratch, float2* scales)
 {
-    hipLaunchKernelGGL(k_fill_u32, dim3((2 * n + 255) / 256), dim3(256), 0, s, ord_scratch, 2 * n, 0xffffffffu, 0u);
+    ASW_TRY(ASW_LAUNCH(k_fill_u32, dim3((2 * n + 255) / 256), dim3(256), 0, s, ord_scratch, 2 * n, 0xffffffffu, 0u));
     int bx = (int)((plane + 256 * 16 - 1) / (256 * 16));
     if (bx > 64) bx = 64;
     if (bx < 1) bx = 1;
-    hipLaunchKernelGGL(k_slice_minmax, dim3(bx, n), dim3(256), 0, s, vol, plane, ord_scratch);
-    hipLaunchKernelGGL(k_scales_from_ord, dim3((n + 255) / 256), dim3(256), 0, s, ord_scratch, n, scales);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    ASW_TRY(ASW_LAUNCH(k_slice_minmax, dim3(bx, n), dim3(256), 0, s, vol, plane, ord_scratch));
+    return ASW_LAUNCH(k_scales_from_ord, dim3((n + 255) / 256), dim3(256), 0, s, ord_scratch, n, scales);
 }
 
 int launch_u8_scale(hipStream_t s, const uint8_t* img, size_t nbytes, uint32_t* ord_scratch, float2* scale1)
 {
-    hipLaunchKernelGGL(k_fill_u32, dim3(1), dim3(256), 0, s, ord_scratch, 2, 0xffffffffu, 0u);
+    ASW_TRY(ASW_LAUNCH(k_fill_u32, dim3(1), dim3(256), 0, s, ord_scratch, 2, 0xffffffffu, 0u));
     int bx = (int)((nbytes + 256 * 64 - 1) / (256 * 64));
     if (bx > 1024) bx = 1024;
     if (bx < 1) bx = 1;
-    hipLaunchKernelGGL(k_minmax_u8, dim3(bx), dim3(256), 0, s, img, nbytes, ord_scratch);
-    if (scale1) hipLaunchKernelGGL(k_scales_from_ord, dim3(1), dim3(256), 0, s, ord_scratch, 1, scale1);
-    ASW_HIP_TRY(hipGetLastError());
+    ASW_TRY(ASW_LAUNCH(k_minmax_u8, dim3(bx), dim3(256), 0, s, img, nbytes, ord_scratch));
+    if (scale1) ASW_TRY(ASW_LAUNCH(k_scales_from_ord, dim3(1), dim3(256), 0, s, ord_scratch, 1, scale1));
     return ASW_OK;
 }
 
@@ -420,9 +412,7 @@ int launch_guide_scales_lr(hipStream_t s, const uint8_t* ref_img, const uint8_t*
 {
     int rc = launch_u8_scale(s, ref_img, (size_t)H * W * 3, ord_scratch, nullptr);
     if (rc != ASW_OK) return rc;
-    hipLaunchKernelGGL(k_fill_u32, dim3((2 * W + 255) / 256), dim3(256), 0, s, reinterpret_cast<uint32_t*>(colmm_scratch), 2 * W, 255u, 0u);
-    hipLaunchKernelGGL(k_col_minmax_u8, dim3((W + 63) / 64, (H + 63) / 64), dim3(256), 0, s, shifted_img, H, W, colmm_scratch);
-    hipLaunchKernelGGL(k_guide_scales_lr, dim3(numD), dim3(64), 0, s, ord_scratch, colmm_scratch, W, minD, numD, disp_type, scales);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    ASW_TRY(ASW_LAUNCH(k_fill_u32, dim3((2 * W + 255) / 256), dim3(256), 0, s, reinterpret_cast<uint32_t*>(colmm_scratch), 2 * W, 255u, 0u));
+    ASW_TRY(ASW_LAUNCH(k_col_minmax_u8, dim3((W + 63) / 64, (H + 63) / 64), dim3(256), 0, s, shifted_img, H, W, colmm_scratch));
+    return ASW_LAUNCH(k_guide_scales_lr, dim3(numD), dim3(64), 0, s, ord_scratch, colmm_scratch, W, minD, numD, disp_type, scales);
 }

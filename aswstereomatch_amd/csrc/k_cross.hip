@@ -178,13 +178,10 @@ int launch_cross_arms(hipStream_t s, const uint8_t* img, int H, int W, int C, in
     if (win < 1 || win / 2 > MAX_L || (C != 1 && C != 3)) return ASW_ERR_BAD_ARGUMENT;
     const dim3 grid((W + 63) / 64, (H + 3) / 4);
     if (C == 3)
-        hipLaunchKernelGGL(k_cross_arms<3>, grid, dim3(256), 0, s, img, H, W, win / 2, tau, arms);
+        ASW_TRY(ASW_LAUNCH(k_cross_arms<3>, grid, dim3(256), 0, s, img, H, W, win / 2, tau, arms));
     else
-        hipLaunchKernelGGL(k_cross_arms<1>, grid, dim3(256), 0, s, img, H, W, win / 2, tau, arms);
-    ASW_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_cross_count, grid, dim3(256), 0, s, arms, H, W, cnt);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+        ASW_TRY(ASW_LAUNCH(k_cross_arms<1>, grid, dim3(256), 0, s, img, H, W, win / 2, tau, arms));
+    return ASW_LAUNCH(k_cross_count, grid, dim3(256), 0, s, arms, H, W, cnt);
 }
 
 int launch_cross_aggregate(hipStream_t s, const uint8_t* cost, const uint32_t* arms, const uint16_t* cnt, int H, int W, int win,
@@ -196,8 +193,6 @@ int launch_cross_aggregate(hipStream_t s, const uint8_t* cost, const uint32_t* a
     // candidates per pass: what fits 64 KB of LDS, at most 4 (256 lanes = 4 x 64 columns in the column prefix)
     const int DC = (int)std::max<size_t>(1, std::min<size_t>(std::min(4, numD), ((size_t)64 * 1024) / per_candidate));
     const dim3 grid((W + TW - 1) / TW, (H + TH - 1) / TH);
-    hipLaunchKernelGGL(k_cross_aggregate, grid, dim3(256), DC * per_candidate, s, cost, arms, cnt, H, W, L, trunc, minD, numD, DC, SA, vol,
-                       disp);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_cross_aggregate, grid, dim3(256), DC * per_candidate, s, cost, arms, cnt, H, W, L, trunc, minD, numD, DC, SA, vol,
+                      disp);
 }

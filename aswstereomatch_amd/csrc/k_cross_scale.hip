@@ -124,9 +124,7 @@ int launch_pyramid_down(hipStream_t s, const uint8_t* src, int H, int W, int C, 
 {
     const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
     const size_t n = (size_t)Ho * Wo * C;
-    hipLaunchKernelGGL(k_pyramid_down, dim3(blocks(n, 256)), dim3(256), 0, s, src, H, W, C, Ho, Wo, dst);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_pyramid_down, dim3(blocks(n, 256)), dim3(256), 0, s, src, H, W, C, Ho, Wo, dst);
 }
 
 // A w = e_0, A the S x S tridiagonal matrix of the paper (diagonal 1 + lambda at both ends and 1 + 2 lambda between,
@@ -174,9 +172,8 @@ int launch_cross_scale_combine(hipStream_t s, const CrossScaleLaunch& l)
     const bool vec = l.W % 4 == 0 && l.W >= 64;
     const size_t lanes = (size_t)l.H * (vec ? l.W / 4 : l.W);
     if (vec)
-        hipLaunchKernelGGL(k_cross_scale_combine<4>, dim3(blocks(lanes, 256)), dim3(256), 0, s, a);
+        ASW_TRY(ASW_LAUNCH(k_cross_scale_combine<4>, dim3(blocks(lanes, 256)), dim3(256), 0, s, a));
     else
-        hipLaunchKernelGGL(k_cross_scale_combine<1>, dim3(blocks(lanes, 256)), dim3(256), 0, s, a);
-    ASW_HIP_TRY(hipGetLastError());
+        ASW_TRY(ASW_LAUNCH(k_cross_scale_combine<1>, dim3(blocks(lanes, 256)), dim3(256), 0, s, a));
     return ASW_OK;
 }

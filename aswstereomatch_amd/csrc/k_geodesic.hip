@@ -426,9 +426,7 @@ template <int WIN, typename OutT>
 int launch_weights_t(hipStream_t s, const uint32_t* img, int H, int W, int backward, int forward, OutT* planes)
 {
     dim3 grid((W + 63) / 64, H);
-    hipLaunchKernelGGL((k_geodesic_weights<WIN, OutT>), grid, dim3(64), 0, s, img, H, W, backward, forward, planes);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH((k_geodesic_weights<WIN, OutT>), grid, dim3(64), 0, s, img, H, W, backward, forward, planes);
 }
 
 template <typename OutT>
@@ -450,9 +448,7 @@ int launch_weights(hipStream_t s, const uint32_t* img, int H, int W, int win, in
 int launch_pack_bgrx(hipStream_t s, const uint8_t* bgr, int H, int W, uint32_t* out)
 {
     size_t n = (size_t)H * W;
-    hipLaunchKernelGGL(k_pack_bgrx, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, bgr, n, out);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_pack_bgrx, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, bgr, n, out);
 }
 
 int launch_geodesic_weights_u16(hipStream_t s, const uint32_t* img, int H, int W, int win, int iter, uint16_t* planes)
@@ -468,9 +464,7 @@ int launch_geodesic_weights_f32(hipStream_t s, const uint32_t* img, int H, int W
 int launch_planes_to_windows(hipStream_t s, const float* planes, int H, int W, int cells, float* out)
 {
     size_t n = (size_t)H * W * cells;
-    hipLaunchKernelGGL(k_planes_to_windows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, planes, (size_t)H * W, cells, out);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_planes_to_windows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, planes, (size_t)H * W, cells, out);
 }
 
 namespace {
@@ -486,8 +480,6 @@ int launch_geo_t(hipStream_t s, GeoParams p, const uint32_t* imgL, const uint32_
 {
     const size_t lds = geo_lds_bytes<GDC>(p.win);
     auto kern = k_asw_geodesic<GDC>;
-    if (lds > 64 * 1024)
-        ASW_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     dim3 grid((p.W + TW - 1) / TW, (p.H + TH - 1) / TH);
     // frames with few tiles (KITTI: 1880 for 1024 resident workgroups) split the candidate range over grid.z in
     // multiples of 16 until there are ~4096 workgroups; a second tiny launch merges the per-slice winners
@@ -498,8 +490,7 @@ int launch_geo_t(hipStream_t s, GeoParams p, const uint32_t* imgL, const uint32_
     nz = (chunks16 + chunks_per_z - 1) / chunks_per_z;
     p.cand_per_z = chunks_per_z * 16;
     grid.z = nz;
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, p, imgL, imgR, wL, wR, vol, disp, partE, partD);
-    ASW_HIP_TRY(hipGetLastError());
+    ASW_TRY(ASW_LAUNCH(kern, grid, dim3(256), lds, s, p, imgL, imgR, wL, wR, vol, disp, partE, partD));
     if (nz > 1) return launch_merge_slices(s, partE, partD, nz, (size_t)p.H * p.W, disp);
     return ASW_OK;
 }
@@ -522,8 +513,6 @@ int launch_asw_geodesic_few(hipStream_t s, const uint32_t* imgF, const uint32_t*
 {
     if (c_begin < 0 || c_begin >= nD || !outE || !outD) return ASW_ERR_BAD_ARGUMENT;
     dim3 grid((W + TW - 1) / TW, (H + TH - 1) / TH);
-    hipLaunchKernelGGL(k_asw_geodesic_few<15>, grid, dim3(256), 0, s, imgF, imgO, wF, wO, H, W, minD, c_begin, nD, right ? 1 : -1, vol,
-                       outE, outD);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_asw_geodesic_few<15>, grid, dim3(256), 0, s, imgF, imgO, wF, wO, H, W, minD, c_begin, nD, right ? 1 : -1, vol,
+                      outE, outD);
 }

@@ -324,26 +324,24 @@ int launch_pass(hipStream_t s, hipStream_t s_border, const GeoXqParams& base, co
     if (right) {  // border tile = the first of a row
         GeoXqParams p = base;
         p.tile0 = 0;
-        hipLaunchKernelGGL((k_asw_geodesic_xq<NWAVE, true, true>), dim3(1, H), dim3(64 * NWAVE), 0, s_border, p, imgL, imgR, wL, wR, vol, outE, outD);
+        ASW_TRY(ASW_LAUNCH((k_asw_geodesic_xq<NWAVE, true, true>), dim3(1, H), dim3(64 * NWAVE), 0, s_border, p, imgL, imgR, wL, wR, vol, outE, outD));
         if (ntiles > 1) {
             p.tile0 = 1;
-            hipLaunchKernelGGL((k_asw_geodesic_xq<NWAVE, false, true>), dim3(ntiles - 1, H), dim3(64 * NWAVE), 0, s, p, imgL, imgR, wL, wR, vol, outE, outD);
+            ASW_TRY(ASW_LAUNCH((k_asw_geodesic_xq<NWAVE, false, true>), dim3(ntiles - 1, H), dim3(64 * NWAVE), 0, s, p, imgL, imgR, wL, wR, vol, outE, outD));
         }
-        ASW_HIP_TRY(hipGetLastError());
         return ASW_OK;
     }
     const int n_int = W >= PXW + HH ? std::min(ntiles, (W - PXW - HH) / PXW + 1) : 0;  // x0 + 63 + 7 <= W - 1
     if (n_int > 0) {
         GeoXqParams p = base;
         p.tile0 = 0;
-        hipLaunchKernelGGL((k_asw_geodesic_xq<NWAVE, false, false>), dim3(n_int, H), dim3(64 * NWAVE), 0, s, p, imgL, imgR, wL, wR, vol, outE, outD);
+        ASW_TRY(ASW_LAUNCH((k_asw_geodesic_xq<NWAVE, false, false>), dim3(n_int, H), dim3(64 * NWAVE), 0, s, p, imgL, imgR, wL, wR, vol, outE, outD));
     }
     if (ntiles > n_int) {
         GeoXqParams p = base;
         p.tile0 = n_int;
-        hipLaunchKernelGGL((k_asw_geodesic_xq<NWAVE, true, false>), dim3(ntiles - n_int, H), dim3(64 * NWAVE), 0, s_border, p, imgL, imgR, wL, wR, vol, outE, outD);
+        ASW_TRY(ASW_LAUNCH((k_asw_geodesic_xq<NWAVE, true, false>), dim3(ntiles - n_int, H), dim3(64 * NWAVE), 0, s_border, p, imgL, imgR, wL, wR, vol, outE, outD));
     }
-    ASW_HIP_TRY(hipGetLastError());
     return ASW_OK;
 }
 

@@ -1178,9 +1178,7 @@ int launch_walk_t(hipStream_t s, const Src& src, const Dst& dst, int H, int W, i
     const int ngx = slice_par ? nxw : (nxw + 3) / 4, nby = (H + band - 1) / band, nzg = (nzs + spw - 1) / spw;
     const long long nwg = (long long)((ngx * nby + 7) / 8) * 8 * nzg;  // regions rounded up to a multiple of the 8 XCDs
     if (nwg > 0x7fffffffLL) return ASW_ERR_BAD_ARGUMENT;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(BW), lds, s, src, dst, H, W, k, band, nxw, n, ngx, nby, slice_par | (ring ? 0 : 2));
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(kern, dim3((unsigned)nwg), dim3(BW), lds, s, src, dst, H, W, k, band, nxw, n, ngx, nby, slice_par | (ring ? 0 : 2));
 }
 
 template <int NP, int ND = 1, bool NANSAFE = false, class Src, class Dst>
@@ -1648,10 +1646,9 @@ int launch_q6_pair(hipStream_t s, const GuidedLaunch& a, const GuideAccT<true>& 
     if (rc != ASW_OK) return rc;
     const size_t lds = 2 * 4 * (128 + 2) * sizeof(double) + 2 * 128 * sizeof(float);
     if (a.nan_safe)
-        hipLaunchKernelGGL(k_q6_pair<true>, dim3(nwg), dim3(128), lds, s, f);
+        ASW_TRY(ASW_LAUNCH(k_q6_pair<true>, dim3(nwg), dim3(128), lds, s, f));
     else
-        hipLaunchKernelGGL(k_q6_pair<false>, dim3(nwg), dim3(128), lds, s, f);
-    ASW_HIP_TRY(hipGetLastError());
+        ASW_TRY(ASW_LAUNCH(k_q6_pair<false>, dim3(nwg), dim3(128), lds, s, f));
     return ASW_OK;
 }
 
@@ -1914,10 +1911,9 @@ int launch_ab6_pair(hipStream_t s, const GuidedLaunch& a, const GuideAccT<true>&
     if (rc != ASW_OK) return rc;
     const size_t lds = 2 * 4 * (128 + 2) * sizeof(double) + 2 * 128 * sizeof(float);
     if (a.nan_safe)
-        hipLaunchKernelGGL(k_ab6_pair<true>, dim3(nwg), dim3(128), lds, s, f);
+        ASW_TRY(ASW_LAUNCH(k_ab6_pair<true>, dim3(nwg), dim3(128), lds, s, f));
     else
-        hipLaunchKernelGGL(k_ab6_pair<false>, dim3(nwg), dim3(128), lds, s, f);
-    ASW_HIP_TRY(hipGetLastError());
+        ASW_TRY(ASW_LAUNCH(k_ab6_pair<false>, dim3(nwg), dim3(128), lds, s, f));
     return ASW_OK;
 }
 
@@ -1929,9 +1925,7 @@ int launch_guided_fused3(hipStream_t s, const GuidedLaunch& a, const GuideAccT<f
     const int rc = pair_geometry(f, 128 - 28, 60, band_opt >= 30 ? band_opt : 0, &nwg);
     if (rc != ASW_OK) return rc;
     const size_t lds = 2 * 4 * (128 + 2) * sizeof(double) + 2 * 4 * 128 * sizeof(float);
-    hipLaunchKernelGGL(k_guided_pair3, dim3(nwg), dim3(128), lds, s, f);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_guided_pair3, dim3(nwg), dim3(128), lds, s, f);
 }
 
 // the 3-channel guided filter (statistics, a/b, q) on the planar layouts, the two big passes in the forms AswTuning selects
@@ -2041,7 +2035,7 @@ int launch_guided(hipStream_t s, const GuidedLaunch& a)
         if (rc != ASW_OK) return rc;
     } else {
         // GuidedF / GuidedF_3: [fixed image, other image shifted by d].  See StatsSplit.
-        hipLaunchKernelGGL(k_scale_groups, dim3((a.n + 255) / 256), dim3(256), 0, s, a.gscales, a.n, a.rep_scratch);
+        ASW_TRY(ASW_LAUNCH(k_scale_groups, dim3((a.n + 255) / 256), dim3(256), 0, s, a.gscales, a.n, a.rep_scratch));
         sp.rep = a.rep_scratch;
         sp.shifted = a.shiftA != 0 ? 0 : 1;
         sp.sgn = a.shiftA != 0 ? a.shiftA : a.shiftB;
@@ -2101,9 +2095,7 @@ __global__ __launch_bounds__(256) void k_pack_words(const uint8_t* __restrict__ 
 int launch_pack_words(hipStream_t s, const uint8_t* img, int H, int W, int C, int w, uint32_t* out)
 {
     size_t n = (size_t)H * W;
-    hipLaunchKernelGGL(k_pack_words, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, img, n, C, w, out);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_pack_words, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, img, n, C, w, out);
 }
 
 // one [slot][H][W][8] array for a 3-channel guide; three for a 6-channel guide (word A, word B, unshifted word: StatsSplit)

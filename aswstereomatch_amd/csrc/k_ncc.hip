@@ -146,16 +146,12 @@ __global__ __launch_bounds__(256) void k_apply_scales(float* __restrict__ vol, s
 int launch_pad_gray(hipStream_t s, const uint8_t* g, int H, int W, int padL, int padR, uint8_t* out)
 {
     const int Wp = W + padL + padR;
-    hipLaunchKernelGGL(k_pad_gray, dim3((Wp + 255) / 256, H), dim3(256), 0, s, g, H, W, padL, Wp, out);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_pad_gray, dim3((Wp + 255) / 256, H), dim3(256), 0, s, g, H, W, padL, Wp, out);
 }
 
 int launch_ncc_selfsum(hipStream_t s, const uint8_t* g, const float* mean, int H, int W, int win, double* ss)
 {
-    hipLaunchKernelGGL(k_ncc_selfsum, dim3((W + 255) / 256, H), dim3(256), 0, s, g, mean, H, W, win, ss);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_ncc_selfsum, dim3((W + 255) / 256, H), dim3(256), 0, s, g, mean, H, W, win, ss);
 }
 
 // the reference tile and one chunk's tile of the other image, f32; no opt-in above 64 KB: the kernel is not built for it
@@ -183,10 +179,9 @@ int launch_ncc(hipStream_t s, const NccLaunch& a)
     if (!ncc_fits(a.win)) return ASW_ERR_BAD_ARGUMENT;
     dim3 grid((a.W + NTW - 1) / NTW, (a.H + NTH - 1) / NTH);
     if (a.right)
-        hipLaunchKernelGGL(k_ncc<true>, grid, dim3(256), lds, s, p, a.gref, a.mref, a.sref, a.goth, a.moth, a.soth, a.vol, a.disp);
+        ASW_TRY(ASW_LAUNCH(k_ncc<true>, grid, dim3(256), lds, s, p, a.gref, a.mref, a.sref, a.goth, a.moth, a.soth, a.vol, a.disp));
     else
-        hipLaunchKernelGGL(k_ncc<false>, grid, dim3(256), lds, s, p, a.gref, a.mref, a.sref, a.goth, a.moth, a.soth, a.vol, a.disp);
-    ASW_HIP_TRY(hipGetLastError());
+        ASW_TRY(ASW_LAUNCH(k_ncc<false>, grid, dim3(256), lds, s, p, a.gref, a.mref, a.sref, a.goth, a.moth, a.soth, a.vol, a.disp));
     return ASW_OK;
 }
 
@@ -195,7 +190,5 @@ int launch_apply_scales(hipStream_t s, float* vol, int n, size_t plane, const fl
     int bx = (int)((plane + 256 * 8 - 1) / (256 * 8));
     if (bx > 256) bx = 256;
     if (bx < 1) bx = 1;
-    hipLaunchKernelGGL(k_apply_scales, dim3(bx, n), dim3(256), 0, s, vol, plane, scales);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_apply_scales, dim3(bx, n), dim3(256), 0, s, vol, plane, scales);
 }

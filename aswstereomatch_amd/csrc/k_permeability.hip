@@ -291,26 +291,20 @@ int launch_perm_weights(hipStream_t s, const uint8_t* img, int H, int W, int C, 
 {
     if (H < 1 || W < 1 || (C != 1 && C != 3) || (size_t)H * W >= ((size_t)1 << 31)) return ASW_ERR_BAD_ARGUMENT;
     const int Wp = perm_padded(W), Hp = perm_padded(H);
-    hipLaunchKernelGGL(k_perm_weights_h, dim3((unsigned)((size_t)((Wp + 255) / 256) * H)), dim3(256), 0, s, img, H, W, C, Wp, P, ph);
-    hipLaunchKernelGGL(k_perm_weights_v, dim3((unsigned)((size_t)((Hp + 63) / 64) * ((W + 3) / 4))), dim3(256), 0, s, img, H, W, C, Hp, P, pvT);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    ASW_TRY(ASW_LAUNCH(k_perm_weights_h, dim3((unsigned)((size_t)((Wp + 255) / 256) * H)), dim3(256), 0, s, img, H, W, C, Wp, P, ph));
+    return ASW_LAUNCH(k_perm_weights_v, dim3((unsigned)((size_t)((Hp + 63) / 64) * ((W + 3) / 4))), dim3(256), 0, s, img, H, W, C, Hp, P, pvT);
 }
 
 int launch_perm_scan_h(hipStream_t s, const PermLaunch& a)
 {
     if (check(a) != ASW_OK) return ASW_ERR_BAD_ARGUMENT;
-    hipLaunchKernelGGL(k_perm_scan_h, dim3(a.H, (a.nc + 63) / 64), dim3(64), 0, s, params(a), a.cost, a.ph, a.ck, a.hs);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_perm_scan_h, dim3(a.H, (a.nc + 63) / 64), dim3(64), 0, s, params(a), a.cost, a.ph, a.ck, a.hs);
 }
 
 int launch_perm_scan_v(hipStream_t s, const PermLaunch& a)
 {
     if (check(a) != ASW_OK) return ASW_ERR_BAD_ARGUMENT;
     if (!a.N && (a.nc != 1 || !a.Nout)) return ASW_ERR_BAD_ARGUMENT;
-    hipLaunchKernelGGL(k_perm_scan_v, dim3((a.W + XW - 1) / XW), dim3(XW * 64), 0, s, params(a), a.cbeg, a.minD, a.first, a.hs, a.pvT,
-                       a.ck, a.N, a.Nout, a.vol, a.bestE, a.disp);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_perm_scan_v, dim3((a.W + XW - 1) / XW), dim3(XW * 64), 0, s, params(a), a.cbeg, a.minD, a.first, a.hs, a.pvT,
+                      a.ck, a.N, a.Nout, a.vol, a.bestE, a.disp);
 }

@@ -179,7 +179,7 @@ int launch_resize_linear(hipStream_t s, const uint8_t* src, int sh, int sw, uint
     const int isx = (int)lrint(scale_x), isy = (int)lrint(scale_y);
     dim3 grid((dw + 255) / 256, dh);
     if (fabs(scale_x - isx) < 2.220446049250313e-16 && fabs(scale_y - isy) < 2.220446049250313e-16 && isx == 2 && isy == 2) {
-        hipLaunchKernelGGL(k_resize_area2, grid, dim3(256), 0, s, src, sw, dst, dh, dw);
+        ASW_TRY(ASW_LAUNCH(k_resize_area2, grid, dim3(256), 0, s, src, sw, dst, dh, dw));
     } else {
         int xmax = dw;  // first destination column whose source pair would leave the image (resize.cpp: xmax)
         for (int dx = 0; dx < dw; dx++) {
@@ -188,35 +188,29 @@ int launch_resize_linear(hipStream_t s, const uint8_t* src, int sh, int sw, uint
             if (sx < 0) sx = 0;
             if (sx + 1 >= sw) { xmax = dx; break; }
         }
-        hipLaunchKernelGGL(k_resize_linear, grid, dim3(256), 0, s, src, sh, sw, dst, dh, dw, scale_x, scale_y, xmax);
+        ASW_TRY(ASW_LAUNCH(k_resize_linear, grid, dim3(256), 0, s, src, sh, sw, dst, dh, dw, scale_x, scale_y, xmax));
     }
-    ASW_HIP_TRY(hipGetLastError());
     return ASW_OK;
 }
 
 int launch_bgr2hsv(hipStream_t s, const uint8_t* bgr, size_t n, const int* sdiv, const int* hdiv, uint8_t* hsv)
 {
-    hipLaunchKernelGGL(k_bgr2hsv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, bgr, n, sdiv, hdiv, hsv);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_bgr2hsv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, bgr, n, sdiv, hdiv, hsv);
 }
 
 int launch_boost_hsv2bgr(hipStream_t s, const uint8_t* hsv, int H, int W, const int* taps, int ntaps, const float* color_lut,
                          uint8_t* bgr)
 {
-    hipLaunchKernelGGL(k_boost_hsv2bgr, dim3((W + 255) / 256, H), dim3(256), 0, s, hsv, H, W, taps, ntaps, color_lut, bgr);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_boost_hsv2bgr, dim3((W + 255) / 256, H), dim3(256), 0, s, hsv, H, W, taps, ntaps, color_lut, bgr);
 }
 
 int launch_disp_to_u8(hipStream_t s, const float* disp, size_t n, int normalize, uint8_t* out, int* mm_scratch)
 {
-    hipLaunchKernelGGL(k_set2, dim3(1), dim3(1), 0, s, mm_scratch, 255, 0);
+    ASW_TRY(ASW_LAUNCH(k_set2, dim3(1), dim3(1), 0, s, mm_scratch, 255, 0));
     int bx = (int)((n + 256 * 8 - 1) / (256 * 8));
     if (bx > 1024) bx = 1024;
     if (bx < 1) bx = 1;
-    hipLaunchKernelGGL(k_disp_to_u8, dim3(bx), dim3(256), 0, s, disp, n, out, mm_scratch);
-    if (normalize) hipLaunchKernelGGL(k_norm_u8, dim3(bx), dim3(256), 0, s, out, n, mm_scratch);
-    ASW_HIP_TRY(hipGetLastError());
+    ASW_TRY(ASW_LAUNCH(k_disp_to_u8, dim3(bx), dim3(256), 0, s, disp, n, out, mm_scratch));
+    if (normalize) ASW_TRY(ASW_LAUNCH(k_norm_u8, dim3(bx), dim3(256), 0, s, out, n, mm_scratch));
     return ASW_OK;
 }

@@ -207,18 +207,17 @@ int launch_refine(hipStream_t s, const RefineLaunch& a)
     if (a.win < 1 || a.win > 35) return ASW_ERR_BAD_ARGUMENT;  // 32-bit sums; also keeps the dynamic LDS under 64 KB
     const size_t lds = refine_median_lds_bytes(a.win, a.ntc);
     ASW_HIP_TRY(hipMemsetAsync(a.counters, 0, 3 * sizeof(unsigned), s));
-    hipLaunchKernelGGL(k_refine_check, dim3((W + 64 * RF_CHECK_CHUNKS - 1) / (64 * RF_CHECK_CHUNKS), (H + 3) / 4), dim3(256), 0, s, a.dl, a.dr, H, W, a.minD, a.n, a.max_diff,
-                       a.mask, a.counters);
-    hipLaunchKernelGGL(k_refine_fill, dim3((H + 3) / 4), dim3(256), 0, s, a.dl, a.mask, H, W, a.minD, a.F, a.out, a.counters);
+    ASW_TRY(ASW_LAUNCH(k_refine_check, dim3((W + 64 * RF_CHECK_CHUNKS - 1) / (64 * RF_CHECK_CHUNKS), (H + 3) / 4), dim3(256), 0, s, a.dl, a.dr, H, W, a.minD, a.n, a.max_diff,
+                       a.mask, a.counters));
+    ASW_TRY(ASW_LAUNCH(k_refine_fill, dim3((H + 3) / 4), dim3(256), 0, s, a.dl, a.mask, H, W, a.minD, a.F, a.out, a.counters));
     if (a.win > 1) {  // win = 1: the centre tap alone, the median is the fill
         const dim3 grid((W + RF_TW - 1) / RF_TW, (H + RF_TH - 1) / RF_TH);
         if (a.C == 3)
-            hipLaunchKernelGGL(k_refine_median<3>, grid, dim3(256), lds, s, a.guide, a.F, a.mask, H, W, a.win / 2, a.minD, a.tc, a.ntc,
-                               a.ts, a.out);
+            ASW_TRY(ASW_LAUNCH(k_refine_median<3>, grid, dim3(256), lds, s, a.guide, a.F, a.mask, H, W, a.win / 2, a.minD, a.tc, a.ntc,
+                               a.ts, a.out));
         else
-            hipLaunchKernelGGL(k_refine_median<1>, grid, dim3(256), lds, s, a.guide, a.F, a.mask, H, W, a.win / 2, a.minD, a.tc, a.ntc,
-                               a.ts, a.out);
+            ASW_TRY(ASW_LAUNCH(k_refine_median<1>, grid, dim3(256), lds, s, a.guide, a.F, a.mask, H, W, a.win / 2, a.minD, a.tc, a.ntc,
+                               a.ts, a.out));
     }
-    ASW_HIP_TRY(hipGetLastError());
     return ASW_OK;
 }

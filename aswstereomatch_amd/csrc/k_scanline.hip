@@ -286,11 +286,9 @@ int launch_scanline(hipStream_t s, const ScanlineLaunch& a)
     if (!p.tc || !v.tc) return ASW_ERR_BAD_ARGUMENT;
     p.tc_log2 = __builtin_ctz(p.tc); v.tc_log2 = __builtin_ctz(v.tc);
     v.xw = std::min(v.tc, XW_MAX); v.xw_log2 = __builtin_ctz(v.xw);
-    hipLaunchKernelGGL(k_scanline_h, dim3(a.H), dim3(64), h_bytes(a.n, p.tc), s, p, a.vol, a.sum, a.ck);
+    ASW_TRY(ASW_LAUNCH(k_scanline_h, dim3(a.H), dim3(64), h_bytes(a.n, p.tc), s, p, a.vol, a.sum, a.ck));
     const dim3 grid((a.W + v.xw - 1) / v.xw), block(v.xw * 64);
     const size_t vb = v_bytes(a.n, v.tc, v.xw);
-    hipLaunchKernelGGL(k_scanline_v<false>, grid, block, vb, s, v, a.vol, a.sum, a.disp);
-    hipLaunchKernelGGL(k_scanline_v<true>, grid, block, vb, s, v, a.vol, a.sum, a.disp);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    ASW_TRY(ASW_LAUNCH(k_scanline_v<false>, grid, block, vb, s, v, a.vol, a.sum, a.disp));
+    return ASW_LAUNCH(k_scanline_v<true>, grid, block, vb, s, v, a.vol, a.sum, a.disp);
 }

@@ -540,22 +540,18 @@ int launch_paths(hipStream_t s, const SgbmLaunch& a, const int* hb, int* C, int*
 {
     const int H = a.H, W = a.W, minD = a.minD, D = a.D, h = a.w / 2, P1 = a.P1, P2 = a.P2, paths = a.paths;
     const int Wv = W - (minD + D);
-    hipLaunchKernelGGL(k_sgbm_top<NPL>, dim3(Wv), dim3(64), 2 * D * sizeof(int), s, hb, H, Wv, D, h, P1, P2, C, T);
-    ASW_HIP_TRY(hipGetLastError());
+    ASW_TRY(ASW_LAUNCH(k_sgbm_top<NPL>, dim3(Wv), dim3(64), 2 * D * sizeof(int), s, hb, H, Wv, D, h, P1, P2, C, T));
     // the directions beyond the three of k_sgbm_top / k_sgbm_row: one launch per line geometry, stream order between them
     const int dirs[3] = {paths & ASW_SGBM_PATH_BT ? 2 : 0,
                          (paths & ASW_SGBM_PATH_TLBR ? 1 : 0) | (paths & ASW_SGBM_PATH_BRTL ? 2 : 0),
                          (paths & ASW_SGBM_PATH_TRBL ? 1 : 0) | (paths & ASW_SGBM_PATH_BLTR ? 2 : 0)};
     for (int geom = 0; geom < 3; geom++) {
         if (!dirs[geom]) continue;
-        hipLaunchKernelGGL(k_sgbm_line<NPL>, dim3(geom == 0 ? Wv : H + Wv - 1), dim3(64), 2 * D * sizeof(int), s, C, T, H, Wv, D, P1,
-                           P2, geom, dirs[geom]);
-        ASW_HIP_TRY(hipGetLastError());
+        ASW_TRY(ASW_LAUNCH(k_sgbm_line<NPL>, dim3(geom == 0 ? Wv : H + Wv - 1), dim3(64), 2 * D * sizeof(int), s, C, T, H, Wv, D, P1,
+                           P2, geom, dirs[geom]));
     }
-    hipLaunchKernelGGL(k_sgbm_row<NPL>, dim3(H), dim3(64), 4 * D * sizeof(int), s, C, T, H, W, minD, D, P1, P2, a.U, a.vol != nullptr,
-                       disp_raw, key);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_sgbm_row<NPL>, dim3(H), dim3(64), 4 * D * sizeof(int), s, C, T, H, W, minD, D, P1, P2, a.U, a.vol != nullptr,
+                      disp_raw, key);
 }
 
 // the census cost stage of asw_sgbm_census: a.L / a.R are the gray planes; codes: room for two code planes (8 bytes a pixel each)
@@ -569,10 +565,6 @@ int launch_hcost_census(hipStream_t s, const SgbmLaunch& a, unsigned long long* 
     ASW_TRY(launch_census_transform(s, a.L, H, W, reinterpret_cast<uint2*>(codeL)));
     ASW_TRY(launch_census_transform(s, a.R, H, W, reinterpret_cast<uint2*>(codeR)));
     const size_t lds = (size_t)W * 16;
-    if (lds > 160 * 1024) return ASW_ERR_BAD_ARGUMENT;
-    if (lds > 64 * 1024)
-        ASW_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sgbm_hcost_census), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)lds));
     // A row alone gives D threads work: few rows or few candidates leave the chip idle, so the valid columns are cut into
     // segments until there are about 2048 workgroups.  A segment pays 2 h + 1 terms for its seed: none is shorter than twice that.
     const int spb = 256 / std::min(D, 256);
@@ -580,9 +572,7 @@ int launch_hcost_census(hipStream_t s, const SgbmLaunch& a, unsigned long long* 
     const int nseg = std::max(1, std::min(want, Wv / std::max(32, 2 * (2 * h + 1))));
     const int seglen = (Wv + nseg - 1) / nseg;
     const unsigned gy = (unsigned)((Wv + seglen * spb - 1) / (seglen * spb));
-    hipLaunchKernelGGL(k_sgbm_hcost_census, dim3(H, gy), dim3(256), lds, s, codeL, codeR, W, a.minD, D, h, seglen, hb);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_sgbm_hcost_census, dim3(H, gy), dim3(256), lds, s, codeL, codeR, W, a.minD, D, h, seglen, hb);
 }
 
 }  // namespace
@@ -622,23 +612,18 @@ int launch_sgbm(hipStream_t s, const SgbmLaunch& a)
     if (a.census) {
         ASW_TRY(launch_hcost_census(s, a, (unsigned long long*)pf, hb));
     } else {
-        hipLaunchKernelGGL(k_sgbm_prefilter, dim3(blocks(plane, 256)), dim3(256), 0, s, a.L, a.R, H, W, a.cn, a.ftzero, pf);
-        ASW_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_sgbm_hcost, dim3(blocks((size_t)H * D, 256)), dim3(256), 0, s, pf, H, W, a.cn, minD, D, a.w / 2, hb);
-        ASW_HIP_TRY(hipGetLastError());
+        ASW_TRY(ASW_LAUNCH(k_sgbm_prefilter, dim3(blocks(plane, 256)), dim3(256), 0, s, a.L, a.R, H, W, a.cn, a.ftzero, pf));
+        ASW_TRY(ASW_LAUNCH(k_sgbm_hcost, dim3(blocks((size_t)H * D, 256)), dim3(256), 0, s, pf, H, W, a.cn, minD, D, a.w / 2, hb));
     }
     ASW_HIP_TRY(hipMemsetAsync(key, 0xff, plane * 8, s));
     if (a.ev_agg0) ASW_HIP_TRY(hipEventRecord(a.ev_agg0, s));
     ASW_TRY(dispatch_npl(D, [&](auto npl) { return launch_paths<decltype(npl)::value>(s, a, hb, C, T, disp_raw, key); }));
     if (a.ev_agg1) ASW_HIP_TRY(hipEventRecord(a.ev_agg1, s));
     if (a.vol) {
-        hipLaunchKernelGGL(k_sgbm_volume, dim3(blocks(plane * D, 256)), dim3(256), 0, s, T, H, W, minD, D, a.vol);
-        ASW_HIP_TRY(hipGetLastError());
+        ASW_TRY(ASW_LAUNCH(k_sgbm_volume, dim3(blocks(plane * D, 256)), dim3(256), 0, s, T, H, W, minD, D, a.vol));
     }
-    hipLaunchKernelGGL(k_sgbm_lr, dim3(blocks(plane, 256)), dim3(256), 0, s, disp_raw, key, H, W, minD, D, a.M, lr);
-    ASW_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_median3_s16, dim3(blocks(plane, 256)), dim3(256), 0, s, lr, H, W, a.disp16);
-    ASW_HIP_TRY(hipGetLastError());
+    ASW_TRY(ASW_LAUNCH(k_sgbm_lr, dim3(blocks(plane, 256)), dim3(256), 0, s, disp_raw, key, H, W, minD, D, a.M, lr));
+    ASW_TRY(ASW_LAUNCH(k_median3_s16, dim3(blocks(plane, 256)), dim3(256), 0, s, lr, H, W, a.disp16));
     if (a.speckle_window > 0)
         ASW_TRY(launch_filter_speckles(s, a.disp16, H, W, INVALID, a.speckle_window, 16 * a.speckle_range, spk));
     return ASW_OK;
@@ -649,34 +634,24 @@ int launch_filter_speckles(hipStream_t s, short* img, int H, int W, int new_val,
     const size_t n = (size_t)H * W;
     int* parent = scratch;
     int* size = scratch + n;
-    hipLaunchKernelGGL(k_spk_init, dim3(blocks(n, 256)), dim3(256), 0, s, img, n, new_val, parent, size);
-    ASW_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_spk_union, dim3(blocks(n, 256)), dim3(256), 0, s, img, H, W, new_val, max_diff, parent);
-    ASW_HIP_TRY(hipGetLastError());
+    ASW_TRY(ASW_LAUNCH(k_spk_init, dim3(blocks(n, 256)), dim3(256), 0, s, img, n, new_val, parent, size));
+    ASW_TRY(ASW_LAUNCH(k_spk_union, dim3(blocks(n, 256)), dim3(256), 0, s, img, H, W, new_val, max_diff, parent));
     for (size_t span = 1; span < n; span *= 2) {
-        hipLaunchKernelGGL(k_spk_jump, dim3(blocks(n, 256)), dim3(256), 0, s, n, parent);
-        ASW_HIP_TRY(hipGetLastError());
+        ASW_TRY(ASW_LAUNCH(k_spk_jump, dim3(blocks(n, 256)), dim3(256), 0, s, n, parent));
     }
-    hipLaunchKernelGGL(k_spk_flatten, dim3(blocks(n, 256)), dim3(256), 0, s, n, parent, size);
-    ASW_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_spk_apply, dim3(blocks(n, 256)), dim3(256), 0, s, img, n, new_val, max_size, parent, size);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    ASW_TRY(ASW_LAUNCH(k_spk_flatten, dim3(blocks(n, 256)), dim3(256), 0, s, n, parent, size));
+    return ASW_LAUNCH(k_spk_apply, dim3(blocks(n, 256)), dim3(256), 0, s, img, n, new_val, max_size, parent, size);
 }
 
 int launch_fill_s16(hipStream_t s, short* out, size_t n, short v)
 {
-    hipLaunchKernelGGL(k_fill_s16, dim3(blocks(n, 256)), dim3(256), 0, s, out, n, v);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_fill_s16, dim3(blocks(n, 256)), dim3(256), 0, s, out, n, v);
 }
 
 template <typename T>
 static int launch_disp16_convert(hipStream_t s, const short* disp16, size_t n, T* out)
 {
-    hipLaunchKernelGGL(k_disp16_to_u8<T>, dim3(blocks(n, 256)), dim3(256), 0, s, disp16, n, out);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_disp16_to_u8<T>, dim3(blocks(n, 256)), dim3(256), 0, s, disp16, n, out);
 }
 
 int launch_disp16_to_u8f(hipStream_t s, const short* disp16, size_t n, float* out) { return launch_disp16_convert(s, disp16, n, out); }

@@ -40,11 +40,10 @@ int launch_subpixel(hipStream_t s, int mode, const float* vol, int n, int H, int
     const size_t plane = (size_t)H * W;
     const dim3 grid((unsigned)((plane + 255) / 256));
     if (mode == ASW_DISPARITY_SUBPIXEL_PARABOLA)
-        hipLaunchKernelGGL(k_subpixel<ASW_DISPARITY_SUBPIXEL_PARABOLA>, grid, dim3(256), 0, s, vol, n, plane, minD, disp);
+        ASW_TRY(ASW_LAUNCH(k_subpixel<ASW_DISPARITY_SUBPIXEL_PARABOLA>, grid, dim3(256), 0, s, vol, n, plane, minD, disp));
     else if (mode == ASW_DISPARITY_SUBPIXEL_EQUIANGULAR)
-        hipLaunchKernelGGL(k_subpixel<ASW_DISPARITY_SUBPIXEL_EQUIANGULAR>, grid, dim3(256), 0, s, vol, n, plane, minD, disp);
+        ASW_TRY(ASW_LAUNCH(k_subpixel<ASW_DISPARITY_SUBPIXEL_EQUIANGULAR>, grid, dim3(256), 0, s, vol, n, plane, minD, disp));
     else
         return ASW_ERR_BAD_ARGUMENT;
-    ASW_HIP_TRY(hipGetLastError());
     return ASW_OK;
 }

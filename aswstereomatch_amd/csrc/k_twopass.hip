@@ -213,12 +213,6 @@ int launch_twopass(hipStream_t s, const TwoPassLaunch& a)
     TwoPassParams p;
     p.H = a.H; p.W = a.W; p.h = a.win / 2; p.minD = a.minD; p.nD = a.nD; p.flip = a.flip;
     const Layout lay(p.h);
-    // on every such launch, on purpose: the attribute is per device, and the batch scheduler runs one context per device -- a
-    // once-per-process flag would leave the second device without it
-    if (lay.total > 64 * 1024)
-        ASW_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_asw_twopass), hipFuncAttributeMaxDynamicSharedMemorySize, lay.total));
     const dim3 grid((a.W + TW - 1) / TW, (a.H + TH - 1) / TH);
-    hipLaunchKernelGGL(k_asw_twopass, grid, dim3(256), lay.total, s, p, a.gL, a.gR, a.table, a.vol, a.disp);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_asw_twopass, grid, dim3(256), lay.total, s, p, a.gL, a.gR, a.table, a.vol, a.disp);
 }

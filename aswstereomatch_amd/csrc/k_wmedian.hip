@@ -248,9 +248,7 @@ int launch_wm_weights(hipStream_t s, const uint8_t* img, int H, int W, int pad, 
                       float* out)
 {
     size_t n = (size_t)H * (W + pad) * win * win;
-    hipLaunchKernelGGL(k_wm_weights, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, img, H, W, pad, win, lut2, wd, out);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_wm_weights, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, img, H, W, pad, win, lut2, wd, out);
 }
 
 int launch_wmedian(hipStream_t s, const float* cost, const float* wLd, const float* wRb, int H, int W, int win, int numD,
@@ -263,16 +261,13 @@ int launch_wmedian(hipStream_t s, const float* cost, const float* wLd, const flo
         const int kpl = n <= 512 ? 8 : (n <= 1024 ? 16 : 32);
         const size_t lds = (size_t)64 * kpl * 12;
         if (kpl == 8)
-            hipLaunchKernelGGL(k_wmedian_big<8>, dim3((unsigned)npix), dim3(64), lds, s, cost, wLd, wRb, H, W, win, numD, max_off, out);
+            ASW_TRY(ASW_LAUNCH(k_wmedian_big<8>, dim3((unsigned)npix), dim3(64), lds, s, cost, wLd, wRb, H, W, win, numD, max_off, out));
         else if (kpl == 16)
-            hipLaunchKernelGGL(k_wmedian_big<16>, dim3((unsigned)npix), dim3(64), lds, s, cost, wLd, wRb, H, W, win, numD, max_off, out);
+            ASW_TRY(ASW_LAUNCH(k_wmedian_big<16>, dim3((unsigned)npix), dim3(64), lds, s, cost, wLd, wRb, H, W, win, numD, max_off, out));
         else
-            hipLaunchKernelGGL(k_wmedian_big<32>, dim3((unsigned)npix), dim3(64), lds, s, cost, wLd, wRb, H, W, win, numD, max_off, out);
-        ASW_HIP_TRY(hipGetLastError());
+            ASW_TRY(ASW_LAUNCH(k_wmedian_big<32>, dim3((unsigned)npix), dim3(64), lds, s, cost, wLd, wRb, H, W, win, numD, max_off, out));
         return ASW_OK;
     }
-    hipLaunchKernelGGL(k_wmedian, dim3((unsigned)((npix + WM_WAVES - 1) / WM_WAVES)), dim3(256), 0, s, cost, wLd, wRb, H, W, win,
-                       numD, max_off, out);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(k_wmedian, dim3((unsigned)((npix + WM_WAVES - 1) / WM_WAVES)), dim3(256), 0, s, cost, wLd, wRb, H, W, win,
+                      numD, max_off, out);
 }

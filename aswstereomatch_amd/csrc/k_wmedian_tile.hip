@@ -288,10 +288,8 @@ int launch_wmedian_tile(hipStream_t s, const float* cost, const float* wLd, cons
 {
     if (d_count <= 0 || d_begin < 0 || d_begin + d_count > numD) return ASW_ERR_BAD_ARGUMENT;
     const int nbx = (W + BW - 1) / BW, nby = (H + BH - 1) / BH;
-    hipLaunchKernelGGL(k_wm_sort_regions, dim3((unsigned)(nbx * nby), (unsigned)((d_count + 3) / 4)), dim3(256), 0, s, cost, H, W, nbx,
-                       d_begin, d_count, listC, listP);
-    hipLaunchKernelGGL(k_wm_pick, dim3((unsigned)(nbx * nby * NSPLIT)), dim3(64 * PICK_WAVES), 0, s, wLd, wRb, listC, listP, H, W, nbx,
-                       numD, max_off, d_begin, d_count, out);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    ASW_TRY(ASW_LAUNCH(k_wm_sort_regions, dim3((unsigned)(nbx * nby), (unsigned)((d_count + 3) / 4)), dim3(256), 0, s, cost, H, W, nbx,
+                       d_begin, d_count, listC, listP));
+    return ASW_LAUNCH(k_wm_pick, dim3((unsigned)(nbx * nby * NSPLIT)), dim3(64 * PICK_WAVES), 0, s, wLd, wRb, listC, listP, H, W, nbx,
+                      numD, max_off, d_begin, d_count, out);
 }

@@ -225,18 +225,13 @@ int launch_t(hipStream_t s, const float* cost, const float* wLd, const float* wR
 {
     const int nbx = (W + BW - 1) / BW, nby = (H + BH - 1) / BH;
     const unsigned nb = (unsigned)(nbx * nby);
-    hipLaunchKernelGGL((k_wmg_sort<KPL>), dim3(nb, (unsigned)((d_count + 3) / 4)), dim3(256), 0, s, cost, H, W, win, nbx, d_begin,
-                       d_count, listC, listP);
+    ASW_TRY(ASW_LAUNCH((k_wmg_sort<KPL>), dim3(nb, (unsigned)((d_count + 3) / 4)), dim3(256), 0, s, cost, H, W, win, nbx, d_begin,
+                       d_count, listC, listP));
     const int NC = win * win, wls = (NC + 1 + 3) & ~3, nparts = BH / rpp;
     const size_t lds = ((size_t)(BW * rpp + NW) * wls) * 4 + (((size_t)win * 64 + 1) * 2 + 15) / 16 * 16;
     auto kern = k_wmg_pick<KPL, NW, WPE>;
-    if (lds > 160 * 1024) return ASW_ERR_BAD_ARGUMENT;
-    if (lds > 64 * 1024)
-        ASW_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(nb * (unsigned)nparts), dim3(64 * NW), lds, s, wLd, wRb, listC, listP, H, W, win, nbx, nparts, rpp, numD,
-                       max_off, d_begin, d_count, out);
-    ASW_HIP_TRY(hipGetLastError());
-    return ASW_OK;
+    return ASW_LAUNCH(kern, dim3(nb * (unsigned)nparts), dim3(64 * NW), lds, s, wLd, wRb, listC, listP, H, W, win, nbx, nparts, rpp, numD,
+                      max_off, d_begin, d_count, out);
 }
 
 }  // namespace

@@ -9,8 +9,8 @@ The references: the CPU oracle for computeAD / TAD / SD and winnerTakeAll, tests
 AD-Census matcher, tests/cross_ref.py over the ORACLE's AD volume for entry 12 (tests/test_gpu_cross.py feeds it ctx.computeAD by
 design; here the raw cost is the thing under test).
 
-Order: every launch that asks for at most 64 KB of LDS comes first; the launches between 64 KB and 160 KB follow.  Neither launcher
-sets hipFuncAttributeMaxDynamicSharedMemorySize; a runtime that refused such a launch would give status ERR_HIP, a failure here."""
+Order: every launch that asks for at most 64 KB of LDS comes first; the launches between 64 KB and 160 KB follow: those
+take the library's opt-in above 64 KB (ASW_LAUNCH); a refused launch would give status ERR_HIP, a failure here."""
 import os
 import sys
 
