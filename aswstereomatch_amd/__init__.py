@@ -259,75 +259,71 @@ class Context:
 
     # ---- whole-method entry point (M.h:91-92) ----
     def stereoMatching(self, srcLeft, srcRight, disparityType, algorithmType, winSize=15, minDisparity=0,
-                       numDisparity=64, return_cost_volume=False, subpixel=None, cross_scale=None, scanline=None):
+                       numDisparity=64, return_cost_volume=False, subpixel=None, cross_scale=None, scanline=None,
+                       return_confidence=False):
         """subpixel: None, SUBPIXEL_PARABOLA or SUBPIXEL_EQUIANGULAR; cross_scale: None or a cross_scale() value; scanline: None or
-        a scanline() value (not together with cross_scale); all are OR-ed into disparityType."""
+        a scanline() value (not together with cross_scale); all are OR-ed into disparityType.  return_confidence: also the
+        per-pixel confidence in [0, 1] of the volume the call returns (asw_mi355x.h), last in the tuple:
+        (disp, conf) or (disp, vol, conf)."""
         disparityType = _disparity_type(disparityType, subpixel, cross_scale, scanline)
-        li, la = _image(srcLeft)
-        ri, ra = _image(srcRight)
-        disp = np.zeros((la.shape[0], la.shape[1]), np.float32)
-        di, _ = _image(disp, 5)
-        vol = None
-        pv = None
-        if return_cost_volume:
-            vol = np.zeros((self._candidates(int(algorithmType), numDisparity), la.shape[0], la.shape[1]), np.float32)
-            pv = vol.ctypes.data_as(C.c_void_p)
-        rc = self._lib.asw_stereo_match(self._h, C.byref(li), C.byref(ri), C.byref(di), disparityType,
-                                        int(algorithmType), winSize, minDisparity, numDisparity, pv, 0 if vol is None else vol.size)
-        if not self._finish(rc, "asw_stereo_match"):
-            return (None, None) if return_cost_volume else None
-        return (disp, vol) if return_cost_volume else disp
 
-    def _aggregate(self, name, algorithm, numDisparity, leftImg, rightImg, args, return_cost_volume, fn=None):
+        def call(h, l, r, d, *args):
+            return self._lib.asw_stereo_match(h, l, r, d, disparityType, int(algorithmType), winSize, minDisparity, numDisparity, *args)
+        return self._aggregate("asw_stereo_match", int(algorithmType), numDisparity, srcLeft, srcRight, (), return_cost_volume, fn=call,
+                               return_confidence=return_confidence)
+
+    def _aggregate(self, name, algorithm, numDisparity, leftImg, rightImg, args, return_cost_volume, fn=None, return_confidence=False):
         """One per-method entry point `name` (or the call `fn` standing for it); the library says how many planes the volume of
-        `algorithm` has (asw_volume_planes)."""
+        `algorithm` has (asw_volume_planes).  return_confidence: the call gets a 2-channel map, disparity and confidence
+        interleaved, and the two come back as separate arrays, the confidence last."""
         fn = fn or getattr(self._lib, name)
         li, la = _image(leftImg)
         ri, ra = _image(rightImg)
-        disp = np.zeros((la.shape[0], la.shape[1]), np.float32)
+        disp = np.zeros((la.shape[0], la.shape[1]) + ((2,) if return_confidence else ()), np.float32)
         di, _ = _image(disp, 5)
         vol, pv = None, None
         if return_cost_volume:
             vol = np.zeros((self._candidates(algorithm, numDisparity), la.shape[0], la.shape[1]), np.float32)
             pv = vol.ctypes.data_as(C.c_void_p)
         rc = fn(self._h, C.byref(li), C.byref(ri), C.byref(di), *args, pv, 0 if vol is None else vol.size)
-        if not self._finish(rc, name):
-            return (None, None) if return_cost_volume else None
-        return (disp, vol) if return_cost_volume else disp
+        ok = self._finish(rc, name)
+        out = ((disp[..., 0].copy(), disp[..., 1].copy()) if return_confidence else (disp,)) if ok else (None,) * (1 + bool(return_confidence))
+        out = out[:1] + ((vol if ok else None,) if return_cost_volume else ()) + out[1:]
+        return out if len(out) > 1 else out[0]
 
     # ---- per-method entry points (M.h:133-182) ----
     def computeAdaptiveWeight(self, leftImg, rightImg, gamma_c=30, gamma_g=2, dispType=DISPARITY_LEFT, winSize=7,
-                              minDisparity=186, numDisparity=144, return_cost_volume=False):
+                              minDisparity=186, numDisparity=144, return_cost_volume=False, return_confidence=False):
         return self._aggregate("asw_aggregate_bilateral", _A.ADAPTIVE_WEIGHT, numDisparity, leftImg, rightImg,
                                (float(gamma_c), float(gamma_g), int(dispType), winSize, minDisparity, numDisparity),
-                               return_cost_volume)
+                               return_cost_volume, return_confidence=return_confidence)
 
     def computeAdaptiveWeight_direct8(self, leftImg, rightImg, dispType=DISPARITY_LEFT, winSize=7, minDisparity=186,
-                                      numDisparity=144, return_cost_volume=False):
+                                      numDisparity=144, return_cost_volume=False, return_confidence=False):
         """M.h:135-136, M.cpp:1167-1319 (DISPARITY_LEFT only: the reference's RIGHT branch is undefined behaviour)."""
         return self._aggregate("asw_aggregate_direct8", _A.ADAPTIVE_WEIGHT_8DIRECT, numDisparity, leftImg, rightImg,
-                               (int(dispType), winSize, minDisparity, numDisparity), return_cost_volume)
+                               (int(dispType), winSize, minDisparity, numDisparity), return_cost_volume, return_confidence=return_confidence)
 
     def computeAdaptiveWeight_geodesic(self, leftImg, rightImg, dispType=DISPARITY_LEFT, winSize=7, minDisparity=186,
-                                       numDisparity=144, return_cost_volume=False):
+                                       numDisparity=144, return_cost_volume=False, return_confidence=False):
         return self._aggregate("asw_aggregate_geodesic", _A.ADAPTIVE_WEIGHT_GEODESIC, numDisparity, leftImg, rightImg,
-                               (int(dispType), winSize, minDisparity, numDisparity), return_cost_volume)
+                               (int(dispType), winSize, minDisparity, numDisparity), return_cost_volume, return_confidence=return_confidence)
 
     def computeAdaptiveWeight_GuidedF(self, leftImg, rightImg, dispType=DISPARITY_LEFT, eps=1e-8, winSize=35,
-                                      minDisparity=186, numDisparity=144, return_cost_volume=False):
+                                      minDisparity=186, numDisparity=144, return_cost_volume=False, return_confidence=False):
         return self._aggregate("asw_aggregate_guided", _A.ADAPTIVE_WEIGHT_GUIDED_FILTER, numDisparity, leftImg, rightImg,
-                               (int(dispType), float(eps), winSize, minDisparity, numDisparity), return_cost_volume)
+                               (int(dispType), float(eps), winSize, minDisparity, numDisparity), return_cost_volume, return_confidence=return_confidence)
 
     def computeAdaptiveWeight_GuidedF_2(self, leftImg, rightImg, dispType=DISPARITY_LEFT, eps=1e-8, winSize=35,
-                                        minDisparity=186, numDisparity=144, return_cost_volume=False):
+                                        minDisparity=186, numDisparity=144, return_cost_volume=False, return_confidence=False):
         return self._aggregate("asw_aggregate_guided2", _A.ADAPTIVE_WEIGHT_GUIDED_FILTER_2, numDisparity, leftImg, rightImg,
-                               (int(dispType), float(eps), winSize, minDisparity, numDisparity), return_cost_volume)
+                               (int(dispType), float(eps), winSize, minDisparity, numDisparity), return_cost_volume, return_confidence=return_confidence)
 
     def computeAdaptiveWeight_GuidedF_3(self, leftImg, rightImg, dispType=DISPARITY_LEFT, eps=1e-6, winSize=35,
-                                        minDisparity=186, numDisparity=144, return_cost_volume=False):
+                                        minDisparity=186, numDisparity=144, return_cost_volume=False, return_confidence=False):
         """M.h:174-176, M.cpp:3063-3137: NCC costs + guided filter."""
         return self._aggregate("asw_aggregate_guided3", _A.ADAPTIVE_WEIGHT_GUIDED_FILTER_3, numDisparity, leftImg, rightImg,
-                               (int(dispType), float(eps), winSize, minDisparity, numDisparity), return_cost_volume)
+                               (int(dispType), float(eps), winSize, minDisparity, numDisparity), return_cost_volume, return_confidence=return_confidence)
 
     def computeNCC(self, leftImg, rightImg, dispType=DISPARITY_LEFT, winSize=7, minDisparity=0, numDisparity=30):
         """computeNCC -> disparity (M.h:122-123, M.cpp:812-913)."""
@@ -347,36 +343,36 @@ class Context:
                           (int(dispType), winSize, minDisparity, numDisparity, int(bool(normalized))))
 
     def computeAdaptiveWeight_BLO1(self, leftImg, rightImg, dispType=DISPARITY_LEFT, sampleRateR=10, winSize=35,
-                                   minDisparity=186, numDisparity=144, return_cost_volume=False):
+                                   minDisparity=186, numDisparity=144, return_cost_volume=False, return_confidence=False):
         return self._aggregate("asw_aggregate_blo1", _A.ADAPTIVE_WEIGHT_BLO1, numDisparity, leftImg, rightImg,
-                               (int(dispType), float(sampleRateR), winSize, minDisparity, numDisparity), return_cost_volume)
+                               (int(dispType), float(sampleRateR), winSize, minDisparity, numDisparity), return_cost_volume, return_confidence=return_confidence)
 
     def computeAdaptiveWeight_bilateralGrid(self, leftImg, rightImg, dispType=DISPARITY_LEFT, sampleRateS=10, sampleRateR=10,
-                                            minDisparity=186, numDisparity=144, return_cost_volume=False):
+                                            minDisparity=186, numDisparity=144, return_cost_volume=False, return_confidence=False):
         """M.h:155-157, M.cpp:2253-2430 (DISPARITY_LEFT only: the reference's RIGHT branch reads past the image row)."""
         return self._aggregate("asw_aggregate_bilgrid", _A.ADAPTIVE_WEIGHT_BILATERAL_GRID, numDisparity, leftImg, rightImg,
                                (int(dispType), float(sampleRateS), float(sampleRateR), minDisparity, numDisparity),
-                               return_cost_volume)
+                               return_cost_volume, return_confidence=return_confidence)
 
     def computeAdaptiveWeight_WeightedMedian(self, leftImg, rightImg, dispType=DISPARITY_LEFT, winSize=35,
                                              sampleRateS=10, sampleRateR=10, minDisparity=186, numDisparity=144,
-                                             return_cost_volume=False):
+                                             return_cost_volume=False, return_confidence=False):
         return self._aggregate("asw_aggregate_wmedian", _A.ADAPTIVE_WEIGHT_MEDIAN, numDisparity, leftImg, rightImg,
                                (int(dispType), winSize, float(sampleRateS), float(sampleRateR), minDisparity, numDisparity),
-                               return_cost_volume)
+                               return_cost_volume, return_confidence=return_confidence)
 
     def computeAdaptiveWeight_cross(self, leftImg, rightImg, dispType=DISPARITY_LEFT, tau=20, trunc=20, winSize=15, minDisparity=0,
-                                    numDisparity=64, return_cost_volume=False):
+                                    numDisparity=64, return_cost_volume=False, return_confidence=False):
         """Cross-based support-region aggregation (asw_aggregate_cross; not in the reference): the truncated
         AD cost summed over every pixel's cross-shaped region, exact integers and one f32 division; 1- or 3-channel pairs."""
         def call(h, l, r, d, *args):
             return self._lib.asw_stereo_match(h, l, r, d, int(dispType), cross_algorithm(tau, trunc), winSize, minDisparity,
                                               numDisparity, *args)
         return self._aggregate("asw_aggregate_cross", _A.ADAPTIVE_WEIGHT_CROSS, numDisparity, leftImg, rightImg, (), return_cost_volume,
-                               fn=call)
+                               fn=call, return_confidence=return_confidence)
 
     def computeAdaptiveWeight_adcensus(self, leftImg, rightImg, dispType=DISPARITY_LEFT, tau=20, lambda_ad=10, lambda_census=30,
-                                       winSize=15, minDisparity=0, numDisparity=64, return_cost_volume=False):
+                                       winSize=15, minDisparity=0, numDisparity=64, return_cost_volume=False, return_confidence=False):
         """AD-Census matching (asw_aggregate_adcensus; not in the reference): the census + AD cost of
         computeADCensus summed over every pixel's cross-shaped region, exact integers and one f32 division; 1- or 3-channel pairs."""
         alg = adcensus_algorithm(tau, lambda_ad, lambda_census)
@@ -384,10 +380,10 @@ class Context:
         def call(h, l, r, d, *args):
             return self._lib.asw_stereo_match(h, l, r, d, int(dispType), alg, winSize, minDisparity, numDisparity, *args)
         return self._aggregate("asw_aggregate_adcensus", _A.ADAPTIVE_WEIGHT_CROSS, numDisparity, leftImg, rightImg, (),
-                               return_cost_volume, fn=call)
+                               return_cost_volume, fn=call, return_confidence=return_confidence)
 
     def computeAdaptiveWeight_twopass(self, leftImg, rightImg, gamma_c=30, gamma_g=20, dispType=DISPARITY_LEFT, winSize=15,
-                                      minDisparity=0, numDisparity=64, return_cost_volume=False):
+                                      minDisparity=0, numDisparity=64, return_cost_volume=False, return_confidence=False):
         """Two-pass (separable) adaptive-support-weight aggregation (asw_aggregate_twopass; not in the
         reference): a vertical, then a horizontal 1-D weighted pass, 2 * winSize taps in place of winSize^2 - 1; integer gammas
         1..255; candidates minDisparity .. minDisparity + numDisparity inclusive; 1- or 3-channel pairs."""
@@ -396,10 +392,10 @@ class Context:
         def call(h, l, r, d, *args):
             return self._lib.asw_stereo_match(h, l, r, d, int(dispType), alg, winSize, minDisparity, numDisparity, *args)
         return self._aggregate("asw_aggregate_twopass", _A.ADAPTIVE_WEIGHT, numDisparity, leftImg, rightImg, (), return_cost_volume,
-                               fn=call)
+                               fn=call, return_confidence=return_confidence)
 
     def computeAdaptiveWeight_permeability(self, leftImg, rightImg, dispType=DISPARITY_LEFT, sigma=8, trunc=20, minDisparity=0,
-                                           numDisparity=64, return_cost_volume=False):
+                                           numDisparity=64, return_cost_volume=False, return_confidence=False):
         """Recursive (permeability) aggregation over the whole image (asw_aggregate_permeability; not in the
         reference): the truncated AD cost carried along rows and columns, damped by exp(-colour step / sigma), f64; no window;
         integers sigma and trunc 1..255; 1- or 3-channel pairs."""
@@ -408,7 +404,7 @@ class Context:
         def call(h, l, r, d, *args):
             return self._lib.asw_stereo_match(h, l, r, d, int(dispType), alg, 0, minDisparity, numDisparity, *args)
         return self._aggregate("asw_aggregate_permeability", _A.ADAPTIVE_WEIGHT_CROSS, numDisparity, leftImg, rightImg, (),
-                               return_cost_volume, fn=call)
+                               return_cost_volume, fn=call, return_confidence=return_confidence)
 
     # ---- semi-global block matching ----
     def getDisparity_SGBM(self, srcLeft, srcRight, winSize=15, minDisparity=0, numDisparity=64):
@@ -687,11 +683,13 @@ class Context:
         self._strict(rc, "asw_match_refined_resident")
         return nr.value, nu.value
 
-    def download_disparity(self, slot, shape):
-        disp = np.zeros(shape, np.float32)
+    def download_disparity(self, slot, shape, confidence=False):
+        """confidence: (disp, conf), the confidence computed from the volume the slot kept (match_resident with keep_volume);
+        ERR_NO_FRAME without one."""
+        disp = np.zeros(tuple(shape) + ((2,) if confidence else ()), np.float32)
         di, _ = _image(disp, 5)
         self._strict(self._lib.asw_download_disparity(self._h, slot, C.byref(di)), "asw_download_disparity")
-        return disp
+        return (disp[..., 0].copy(), disp[..., 1].copy()) if confidence else disp
 
     def download_volume(self, slot, shape):
         vol = np.zeros(shape, np.float32)

@@ -18,7 +18,7 @@ int match_host(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_
 {
     if (!ctx) return ASW_ERR_BAD_ARGUMENT;
     ASW_TRY(check_pair(left, right));
-    ASW_TRY(check_disp_out(disp, left->rows, left->cols));
+    ASW_TRY(check_disp_out(disp, left->rows, left->cols, 2));  // 2 channels: disparity and confidence, interleaved
     if (cost_volume_out) {  // the caller states what its buffer holds; a short one is refused before anything is written
         const MethodInfo* m = method_info(algorithm);
         if (m && m->run && m->no_volume) return ASW_ERR_BAD_ARGUMENT;  // the selector's SGBM has no volume (asw_sgbm has S)
@@ -28,7 +28,7 @@ int match_host(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_
     ASW_HIP_TRY(hipSetDevice(ctx->device));
     Frame* f = &ctx->host_frame;
     ASW_TRY(upload_pair_into(ctx, f, left, right));
-    ASW_TRY(run_method(ctx, f, algorithm, mp, cost_volume_out != nullptr));
+    ASW_TRY(run_method(ctx, f, algorithm, mp, cost_volume_out != nullptr, true, disp->channels == 2));
     ASW_TRY(download_disparity_from(ctx, f, disp));
     if (cost_volume_out) {
         if (f->vol_floats > cost_volume_floats) return ASW_ERR_BAD_ARGUMENT;

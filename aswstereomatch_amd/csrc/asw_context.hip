@@ -177,11 +177,11 @@ int upload_image(asw_ctx* ctx, const asw_image* im, DevBuf& dst)
     return ASW_OK;
 }
 
-int check_disp_out(const asw_image* d, int rows, int cols)
+int check_disp_out(const asw_image* d, int rows, int cols, int max_channels)
 {
     if (!d || !d->data) return ASW_ERR_BAD_ARGUMENT;
-    if (d->depth != ASW_32F || d->channels != 1) return ASW_ERR_BAD_ARGUMENT;
-    if (d->rows != rows || d->cols != cols || d->step < (size_t)cols * 4) return ASW_ERR_BAD_ARGUMENT;
+    if (d->depth != ASW_32F || d->channels < 1 || d->channels > max_channels) return ASW_ERR_BAD_ARGUMENT;
+    if (d->rows != rows || d->cols != cols || d->step < (size_t)cols * 4 * d->channels) return ASW_ERR_BAD_ARGUMENT;
     return ASW_OK;
 }
 
@@ -339,9 +339,23 @@ extern "C" int asw_download_disparity_u8(asw_ctx* ctx, int slot, asw_image* disp
 int download_disparity_from(asw_ctx* ctx, Frame* f, asw_image* disp)
 {
     if (!f || !f->valid || !f->has_disp || !f->disp.p || f->disp_rows != f->rows || f->disp_cols != f->cols) return ASW_ERR_NO_FRAME;
-    ASW_TRY(check_disp_out(disp, f->rows, f->cols));
+    ASW_TRY(check_disp_out(disp, f->rows, f->cols, 2));
+    const void* src = f->disp.p;
+    if (disp->channels == 2) {  // {disparity, confidence}: of the match itself, or now from the volume the slot kept
+        if (!f->has_conf && (!f->vol.p || f->vol_floats == 0)) return ASW_ERR_NO_FRAME;
+        ASW_HIP_TRY(hipSetDevice(ctx->device));
+        if (!f->has_conf) {
+            const size_t plane = (size_t)f->rows * f->cols;
+            ASW_TRY(f->dconf.ensure(plane * sizeof(float2)));
+            ASW_TRY(launch_confidence(ctx->stream, f->vol.as<float>(), (int)(f->vol_floats / plane), f->rows, f->cols, f->disp.as<float>(),
+                                      f->dconf.as<float2>()));
+            f->has_conf = true;
+        }
+        src = f->dconf.p;
+    }
+    const size_t rowbytes = (size_t)f->cols * 4 * disp->channels;
     ASW_HIP_TRY(hipSetDevice(ctx->device));
-    ASW_HIP_TRY(copy_rows(ctx, disp->data, disp->step, f->disp.p, (size_t)f->cols * 4, (size_t)f->cols * 4, f->rows, hipMemcpyDeviceToHost));
+    ASW_HIP_TRY(copy_rows(ctx, disp->data, disp->step, src, rowbytes, rowbytes, f->rows, hipMemcpyDeviceToHost));
     ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ASW_OK;
 }

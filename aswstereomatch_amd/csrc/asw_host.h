@@ -45,9 +45,12 @@ int upload_image(asw_ctx* ctx, const asw_image* im, DevBuf& dst);
 // pitched host rows <-> dense device rows on the context's stream (asw_context.hip)
 hipError_t copy_rows(asw_ctx* ctx, void* dst, size_t dpitch, const void* src, size_t spitch, size_t rowbytes, size_t rows,
                      hipMemcpyKind kind);
-int check_disp_out(const asw_image* d, int rows, int cols);
+// d: ASW_32F, rows x cols, 1 .. max_channels channels (2: disparity and confidence interleaved), step >= cols * 4 * channels
+int check_disp_out(const asw_image* d, int rows, int cols, int max_channels = 1);
 Frame* frame_slot(asw_ctx* ctx, int slot, bool create);
 int upload_pair_into(asw_ctx* ctx, Frame* f, const asw_image* left, const asw_image* right);
+// disp with 1 channel: the frame's map; with 2: the map and its confidence, computed here from the frame's kept volume unless the
+// match already did (Frame::has_conf); ASW_ERR_NO_FRAME without either
 int download_disparity_from(asw_ctx* ctx, Frame* f, asw_image* disp);
 int download_volume_from(asw_ctx* ctx, Frame* f, float* out, size_t n_floats);
 // 3 channels: cvtColor(BGR2GRAY) of both images into the scratch planes "grayL" / "grayR"; 1 channel: the images as they are
@@ -90,6 +93,8 @@ int run_refine(asw_ctx* ctx, const uint8_t* guide, int channels, const float* dl
                float* out, int* n_rejected, int* n_unfillable);
 int match_refined(asw_ctx* ctx, Frame* f, int algorithm, int win_size, int min_disparity, int num_disparity, float max_diff,
                   int refine_win, double gamma_c, double gamma_s, int* n_rejected, int* n_unfillable);
-int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp, bool keep_volume, bool sync = true);
+// confidence: also fill f->dconf from the volume the call returns (implies the volume is computed, as a sub-pixel flag does)
+int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp, bool keep_volume, bool sync = true,
+               bool confidence = false);
 int match_host(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp, int algorithm,
                       const MatchParams& mp, float* cost_volume_out, size_t cost_volume_floats);

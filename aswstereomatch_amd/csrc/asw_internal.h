@@ -41,13 +41,15 @@ struct Frame {
     DevBuf disp;  // f32 rows x cols
     DevBuf vol;   // f32 aggregated cost volume of the last match (if kept)
     size_t vol_floats = 0;
+    DevBuf dconf; // float2 {disparity, confidence} rows x cols, packed: only a 2-channel disparity image asks for it (k_confidence.hip)
+    bool has_conf = false;  // dconf belongs to the current disp / vol
     bool valid = false;
     // the disparity (and volume) in `disp` / `vol` belong to the CURRENT pair: set by a successful match, cleared by every
     // upload / pre-processing into the slot and by a failed match, so a download can never return another frame's result
     // or read a smaller, older allocation
     bool has_disp = false;
     int disp_rows = 0, disp_cols = 0;
-    void invalidate_results() { has_disp = false; disp_rows = disp_cols = 0; vol_floats = 0; }
+    void invalidate_results() { has_disp = has_conf = false; disp_rows = disp_cols = 0; vol_floats = 0; }
 };
 
 struct BilateralTables {
@@ -178,6 +180,9 @@ int launch_wta(hipStream_t s, const float* vol, int n, int H, int W, int minD, f
 // mode: ASW_DISPARITY_SUBPIXEL_PARABOLA | ASW_DISPARITY_SUBPIXEL_EQUIANGULAR; vol [n][H][W] (plane k <-> disparity minD + k);
 // disp [H][W]: the integer winner-take-all map, refined in place
 int launch_subpixel(hipStream_t s, int mode, const float* vol, int n, int H, int W, int minD, float* disp);
+// ---- confidence (k_confidence.hip), DESIGN.md section 4.24 ----
+// vol [n][H][W], disp [H][W]: the final map, copied; out [H][W]: {disparity, confidence} interleaved, 8 bytes per pixel
+int launch_confidence(hipStream_t s, const float* vol, int n, int H, int W, const float* disp, float2* out);
 
 // ---- cross-scale aggregation (k_cross_scale.hip), DESIGN.md section 4.18 ----
 // one pyramid step: dst [ceil(H/2)][ceil(W/2)][C] from src [H][W][C], the rounded 2x2 mean with the last row / column repeated

@@ -1065,7 +1065,7 @@ static int run_cross_scale(asw_ctx* ctx, Frame* f, const MethodInfo* m, const Ma
     return launch_cross_scale_combine(ctx->stream, a);
 }
 
-int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp_in, bool keep_volume, bool sync)
+int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp_in, bool keep_volume, bool sync, bool confidence)
 {
     f->invalidate_results();  // whatever the slot's disparity / volume were, they are not this call's
     MatchParams mp = mp_in;
@@ -1073,9 +1073,12 @@ int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp_in, 
     ASW_TRY(decode_algorithm(algorithm, &algorithm, &mp, method_info));  // an asw_alg_*() value -> the plain one + its parameters
     const MethodInfo* m = method_info(algorithm);
     ASW_TRY(decode_disparity_type(m, m && m->run, scanline_max_planes(), mp));  // the flags: every refusal before any work
-    // the sub-pixel kernel reads the aggregated volume: the methods that can skip it (bilateral / direct8, geodesic, BLO1, the
-    // bilateral grid) are asked for it; what the CALLER keeps is decided below
-    const bool want_volume = keep_volume || mp.subpixel != 0 || mp.scan_p1 != 0;
+    // the confidence is read off a selector volume with the selector's candidate range: no volume (SGBM, BM, a value outside the
+    // table) or a range of its own (NCC) is refused like a sub-pixel flag on NCC
+    if (confidence && (!m || !m->run || m->no_volume || m->no_subpixel)) return ASW_ERR_UNSUPPORTED_METHOD;
+    // the sub-pixel and confidence kernels read the aggregated volume: the methods that can skip it (bilateral / direct8, geodesic,
+    // BLO1, the bilateral grid) are asked for it; what the CALLER keeps is decided below
+    const bool want_volume = keep_volume || mp.subpixel != 0 || mp.scan_p1 != 0 || confidence;
     ASW_HIP_TRY(hipSetDevice(ctx->device));
     ASW_HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
     int rc;
@@ -1088,6 +1091,12 @@ int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp_in, 
     if (rc == ASW_OK && mp.subpixel)  // after the aggregation events: counts in total_ms and cost_ms, not in aggregate_ms
         rc = launch_subpixel(ctx->stream, mp.subpixel, f->vol.as<float>(), m->planes(mp.numD), f->rows, f->cols,
                              mp.minD, f->disp.as<float>());
+    if (rc == ASW_OK && confidence) {  // of the volume the call returns, beside the final map; timed like the sub-pixel step
+        rc = f->dconf.ensure((size_t)f->rows * f->cols * sizeof(float2));
+        if (rc == ASW_OK)
+            rc = launch_confidence(ctx->stream, f->vol.as<float>(), m->planes(mp.numD), f->rows, f->cols, f->disp.as<float>(),
+                                   f->dconf.as<float2>());
+    }
     if (rc != ASW_OK) {
         f->invalidate_results();
         return rc;
@@ -1098,7 +1107,7 @@ int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp_in, 
         ASW_TRY(timed_finish(ctx));
     else  // pipelined callers (batch scheduler) order and wait on the stream themselves
         ASW_HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
-    f->has_disp = true; f->disp_rows = f->rows; f->disp_cols = f->cols; f->vol_floats = kept_floats;
+    f->has_disp = true; f->disp_rows = f->rows; f->disp_cols = f->cols; f->vol_floats = kept_floats; f->has_conf = confidence;
     return ASW_OK;
 }
 

@@ -321,6 +321,35 @@ inline void stereoMatchingScanline(AswMat srcLeft, AswMat srcRight, AswMat& disp
     disparityMap = d;
 }
 
+// Not in the reference: stereoMatching with a per-pixel confidence beside the map (asw_mi355x.h "Confidence") --
+// the winner's margin over the best candidate that is not its neighbour, in units of the cost range of the pixel, in [0, 1], read off
+// the volume the call works on.  disparityType: DISPARITY_LEFT / DISPARITY_RIGHT, optionally with the sub-pixel, cross-scale or
+// scanline flags of asw_mi355x.h OR-ed in.  Both maps are CV_32F, one channel.  Silent errors leave two empty Mats like
+// stereoMatching; SGBM (it has no selector volume), BM and NCC throw.
+inline void stereoMatchingConfidence(AswMat srcLeft, AswMat srcRight, AswMat& disparityMap, AswMat& confidenceMap, int disparityType,
+                                     StereoMatchingAlgorithms algorithmType, int winSize = 15, int minDisparity = 0, int numDisparity = 64)
+{
+    using namespace asw::detail;
+    disparityMap = AswMat();
+    confidenceMap = AswMat();
+    if (srcLeft.empty() || srcRight.empty()) return;
+    AswMat both = make(srcLeft.rows, srcLeft.cols, ASW_32F, 2);  // {disparity, confidence} interleaved
+    asw_image li = view(srcLeft), ri = view(srcRight), bi = view(both);
+    const int rc = asw_stereo_match(context(), &li, &ri, &bi, disparityType, (int)algorithmType, winSize, minDisparity, numDisparity, nullptr, 0);
+    raise_unless_ok(rc, "stereoMatchingConfidence");
+    if (rc != ASW_OK) return;
+    AswMat d = make(both.rows, both.cols, ASW_32F, 1), c = make(both.rows, both.cols, ASW_32F, 1);
+    asw_image di = view(d), ci = view(c);
+    for (int y = 0; y < both.rows; y++) {
+        const float* src = (const float*)((const uint8_t*)bi.data + (size_t)y * bi.step);
+        float* dd = (float*)((uint8_t*)di.data + (size_t)y * di.step);
+        float* cc = (float*)((uint8_t*)ci.data + (size_t)y * ci.step);
+        for (int x = 0; x < both.cols; x++) { dd[x] = src[2 * x]; cc[x] = src[2 * x + 1]; }
+    }
+    disparityMap = d;
+    confidenceMap = c;
+}
+
 // M.h:101-102
 inline void computeAD(AswMat leftImg, AswMat rightImg, std::vector<AswMat>& cost_ds, DisparityType dispType = DISPARITY_LEFT,
                       int minDisparity = 0, int numDisparity = 30)

@@ -61,6 +61,28 @@ enum { ASW_DISPARITY_LEFT = 0, ASW_DISPARITY_RIGHT = 1 };
  * and the refined calls do not take the flags.  asw_get_timing: the extra kernel counts in total_ms and cost_ms. */
 enum { ASW_DISPARITY_SUBPIXEL_PARABOLA = 0x100, ASW_DISPARITY_SUBPIXEL_EQUIANGULAR = 0x200 };
 
+/* Confidence (not in the reference): a `disp` image with 2 channels (ASW_32F, step >= cols * 8; the cv::Mat
+ * idiom CV_32FC2) passed to asw_stereo_match, to any asw_aggregate_* or to asw_download_disparity receives the disparity in channel
+ * 0 and a confidence in channel 1, interleaved.  Channel 0 and the returned volume are those of the same call with a 1-channel
+ * image.  The confidence is a function of the volume alone: for every pixel let V[k], k = 0 .. n - 1 (n = asw_volume_planes()), be
+ * the volume the same call returns in cost_volume_out -- the combined volume under the cross-scale flag, the optimised volume under
+ * the scanline flag, the unflagged volume under a sub-pixel flag, the method's volume otherwise.  Then
+ *   F = { k : V[k] finite };  F empty: conf = 0;
+ *   c1 = min over F, k1 = the smallest k with V[k] == c1 (strict '<' in ascending k), cmax = max over F;
+ *   G = { k in F : |k - k1| >= 2 } -- the winner's two neighbours are left out: a true minimum between two samples makes them
+ *     nearly equal;  G empty, cmax == c1 or c2 == c1: conf = 0;
+ *   c2 = min over G;  conf = (float)(((double)c2 - (double)c1) / ((double)cmax - (double)c1)), one IEEE f64 operation each.
+ * The winner's margin over the best candidate that is not its neighbour, in units of the column's range: it lies in [0, 1], is
+ * never -0 and never NaN, and does not change when the volume is scaled by a power of two.  Thresholding is the caller's.
+ * Statuses, after those of the two packed words and before any work: ASW_ALG_SGBM, ASW_ALG_BM, a value outside the selector,
+ * ASW_ALG_NCC and asw_ncc_disparity give ASW_ERR_UNSUPPORTED_METHOD; everything a 1-channel call refuses is refused with the same
+ * status.  asw_match_resident takes no such request: asw_download_disparity with a 2-channel image computes the confidence from
+ * the volume the slot kept (keep_volume != 0) and returns ASW_ERR_NO_FRAME without one (keep_volume == 0, or after
+ * asw_match_refined_resident), as asw_download_volume does.  asw_stereo_match_batch, the refined calls, asw_sgbm and the block
+ * matchers refuse a 2-channel image as before (ASW_ERR_BAD_ARGUMENT / their own status).  asw_get_timing: the extra kernel of a
+ * 2-channel asw_stereo_match / asw_aggregate_* call counts in total_ms and cost_ms.  A 1-channel call allocates and launches
+ * nothing new. */
+
 /* Cross-scale cost aggregation (Zhang et al., CVPR 2014; not in the reference): asw_disparity_cross_scale(S, q)
  * OR-ed into the disparity_type of asw_stereo_match, asw_match_resident, every asw_aggregate_* and asw_stereo_match_batch.  The method
  * (same window, same parameters) aggregates on S levels of a 2x2-mean pyramid of the pair; the regularised finest-scale volume is
@@ -283,7 +305,7 @@ int asw_set_gray_bits(asw_ctx* ctx, int bits);
 
 /* ---- whole-method entry point: stereoMatching(), M.h:91-92, M.cpp:46-88 ----
  * disp: ASW_32F, 1 channel, rows x cols, caller-allocated; receives ABSOLUTE disparity
- * (min_d + index), like the reference's CV_32FC1 result.  Per-method literals are the
+ * (min_d + index), like the reference's CV_32FC1 result; with 2 channels also the confidence ("Confidence" above).  Per-method literals are the
  * selector's (gamma_c=30, gamma_g=20; eps=1e-6; rateS=rateR=10).
  * cost_volume_out (optional, may be NULL): aggregated cost volume, [n][rows][cols] f32 with
  * n = asw_volume_planes(algorithm, num_d): num_d, or num_d + 1 for ADAPTIVE_WEIGHT, 8DIRECT, GEODESIC and BILATERAL_GRID, whose

@@ -62,6 +62,13 @@ included), with and without the kept volume; its cases come from scanline_ref.ra
 scanline_ref.build_case rebuilds.
 
     python tools/fuzz_parity.py --seconds 120 --seed 1 --only scanline
+
+The leg confidence is the confidence channel of a 2-channel disparity image (asw_mi355x.h "Confidence") over the
+same methods, with and without a step flag and a sub-pixel flag: map and volume against a second context's 1-channel call, the confidence
+against the restatement of tests/confidence_ref.py applied to the returned volume, with and without the kept volume; its cases come
+from confidence_ref.random_case and a mismatch prints the tag confidence_ref.build_case rebuilds.
+
+    python tools/fuzz_parity.py --seconds 120 --seed 1 --only confidence
 """
 import argparse
 import os
@@ -77,6 +84,7 @@ from oracle import asw_oracle as O  # noqa: E402
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import asw_cases  # noqa: E402
+import confidence_ref  # noqa: E402
 import cross_scale_ref  # noqa: E402
 import matcher_cases as mc  # noqa: E402
 import permeability_ref  # noqa: E402
@@ -111,7 +119,8 @@ REF_LEGS["sgbm_census"] = SgbmCensusLeg
 REF_LEGS.update((m.name, m) for m in SELECTOR_METHODS[2:])
 REF_LEGS["permeability"] = permeability_ref  # behind the others: the legs before it keep the cases a seed drew for them
 REF_LEGS["cross_scale"] = cross_scale_ref    # behind those, for the same reason
-REF_LEGS["scanline"] = scanline_ref          # last, for the same reason
+REF_LEGS["scanline"] = scanline_ref          # behind those, for the same reason
+REF_LEGS["confidence"] = confidence_ref      # last, for the same reason
 LEGS = tuple(mc.FAMILIES) + tuple(REF_LEGS)
 ORACLE_METHODS = ["classic", "direct8", "geodesic", "guided", "guided2", "guided3", "wmedian", "blo1", "ncc", "ncc_cost",
                   "ad_tad", "similarity", "sad", "geodist", "gfilter", "prep", "bilgrid", "lrcheck", "resident", "batch"]
