@@ -29,6 +29,7 @@ __all__ = [
     "computeAdaptiveWeight_GuidedF_3", "getDisparity_SGBM", "sgbm", "sgbm_paths", "sgbm_census", "filterSpeckles", "getDisparity_BM", "stereoBM",
     "PREFILTER_NORMALIZED_RESPONSE", "PREFILTER_XSOBEL", "refineDisparity", "stereoMatchingRefined",
     "REFINE_GAMMA_C", "REFINE_GAMMA_S", "SUBPIXEL_PARABOLA", "SUBPIXEL_EQUIANGULAR",
+    "REFINE_SMOOTH", "SMOOTH_SIGMA_C", "SMOOTH_LAMBDA", "SMOOTH_ITERATIONS", "smoothDisparity", "stereoMatchingSmoothed",
     "SGBM_PATH_LR", "SGBM_PATH_RL", "SGBM_PATH_TB", "SGBM_PATH_BT", "SGBM_PATH_TLBR", "SGBM_PATH_TRBL", "SGBM_PATH_BRTL",
     "SGBM_PATH_BLTR", "SGBM_PATHS_3WAY", "SGBM_PATHS_HH4", "SGBM_PATHS_SGBM", "SGBM_PATHS_HH",
     "cross_algorithm", "computeAdaptiveWeight_cross",
@@ -174,6 +175,17 @@ def _disparity_type(disparityType, subpixel, cross_scale, scanline):
 
 PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL = 0, 1  # StereoBM::PREFILTER_*; asw_stereo_bm serves XSOBEL
 REFINE_GAMMA_C, REFINE_GAMMA_S = 60.0, 9.0  # default colour / distance gammas of the refinement's weighted median (asw_mi355x.h)
+# Smoothing (asw_mi355x.h: ASW_REFINE_SMOOTH): the flag that turns the refinement family's window argument into
+# a smoothing request, and the wrappers' defaults (the paper's demonstration values: sigma about 0.03 * 255, lambda = 30^2, T = 3)
+REFINE_SMOOTH = 0x40000000
+SMOOTH_SIGMA_C, SMOOTH_LAMBDA, SMOOTH_ITERATIONS = 8.0, 900.0, 3
+
+
+def _smooth_word(iterations):
+    """REFINE_SMOOTH | T as the header's inline functions form it: iterations outside 1..8 travel as the word the library refuses"""
+    return REFINE_SMOOTH | (int(iterations) if 1 <= int(iterations) <= 8 else 0)
+
+
 # statuses for which the reference returns silently / an empty Mat
 _SILENT = (ERR_SIZE_MISMATCH, ERR_EVEN_WINDOW)
 
@@ -646,6 +658,39 @@ class Context:
         self._strict(rc, "asw_stereo_match_refined")
         return disp, nr.value, nu.value
 
+    # ---- confidence-weighted edge-aware smoothing (asw_mi355x.h "Smoothing").  The three calls are the
+    # header's inline functions: the request travels in the refinement family's window argument as REFINE_SMOOTH | iterations ----
+    def smoothDisparity(self, guide, disp, conf, sigma_c=SMOOTH_SIGMA_C, lam=SMOOTH_LAMBDA, iterations=SMOOTH_ITERATIONS):
+        """asw_smooth_disparity: the fast global smoother over disp * conf and conf, guided by the 8-bit image `guide` (1 or 3
+        channels) -> the dense fractional map.  conf: any float32 trust value per pixel, e.g. the confidence a return_confidence=True
+        call gives, or a 0/1 validity mask; non-finite map values and confidences <= 0 are holes.  The defaults are the paper's
+        demonstration values (lambda = 30^2, sigma about 0.03 * 255, 3 iterations): a starting point, not a tuned choice."""
+        gi, ga = _image(guide)
+        a = np.ascontiguousarray(disp, dtype=np.float32)
+        b = np.ascontiguousarray(conf, dtype=np.float32)
+        if a.ndim != 2 or a.shape != b.shape or a.shape != ga.shape[:2]:
+            raise ValueError("smoothDisparity: a guide, a float32 map and a float32 confidence of equal (H, W) shape expected")
+        out = np.zeros(a.shape, np.float32)
+        rc = self._lib.asw_refine_disparity(self._h, C.byref(gi), a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), 0, 1, 0.0,
+                                            _smooth_word(iterations), float(sigma_c), float(lam), out.ctypes.data_as(C.c_void_p),
+                                            None, None, None)
+        self._strict(rc, "asw_smooth_disparity")
+        return out
+
+    def stereoMatchingSmoothed(self, srcLeft, srcRight, algorithmType, winSize=15, minDisparity=0, numDisparity=64,
+                               sigma_c=SMOOTH_SIGMA_C, lam=SMOOTH_LAMBDA, iterations=SMOOTH_ITERATIONS):
+        """asw_stereo_match_smoothed: ONE DISPARITY_LEFT match of the method with its confidence + smoothDisparity with srcLeft
+        as guide -> the smoothed left-view map.  Every non-zero status raises AswError, as for stereoMatchingRefined."""
+        li, la = _image(srcLeft)
+        ri, ra = _image(srcRight)
+        disp = np.zeros(la.shape[:2], np.float32)
+        di, _ = _image(disp, 5)
+        rc = self._lib.asw_stereo_match_refined(self._h, C.byref(li), C.byref(ri), C.byref(di), int(algorithmType), winSize,
+                                                minDisparity, numDisparity, 0.0, _smooth_word(iterations), float(sigma_c), float(lam),
+                                                None, None)
+        self._strict(rc, "asw_stereo_match_smoothed")
+        return disp
+
     def bgr2gray(self, img):
         ii, ia = _image(img)
         out = np.zeros(ia.shape[:2], np.uint8)
@@ -682,6 +727,14 @@ class Context:
                                                   C.byref(nu))
         self._strict(rc, "asw_match_refined_resident")
         return nr.value, nu.value
+
+    def match_smoothed_resident(self, slot, algorithmType, winSize, minDisparity, numDisparity, sigma_c=SMOOTH_SIGMA_C,
+                                lam=SMOOTH_LAMBDA, iterations=SMOOTH_ITERATIONS):
+        """asw_match_smoothed_resident: one DISPARITY_LEFT match on the slot's pair with its confidence, smoothed with the resident
+        left image as guide; the smoothed map becomes the slot's disparity (no volume is kept)."""
+        rc = self._lib.asw_match_refined_resident(self._h, slot, int(algorithmType), winSize, minDisparity, numDisparity, 0.0,
+                                                  _smooth_word(iterations), float(sigma_c), float(lam), None, None)
+        self._strict(rc, "asw_match_smoothed_resident")
 
     def download_disparity(self, slot, shape, confidence=False):
         """confidence: (disp, conf), the confidence computed from the volume the slot kept (match_resident with keep_volume);
@@ -829,3 +882,5 @@ getDisparity_BM = _bind("getDisparity_BM")
 stereoBM = _bind("stereoBM")
 refineDisparity = _bind("refineDisparity")
 stereoMatchingRefined = _bind("stereoMatchingRefined")
+smoothDisparity = _bind("smoothDisparity")
+stereoMatchingSmoothed = _bind("stereoMatchingSmoothed")

@@ -478,9 +478,14 @@ extern "C" int asw_refine_disparity(asw_ctx* ctx, const asw_image* guide, const 
     if (!ctx || !disp_left || !disp_right || !out) return ASW_ERR_BAD_ARGUMENT;
     ASW_TRY(check_u8_image(guide));
     const int H = guide->rows, W = guide->cols;
+    const bool smooth = win_size > 0 && (win_size & ASW_REFINE_SMOOTH);  // asw_smooth_disparity: no window has bit 30
     RefineParams rp;
     rp.minD = min_disparity; rp.n = num_values; rp.max_diff = max_diff; rp.win = win_size; rp.gamma_c = gamma_c; rp.gamma_s = gamma_s;
-    ASW_TRY(check_refine_params(rp, H, W, guide->channels));
+    int T = 0;
+    if (smooth)  // disp_right is the confidence, gamma_c sigma_c, gamma_s lambda; the map's domain and max_diff are not looked at
+        ASW_TRY(check_smooth_params(H, W, guide->channels, win_size, gamma_c, gamma_s, mask_out != nullptr, &T));
+    else
+        ASW_TRY(check_refine_params(rp, H, W, guide->channels));
     ASW_HIP_TRY(hipSetDevice(ctx->device));
     const size_t plane = (size_t)H * W;
     DevBuf& dg = ctx->buf("stageL");
@@ -493,6 +498,11 @@ extern "C" int asw_refine_disparity(asw_ctx* ctx, const asw_image* guide, const 
     ASW_TRY(o.ensure(plane * 4));
     ASW_HIP_TRY(hipMemcpyAsync(a.p, disp_left, plane * 4, hipMemcpyHostToDevice, ctx->stream));
     ASW_HIP_TRY(hipMemcpyAsync(b.p, disp_right, plane * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (smooth) {  // the counts are the cross-check's: not written
+        ASW_TRY(run_smooth(ctx, dg.as<uint8_t>(), guide->channels, a.as<float>(), b.as<float>(), 1, H, W, T, gamma_c, gamma_s,
+                           o.as<float>()));
+        return download_sync(ctx, out, o.p, plane * 4);
+    }
     int rejected = 0, unfillable = 0;
     ASW_TRY(run_refine(ctx, dg.as<uint8_t>(), guide->channels, a.as<float>(), b.as<float>(), H, W, rp, o.as<float>(), &rejected,
                        &unfillable));  // a map outside the domain returns here: nothing of the caller's has been written

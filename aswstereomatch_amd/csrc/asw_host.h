@@ -93,6 +93,14 @@ int run_refine(asw_ctx* ctx, const uint8_t* guide, int channels, const float* dl
                float* out, int* n_rejected, int* n_unfillable);
 int match_refined(asw_ctx* ctx, Frame* f, int algorithm, int win_size, int min_disparity, int num_disparity, float max_diff,
                   int refine_win, double gamma_c, double gamma_s, int* n_rejected, int* n_unfillable);
+// Confidence-weighted smoothing, the refinement family's win_size / refine_win with ASW_REFINE_SMOOTH set.
+// check_smooth_params: the frame-size rule of check_refine_params, the word, sigma_c and lambda, a mask asked for, the channels, in
+// that order; fills *iterations.  run_smooth: the 2 T + 2 kernels on a device map and confidence (element stride 1 or 2, see
+// SmoothLaunch) into `out`, enqueued on the context's stream; does not wait.  match_refined under the flag: ONE DISPARITY_LEFT
+// match of `algorithm` with its confidence, smoothed with the frame's left image as guide into the frame's disparity.
+int check_smooth_params(int rows, int cols, int channels, int word, double sigma_c, double lambda, bool wants_mask, int* iterations);
+int run_smooth(asw_ctx* ctx, const uint8_t* guide, int channels, const float* d, const float* c, int stride, int H, int W,
+               int iterations, double sigma_c, double lambda, float* out);
 // confidence: also fill f->dconf from the volume the call returns (implies the volume is computed, as a sub-pixel flag does)
 int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp, bool keep_volume, bool sync = true,
                bool confidence = false);

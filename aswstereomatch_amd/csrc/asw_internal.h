@@ -104,6 +104,11 @@ struct PermTable {  // the permeability table of k_permeability.hip
     DevBuf t;  // double [256]: (double)(float)exp(-(double)k / sigma)
 };
 
+struct SmoothTable {  // the link-weight table of k_smooth.hip
+    TableCache<std::tuple<double, int>> cache;  // (sigma_c, channels)
+    DevBuf t;  // double [255 * channels + 1]: floor(65536 * exp(-k / sigma_c) + 0.5) / 65536
+};
+
 struct CensusTables {  // the AD-Census cost tables (asw_methods.hip: ensure_census_tables)
     TableCache<std::tuple<int, int>> cache;  // (lambda_ad, lambda_census)
     DevBuf t;  // u8 TA[256] | TC[64]
@@ -138,6 +143,7 @@ struct asw_ctx {
     RefineTables refine;
     TwoPassTable twopass;
     PermTable perm;
+    SmoothTable smooth;
     CensusTables census;
     WMedianTables wm;
     PrepTables prep;
@@ -431,6 +437,28 @@ struct RefineLaunch {
     unsigned* counters;    // 3 words: rejected pixels, unfillable pixels, != 0 when dl leaves the domain
 };
 int launch_refine(hipStream_t s, const RefineLaunch& a);
+
+// ---- confidence-weighted edge-aware smoothing (k_smooth.hip): the fast global smoother; DESIGN.md section 4.25 ----
+struct SmoothLaunch {
+    const uint8_t* guide;  // dense interleaved 8U, C = 1 or 3 channels
+    int C;
+    const float* d;        // the map and its confidence: element i at d[i * stride], c[i * stride]
+    const float* c;        // stride 1: two dense planes; 2: the interleaved {disparity, confidence} pairs of launch_confidence
+    int stride;
+    int H, W, T;           // T iterations, 1..8
+    double lambda;
+    const double* Wt;      // SmoothTable: [255 * C + 1]
+    double* N;             // scratch, H * W doubles each: the two right-hand sides
+    double* D;
+    uint16_t* linkV;       // scratch, H * W each: the Wt index of a pixel's link to the pixel above / (transposed, [W][H]) to its left
+    uint16_t* linkHT;
+    double* cp;            // scratch, H * W doubles each: what a forward sweep leaves for its backward sweep
+    double* fN;
+    double* fD;
+    float* out;            // [H][W]; must not alias d / c
+};
+// prep, 2 * T passes (row, column, row, ...), final: 2 * T + 2 launches
+int launch_smooth(hipStream_t s, const SmoothLaunch& a);
 
 // ---- bilateral-grid ASW, k_bilgrid.hip ----
 // grid extents (last index per axis; both range axes share nz); ASW_ERR_BAD_ARGUMENT for rates <= 0 or a range axis too fine for LDS

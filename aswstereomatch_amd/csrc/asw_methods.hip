@@ -1,5 +1,6 @@
 // Method runners behind the selector stereoMatching (M.cpp:46-88): tables, scratch buffers and launch sequences of every
 // method, with the literals the selector hard-codes and the reference's error behaviour.
+#include <float.h>
 #include <limits.h>
 #include <math.h>
 #include <stdio.h>
@@ -1123,9 +1124,15 @@ extern "C" int asw_match_resident(asw_ctx* ctx, int slot, int disparity_type, in
 // ------------------------------------------------------------------------------------------
 // left-right refinement: cross-check, scan-line fill, weighted median (not in the reference)
 // ------------------------------------------------------------------------------------------
-int check_refine_params(const RefineParams& p, int rows, int cols, int channels)
+static int check_refine_frame(int rows, int cols)
 {
     if (rows <= 0 || cols <= 0 || (size_t)rows * cols >= ((size_t)1 << 31) || rows > 4 * 65535) return ASW_ERR_BAD_ARGUMENT;
+    return ASW_OK;
+}
+
+int check_refine_params(const RefineParams& p, int rows, int cols, int channels)
+{
+    ASW_TRY(check_refine_frame(rows, cols));
     if (p.n < 1 || p.n > 1025 || p.minD < -(1 << 20) || p.minD > (1 << 20)) return ASW_ERR_BAD_ARGUMENT;
     if (!(p.max_diff >= 0)) return ASW_ERR_BAD_ARGUMENT;
     if (p.win < 1 || p.win > 35 || p.win % 2 == 0) return ASW_ERR_BAD_ARGUMENT;
@@ -1176,11 +1183,87 @@ int run_refine(asw_ctx* ctx, const uint8_t* guide, int channels, const float* dl
     return ASW_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// confidence-weighted edge-aware smoothing: the fast global smoother (not in the reference)
+// ------------------------------------------------------------------------------------------
+int check_smooth_params(int rows, int cols, int channels, int word, double sigma_c, double lambda, bool wants_mask, int* iterations)
+{
+    ASW_TRY(check_refine_frame(rows, cols));
+    const int T = word & ~ASW_REFINE_SMOOTH;
+    if (!(word & ASW_REFINE_SMOOTH) || T < 1 || T > 8) return ASW_ERR_BAD_ARGUMENT;  // a stray bit makes T large (or the word negative)
+    if (!(sigma_c > 0 && sigma_c <= DBL_MAX) || !(lambda > 0 && lambda <= DBL_MAX)) return ASW_ERR_BAD_ARGUMENT;  // NaN fails both
+    if (wants_mask) return ASW_ERR_BAD_ARGUMENT;
+    if (channels != 1 && channels != 3) return ASW_ERR_UNSUPPORTED_LAYOUT;
+    *iterations = T;
+    return ASW_OK;
+}
+
+static int ensure_smooth_table(asw_ctx* ctx, double sigma_c, int channels)
+{
+    SmoothTable& t = ctx->smooth;
+    const auto key = std::make_tuple(sigma_c, channels);
+    if (t.cache.hit(key, ctx->stream)) return ASW_OK;
+    std::vector<double> wt((size_t)255 * channels + 1);
+    for (size_t k = 0; k < wt.size(); k++) wt[k] = floor(65536.0 * exp(-(double)k / sigma_c) + 0.5) / 65536.0;
+    ASW_TRY(t.cache.upload(t.t, wt.data(), wt.size() * sizeof(double)));
+    return t.cache.commit(key);
+}
+
+int run_smooth(asw_ctx* ctx, const uint8_t* guide, int channels, const float* d, const float* c, int stride, int H, int W,
+               int iterations, double sigma_c, double lambda, float* out)
+{
+    ASW_TRY(ensure_smooth_table(ctx, sigma_c, channels));
+    const size_t plane = (size_t)H * W;
+    DevBuf& nd = ctx->buf("smooth_nd");        // N | D
+    DevBuf& fwd = ctx->buf("smooth_forward");  // cp | fN | fD
+    DevBuf& link = ctx->buf("smooth_links");   // vertical | horizontal (transposed)
+    ASW_TRY(nd.ensure(plane * 2 * sizeof(double)));
+    ASW_TRY(fwd.ensure(plane * 3 * sizeof(double)));
+    ASW_TRY(link.ensure(plane * 2 * sizeof(uint16_t)));
+    SmoothLaunch a;
+    a.guide = guide; a.C = channels; a.d = d; a.c = c; a.stride = stride; a.H = H; a.W = W; a.T = iterations; a.lambda = lambda;
+    a.Wt = ctx->smooth.t.as<double>();
+    a.N = nd.as<double>(); a.D = a.N + plane;
+    a.cp = fwd.as<double>(); a.fN = a.cp + plane; a.fD = a.fN + plane;
+    a.linkV = link.as<uint16_t>(); a.linkHT = a.linkV + plane;
+    a.out = out;
+    return launch_smooth(ctx->stream, a);
+}
+
+// match_refined under ASW_REFINE_SMOOTH: the smoothing's own checks first (nothing is computed for a call that would be refused
+// after its match), then one LEFT match with its confidence under the checks of a plain match, then the smoothing of the frame's
+// {disparity, confidence} pairs into the frame's map.  The pairs no longer describe that map afterwards.
+static int match_smoothed(asw_ctx* ctx, Frame* f, int algorithm, int win_size, int min_disparity, int num_disparity, int word,
+                          double sigma_c, double lambda)
+{
+    f->invalidate_results();
+    int T = 0;
+    ASW_TRY(check_smooth_params(f->rows, f->cols, f->channels, word, sigma_c, lambda, false, &T));
+    ASW_TRY(run_method(ctx, f, algorithm, match_params(ASW_DISPARITY_LEFT, win_size, min_disparity, num_disparity), false, true, true));
+    asw_timing sum = ctx->timing;  // the match and its confidence
+    f->invalidate_results();  // whatever fails from here on, the slot holds no result
+    const float* pairs = f->dconf.as<float>();
+    ASW_HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
+    ASW_TRY(run_smooth(ctx, f->L.as<uint8_t>(), f->channels, pairs, pairs + 1, 2, f->rows, f->cols, T, sigma_c, lambda,
+                       f->disp.as<float>()));
+    ASW_HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
+    ASW_HIP_TRY(hipEventSynchronize(ctx->ev[1]));
+    float t = 0;
+    ASW_HIP_TRY(hipEventElapsedTime(&t, ctx->ev[0], ctx->ev[1]));
+    sum.total_ms += t;
+    sum.cost_ms = sum.total_ms - sum.aggregate_ms;
+    ctx->timing = sum;
+    f->has_disp = true; f->disp_rows = f->rows; f->disp_cols = f->cols;
+    return ASW_OK;
+}
+
 // Both directions of `algorithm` (RIGHT, then LEFT), each WTA map swapped out of the frame into context scratch as soon as it exists (the second
 // match cannot overwrite the first, nothing travels through the host), then the refinement into the frame's own map.
 int match_refined(asw_ctx* ctx, Frame* f, int algorithm, int win_size, int min_disparity, int num_disparity, float max_diff,
                   int refine_win, double gamma_c, double gamma_s, int* n_rejected, int* n_unfillable)
 {
+    if (refine_win > 0 && (refine_win & ASW_REFINE_SMOOTH))  // no window has bit 30: asw_match_smoothed_resident / asw_stereo_match_smoothed
+        return match_smoothed(ctx, f, algorithm, win_size, min_disparity, num_disparity, refine_win, gamma_c, gamma_s);
     f->invalidate_results();
     const MethodInfo* m = method_info(algorithm);
     if (m && m->no_volume) return ASW_ERR_UNSUPPORTED_METHOD;  // SGBM / BM carry their own disp12MaxDiff

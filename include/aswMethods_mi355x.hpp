@@ -556,6 +556,38 @@ inline AswMat stereoMatchingRefined(AswMat srcLeft, AswMat srcRight, StereoMatch
     }, "stereoMatchingRefined");
 }
 
+// Not in the reference: confidence-weighted edge-aware smoothing (asw_smooth_disparity; asw_mi355x.h "Smoothing", DESIGN.md section
+// 4.25) of a CV_32FC1 map with a CV_32FC1 trust value per pixel (e.g. the two maps of stereoMatchingConfidence, or a 0/1 validity mask),
+// guided by an 8-bit image of 1 or 3 channels -> the dense fractional map.  The defaults are the paper's demonstration values.  Throws
+// like refineDisparity.
+inline AswMat smoothDisparity(AswMat guide, AswMat disparityMap, AswMat confidenceMap, double sigma_c = 8.0, double lambda = 900.0,
+                              int iterations = 3)
+{
+    if (disparityMap.rows != confidenceMap.rows || disparityMap.cols != confidenceMap.cols || guide.rows != disparityMap.rows ||
+        guide.cols != disparityMap.cols)
+        return AswMat();
+    AswMat out = asw::detail::make(disparityMap.rows, disparityMap.cols, ASW_32F, 1);
+    asw_image g = asw::detail::view(guide), a = asw::detail::view(disparityMap), b = asw::detail::view(confidenceMap), o = asw::detail::view(out);
+    if (a.depth != ASW_32F || b.depth != ASW_32F || a.channels != 1 || b.channels != 1 || a.step != (size_t)a.cols * 4 ||
+        b.step != (size_t)b.cols * 4 || o.step != (size_t)o.cols * 4)
+        throw std::runtime_error("smoothDisparity: continuous CV_32FC1 maps expected");
+    int rc = asw_smooth_disparity(asw::detail::context(), &g, (const float*)a.data, (const float*)b.data, sigma_c, lambda, iterations,
+                                  (float*)o.data);
+    asw::detail::raise_unless_ok(rc, "smoothDisparity");
+    return rc == ASW_OK ? out : AswMat();
+}
+
+// Not in the reference: ONE DISPARITY_LEFT stereoMatching with its confidence + smoothDisparity with srcLeft as guide
+// (asw_stereo_match_smoothed); serves the methods stereoMatchingRefined refuses for their missing DISPARITY_RIGHT branch
+inline AswMat stereoMatchingSmoothed(AswMat srcLeft, AswMat srcRight, StereoMatchingAlgorithms algorithmType, int winSize = 15,
+                                     int minDisparity = 0, int numDisparity = 64, double sigma_c = 8.0, double lambda = 900.0,
+                                     int iterations = 3)
+{
+    return asw::detail::aggregate(srcLeft, srcRight, [&](asw_ctx* c, asw_image* l, asw_image* r, asw_image* o) {
+        return asw_stereo_match_smoothed(c, l, r, o, (int)algorithmType, winSize, minDisparity, numDisparity, sigma_c, lambda, iterations);
+    }, "stereoMatchingSmoothed");
+}
+
 // M.h:156 / M.cpp:2442-2503: ONE disparity; the view that is not the reference view arrives bordered by the caller
 // (copyMakeBorder by max_offset, M.cpp:2877-2878).  Empty Mat for an even window or a bordered view that is not wider.
 inline AswMat getCostSAD_d(AswMat leftImg, AswMat rightImg, int disparity, DisparityType dispType = DISPARITY_LEFT, int winSize = 35)

@@ -557,6 +557,71 @@ int asw_match_refined_resident(asw_ctx* ctx, int slot, int algorithm, int win_si
 int asw_stereo_match_refined(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp, int algorithm,
                              int win_size, int min_disparity, int num_disparity, float max_diff, int refine_win, double gamma_c,
                              double gamma_s, int* n_rejected, int* n_unfillable);
+/* ---- Smoothing: confidence-weighted edge-aware smoothing of a disparity map (not in the reference) ----
+ * The fast global smoother of Min, Choi, Lu, Ham, Sohn, Do ("Fast global image smoothing based on weighted least squares", TIP
+ * 2014) applied the way OpenCV's DisparityWLSFilter applies it: the map times its confidence and the confidence itself are smoothed
+ * along the guide's edges and divided, so unreliable pixels are pulled towards reliable neighbours of similar colour.  It takes ONE
+ * match (the left-right refinement above takes two), serves every method that has a confidence, and returns a dense fractional map.
+ * Inputs: guide G, ASW_8U, 1 or 3 channels, rows x cols, its step honoured; d: dense f32 map; c: dense f32 confidence (the second
+ * channel of a 2-channel disparity image, or any trust value: a 0/1 validity mask is a legal confidence); sigma_c and lambda finite
+ * and > 0; T iterations, 1..8.  All arithmetic is f64, one IEEE operation per written operation, in the written order, never
+ * contracted; N and D stay f64 from step 2 to step 6:
+ *   1. ce = (isfinite(d) && isfinite(c) && c > 0) ? (double)c : 0  (selects: a non-finite value never enters a product);
+ *   2. N0 = ce > 0 ? ce * (double)d : 0,  D0 = ce: non-finite map values and non-positive confidences are holes;
+ *   3. Wt[k] = floor(65536 * exp(-k / sigma_c) + 0.5) / 65536, k = 0 .. 255 * channels (host, double, libm; quantised like Tc above, so
+ *      a last-bit difference between libms cannot move it);
+ *   4. wh(y, x) = Wt[sum over channels |G(y,x) - G(y,x-1)|] for x >= 1, wv(y, x) the same with the pixel above for y >= 1;
+ *   5. for t = 1..T: lam_t = (1.5 * lambda * (double)(1 << 2*(T-t))) / (double)((1 << 2*T) - 1); a pass over every row, then a pass
+ *      over every column; a pass solves one tridiagonal system per line for the two right-hand sides N and D of the previous pass.
+ *      For a line of length n with link weights w_1 .. w_{n-1} and right-hand side f:
+ *        a_i = -(lam_t * w_i), a_0 = 0;  c_i = -(lam_t * w_{i+1}), c_{n-1} = 0;  b_i = (1.0 - a_i) - c_i;
+ *        forward:  m_0 = b_0,  m_i = b_i - a_i * cp_{i-1};  r_i = 1.0 / m_i;  cp_i = c_i * r_i;
+ *                  fp_0 = f_0 * r_0,  fp_i = (f_i - a_i * fp_{i-1}) * r_i   (one reciprocal per step, shared by N and D);
+ *        backward: u_{n-1} = fp_{n-1},  u_i = fp_i - cp_i * u_{i+1};
+ *      a line of length 1 returns its input;
+ *   6. out = D_T > 0 ? (float)(N_T / D_T) : d, the input's bits unchanged (a frame, or a region cut off by zero weights, without a
+ *      confident pixel).
+ * The request travels in the refinement family's win_size / refine_win argument as a value no window can take, ASW_REFINE_SMOOTH | T;
+ * under it gamma_c carries sigma_c, gamma_s carries lambda and disp_right the confidence plane; the library does not look at
+ * min_disparity, num_values or max_diff, places no domain requirement on the map and writes neither count.  The three functions
+ * below are inline functions of this header, not symbols of the library (the exported set stays as it is).  Every win_size /
+ * refine_win without bit 30 behaves as described above.
+ * asw_smooth_disparity: the checks, in this order: null pointers and the guide as an image, as asw_refine_disparity; rows <= 262140
+ * and rows * cols < 2^31; the word (iterations outside 1..8 travel as the invalid word ASW_REFINE_SMOOTH | 0): ASW_ERR_BAD_ARGUMENT;
+ * sigma_c / lambda not finite and > 0: ASW_ERR_BAD_ARGUMENT; guide channels not 1 or 3: ASW_ERR_UNSUPPORTED_LAYOUT.  (A caller of
+ * asw_refine_disparity itself who passes a mask_out under the flag gets ASW_ERR_BAD_ARGUMENT in front of the channel check.)
+ * Nothing of the caller's is written on a refusal.
+ * asw_match_smoothed_resident: ONE DISPARITY_LEFT match of `algorithm` on the resident pair of `slot`, with its volume written and
+ * the confidence of the 2-channel disparity image computed from it; then the integer winner-take-all map is smoothed with that
+ * confidence and the resident left image as guide, and the result becomes the slot's disparity (no volume is kept, as after
+ * asw_match_refined_resident).  The methods without a DISPARITY_RIGHT branch are served.  The smoothing's own checks (frame size,
+ * word, sigma_c, lambda, channels, as above) come first, so that nothing is computed for a call they refuse; then the argument
+ * checks of asw_match_resident apply, in their order; a method that cannot give a confidence (ASW_ALG_SGBM, ASW_ALG_BM,
+ * ASW_ALG_NCC, a value outside the table) returns what a 2-channel asw_stereo_match returns for it.  A failure drops the slot's
+ * results and leaves the pair alone.  asw_get_timing afterwards: aggregate_ms / aggregate_launches are the match's, total_ms = the
+ * match + the confidence + the smoothing (its 2 T + 2 launches), cost_ms = total_ms - aggregate_ms.
+ * asw_stereo_match_smoothed: the same on host images, on the context's private frame; disp: ASW_32F, 1 channel.
+ * The carrier has no disparity_type: the matched forms are LEFT-view matches without sub-pixel, cross-scale or scanline flags.  A
+ * caller who wants a flagged match makes a 2-channel call and hands its two channels to asw_smooth_disparity. */
+enum { ASW_REFINE_SMOOTH = 0x40000000 }; /* win_size / refine_win = ASW_REFINE_SMOOTH | T, T in 1..8 */
+static inline int asw_smooth_disparity(asw_ctx* ctx, const asw_image* guide, const float* disp, const float* conf, double sigma_c,
+                                       double lambda, int iterations, float* out)
+{
+    return asw_refine_disparity(ctx, guide, disp, conf, 0, 1, 0.f, ASW_REFINE_SMOOTH | (iterations >= 1 && iterations <= 8 ? iterations : 0), sigma_c, lambda, out, NULL, NULL, NULL);
+}
+static inline int asw_match_smoothed_resident(asw_ctx* ctx, int slot, int algorithm, int win_size, int min_disparity, int num_disparity,
+                                              double sigma_c, double lambda, int iterations)
+{
+    return asw_match_refined_resident(ctx, slot, algorithm, win_size, min_disparity, num_disparity, 0.f, ASW_REFINE_SMOOTH | (iterations >= 1 && iterations <= 8 ? iterations : 0),
+                                      sigma_c, lambda, NULL, NULL);
+}
+static inline int asw_stereo_match_smoothed(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp, int algorithm,
+                                            int win_size, int min_disparity, int num_disparity, double sigma_c, double lambda,
+                                            int iterations)
+{
+    return asw_stereo_match_refined(ctx, left, right, disp, algorithm, win_size, min_disparity, num_disparity, 0.f,
+                                    ASW_REFINE_SMOOTH | (iterations >= 1 && iterations <= 8 ? iterations : 0), sigma_c, lambda, NULL, NULL);
+}
 /* cvtColor(COLOR_BGR2GRAY) as used at M.cpp:1031-1033 */
 int asw_bgr2gray(asw_ctx* ctx, const asw_image* bgr, uint8_t* gray);
 

@@ -69,6 +69,14 @@ against the restatement of tests/confidence_ref.py applied to the returned volum
 from confidence_ref.random_case and a mismatch prints the tag confidence_ref.build_case rebuilds.
 
     python tools/fuzz_parity.py --seconds 120 --seed 1 --only confidence
+
+The leg smooth is the confidence-weighted smoothing (asw_mi355x.h "Smoothing"): asw_smooth_disparity on small
+frames around the kernels' tile constants, guides of five kinds with and without padded rows, maps with NaN and infinities, confidences
+with zeros, negatives, NaN and values above 1, T in 1..8, lambda from 2^-10 to 2^20, sigma_c from 0.05 to 1000, against the restatement
+of tests/smooth_ref.py, bit pattern for bit pattern: the context's first and second call and a fresh context's; its cases come from
+smooth_ref.random_case and a mismatch prints the tag smooth_ref.build_case rebuilds.
+
+    python tools/fuzz_parity.py --seconds 120 --seed 1 --only smooth
 """
 import argparse
 import os
@@ -90,6 +98,7 @@ import matcher_cases as mc  # noqa: E402
 import permeability_ref  # noqa: E402
 import scanline_ref  # noqa: E402
 import sgbm_census_ref as scr  # noqa: E402
+import smooth_ref  # noqa: E402
 from selector_methods import METHODS as SELECTOR_METHODS  # noqa: E402
 
 A = asw.StereoMatchingAlgorithms
@@ -120,7 +129,8 @@ REF_LEGS.update((m.name, m) for m in SELECTOR_METHODS[2:])
 REF_LEGS["permeability"] = permeability_ref  # behind the others: the legs before it keep the cases a seed drew for them
 REF_LEGS["cross_scale"] = cross_scale_ref    # behind those, for the same reason
 REF_LEGS["scanline"] = scanline_ref          # behind those, for the same reason
-REF_LEGS["confidence"] = confidence_ref      # last, for the same reason
+REF_LEGS["confidence"] = confidence_ref      # behind those, for the same reason
+REF_LEGS["smooth"] = smooth_ref              # last, for the same reason
 LEGS = tuple(mc.FAMILIES) + tuple(REF_LEGS)
 ORACLE_METHODS = ["classic", "direct8", "geodesic", "guided", "guided2", "guided3", "wmedian", "blo1", "ncc", "ncc_cost",
                   "ad_tad", "similarity", "sad", "geodist", "gfilter", "prep", "bilgrid", "lrcheck", "resident", "batch"]
