@@ -560,16 +560,14 @@ static int disp16_stage(asw_ctx* ctx, const asw_image* left, const asw_image* ri
         *vol_dev = vol.as<float>();
     }
     *frame = f;
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
-    return ASW_OK;
+    return ctx->clock.begin_total();
 }
 
 // disp16_finish: the clock stopped, the device map (elements of `elem` bytes) into the caller's pitched map, the volume into its buffer
-static int disp16_finish(asw_ctx* ctx, int launches, asw_image* map, const void* map_dev, size_t elem, float* cost_volume_out,
+static int disp16_finish(asw_ctx* ctx, asw_image* map, const void* map_dev, size_t elem, float* cost_volume_out,
                          const float* vol_dev, int numD)
 {
-    ASW_TRY(timed_finish(ctx));
-    ctx->timing.aggregate_launches = launches;
+    ASW_TRY(ctx->clock.finish(true));
     const size_t row = (size_t)map->cols * elem;
     ASW_HIP_TRY(copy_rows(ctx, map->data, map->step, map_dev, row, row, map->rows, hipMemcpyDeviceToHost));
     if (cost_volume_out)
@@ -603,12 +601,12 @@ static int sgbm_host(asw_ctx* ctx, const asw_image* left, const asw_image* right
     ASW_TRY(disp16_stage(ctx, left, right, num_disparities, "sgbm_volume", cost_volume_out, cost_volume_floats, &f, &a.vol));
     a.L = f->L.as<uint8_t>(); a.R = f->R.as<uint8_t>();
     if (census) ASW_TRY(gray_pair(ctx, a.L, a.R, left->channels, H, W, &a.L, &a.R));  // the cost reads one gray plane per image
-    a.ev_agg0 = ctx->ev[2]; a.ev_agg1 = ctx->ev[3];
-    ASW_TRY(launch_sgbm(ctx->stream, a));
     // k_sgbm_top, k_sgbm_row + one k_sgbm_line per line geometry in use (columns, diagonals, anti-diagonals)
     const int launches = 2 + !!(paths & ASW_SGBM_PATH_BT) + !!(paths & (ASW_SGBM_PATH_TLBR | ASW_SGBM_PATH_BRTL)) +
                          !!(paths & (ASW_SGBM_PATH_TRBL | ASW_SGBM_PATH_BLTR));
-    return disp16_finish(ctx, launches, disp16, a.disp16, sizeof(short), cost_volume_out, a.vol, num_disparities);
+    a.agg = {&ctx->clock, launches};
+    ASW_TRY(launch_sgbm(ctx->stream, a));
+    return disp16_finish(ctx, disp16, a.disp16, sizeof(short), cost_volume_out, a.vol, num_disparities);
 }
 
 extern "C" int asw_sgbm(asw_ctx* ctx, const asw_image* left, const asw_image* right, asw_image* disp16, int min_disparity,
@@ -642,12 +640,11 @@ extern "C" int asw_filter_speckles(asw_ctx* ctx, asw_image* img, int new_val, in
     ASW_TRY(scratch.ensure(plane * 2 * sizeof(int)));
     const size_t row = (size_t)W * sizeof(short);
     ASW_HIP_TRY(copy_rows(ctx, buf.p, row, img->data, img->step, row, H, hipMemcpyHostToDevice));
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
+    ASW_TRY(ctx->clock.begin_total());
+    ASW_TRY(ctx->clock.begin_aggregate());
     ASW_TRY(launch_filter_speckles(ctx->stream, buf.as<short>(), H, W, new_val, max_speckle_size, max_diff, scratch.as<int>()));
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
-    ASW_TRY(timed_finish(ctx));
-    ctx->timing.aggregate_launches = 4;  // k_spk_init, union, flatten, apply (+ the pointer-jumping rounds between them)
+    ASW_TRY(ctx->clock.end_aggregate(4));  // k_spk_init, union, flatten, apply (+ the pointer-jumping rounds between them)
+    ASW_TRY(ctx->clock.finish(true));
     ASW_HIP_TRY(copy_rows(ctx, img->data, img->step, buf.p, row, row, H, hipMemcpyDeviceToHost));
     ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ASW_OK;
@@ -676,9 +673,9 @@ extern "C" int asw_stereo_bm(asw_ctx* ctx, const asw_image* left, const asw_imag
     Frame* f;
     ASW_TRY(disp16_stage(ctx, left, right, num_disparities, "bm_volume", cost_volume_out, cost_volume_floats, &f, &a.vol));
     a.L = f->L.as<uint8_t>(); a.R = f->R.as<uint8_t>();
-    a.ev_agg0 = ctx->ev[2]; a.ev_agg1 = ctx->ev[3];
+    a.agg = {&ctx->clock, 1};
     ASW_TRY(launch_bm(ctx->stream, a));
-    return disp16_finish(ctx, 1, disp16, a.disp16, sizeof(short), cost_volume_out, a.vol, num_disparities);
+    return disp16_finish(ctx, disp16, a.disp16, sizeof(short), cost_volume_out, a.vol, num_disparities);
 }
 
 // getDisparity_BM (aswMethods.cpp:100-146): the CV_Error cases (numDisparity % 16 != 0, an even winSize, an empty image, and
@@ -713,8 +710,8 @@ extern "C" int asw_get_disparity_bm(asw_ctx* ctx, const asw_image* left, const a
     Frame* f;
     ASW_TRY(disp16_stage(ctx, left, right, num_disparities, nullptr, nullptr, 0, &f, &a.vol));
     ASW_TRY(gray_pair(ctx, f->L.as<uint8_t>(), f->R.as<uint8_t>(), cn, H, W, &a.L, &a.R));
-    a.ev_agg0 = ctx->ev[2]; a.ev_agg1 = ctx->ev[3];
+    a.agg = {&ctx->clock, 1};
     ASW_TRY(launch_bm(ctx->stream, a));
     ASW_TRY(launch_disp16_to_u8(ctx->stream, a.disp16, plane, u8.as<uint8_t>()));
-    return disp16_finish(ctx, 1, disp_u8, u8.p, 1, nullptr, nullptr, 0);
+    return disp16_finish(ctx, disp_u8, u8.p, 1, nullptr, nullptr, 0);
 }

@@ -78,14 +78,16 @@ extern "C" int asw_create(int device_id, asw_ctx** out)
         delete c;
         return ASW_ERR_HIP;
     }
-    for (int i = 0; i < 4; i++)
-        if (hipEventCreate(&c->ev[i]) != hipSuccess) {
+    c->clock.stream = c->stream;
+    for (hipEvent_t* e : {&c->clock.total_start, &c->clock.total_stop, &c->clock.agg_start, &c->clock.agg_stop})
+        if (hipEventCreate(e) != hipSuccess) {
             delete c;
             return ASW_ERR_HIP;
         }
     bool ok = true;
-    for (int i = 0; i < 2; i++) ok = ok && hipStreamCreateWithFlags(&c->aux[i], hipStreamNonBlocking) == hipSuccess;
-    for (int i = 0; i < 3; i++) ok = ok && hipEventCreateWithFlags(&c->aux_ev[i], hipEventDisableTiming) == hipSuccess;
+    for (hipStream_t& s : c->side.stream) ok = ok && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess;
+    for (hipEvent_t* e : {&c->side.fork, &c->side.joined[0], &c->side.joined[1]})
+        ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
     if (!ok) {
         delete c;
         return ASW_ERR_HIP;
@@ -118,7 +120,7 @@ extern "C" int asw_set_gray_bits(asw_ctx* ctx, int bits)
 extern "C" int asw_get_timing(asw_ctx* ctx, asw_timing* out)
 {
     if (!ctx || !out) return ASW_ERR_BAD_ARGUMENT;
-    *out = ctx->timing;
+    *out = ctx->clock.timing;
     return ASW_OK;
 }
 

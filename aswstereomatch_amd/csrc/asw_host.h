@@ -55,8 +55,6 @@ int download_disparity_from(asw_ctx* ctx, Frame* f, asw_image* disp);
 int download_volume_from(asw_ctx* ctx, Frame* f, float* out, size_t n_floats);
 // 3 channels: cvtColor(BGR2GRAY) of both images into the scratch planes "grayL" / "grayR"; 1 channel: the images as they are
 int gray_pair(asw_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int channels, int H, int W, const uint8_t** gl, const uint8_t** gr);
-// records ev[1], waits for the stream and fills ctx->timing's three times from ev[0..3]
-int timed_finish(asw_ctx* ctx);
 int build_similarity_volume(asw_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int H, int W, int minD, int numD,
                                    double regularity, double thresC, double thresG, float* cost,
                                    uint32_t* ord_scratch = nullptr, float2* scales = nullptr);

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "asw_devmem.h"
+#include "asw_streams.h"
 
 // The one way a kernel is launched: ASW_LAUNCH(kernel, grid, block, dynamic LDS bytes, stream, arguments...) gives an asw_status.
 //   - more than 160 KB of dynamic LDS (a workgroup's whole share on gfx950): ASW_ERR_BAD_ARGUMENT, nothing is launched;
@@ -147,12 +148,8 @@ struct asw_ctx {
     CensusTables census;
     WMedianTables wm;
     PrepTables prep;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // total start/stop, aggregate start/stop
-    // side streams for small launches that are independent of a method's main kernel (border tiles and the one-candidate tail
-    // of the classic bilateral method: 0.5 ms each when serialised, latency-bound) + fork / join events
-    hipStream_t aux[2] = {nullptr, nullptr};
-    hipEvent_t aux_ev[3] = {nullptr, nullptr, nullptr};
-    asw_timing timing = {0, 0, 0, 0};
+    CallClock clock;  // the call's four timing events and the asw_timing they give (asw_streams.h)
+    SideSet side;     // the two side streams and their fork / join events; a runner uses them through a SideStreams scope
     DevBuf& buf(const char* name) { return scratch[name]; }
     asw_ctx() = default;
     asw_ctx(const asw_ctx&) = delete;
@@ -161,13 +158,13 @@ struct asw_ctx {
     ~asw_ctx()
     {
         (void)hipSetDevice(device);
-        for (hipStream_t s : {stream, aux[0], aux[1]})
+        for (hipStream_t s : {stream, side.stream[0], side.stream[1]})
             if (s) (void)hipStreamSynchronize(s);
-        for (hipEvent_t e : ev)
+        for (hipEvent_t e : {clock.total_start, clock.total_stop, clock.agg_start, clock.agg_stop})
             if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : aux_ev)
+        for (hipEvent_t e : {side.fork, side.joined[0], side.joined[1]})
             if (e) (void)hipEventDestroy(e);
-        for (hipStream_t s : {stream, aux[0], aux[1]})
+        for (hipStream_t s : {stream, side.stream[0], side.stream[1]})
             if (s) (void)hipStreamDestroy(s);
     }
 };
@@ -501,7 +498,7 @@ struct SgbmLaunch {
     void* scratch;     // sgbm_scratch_bytes()
     short* disp16;     // out [H][W], scaled by 16
     float* vol;        // optional S [D][H][W]
-    hipEvent_t ev_agg0 = nullptr, ev_agg1 = nullptr;  // optional: recorded around the path kernels (asw_timing::aggregate_ms)
+    AggMarks agg;      // optional: the clock's aggregate marks go around the path kernels (asw_timing::aggregate_ms)
 };
 size_t sgbm_scratch_bytes(int H, int W, int cn, int minD, int D);
 int launch_sgbm(hipStream_t s, const SgbmLaunch& a);
@@ -523,7 +520,7 @@ struct BmLaunch {
     void* scratch;     // bm_scratch_bytes()
     short* disp16;     // out [H][W], scaled by 16, FILTERED = 16 * (minD - 1)
     float* vol;        // optional SAD [D][H][W] (plane p <-> disparity minD + p), NaN where nothing is computed
-    hipEvent_t ev_agg0 = nullptr, ev_agg1 = nullptr;  // optional: recorded around k_bm_match (asw_timing::aggregate_ms)
+    AggMarks agg;      // optional: the clock's aggregate marks go around k_bm_match (asw_timing::aggregate_ms)
 };
 size_t bm_scratch_bytes(int H, int W);
 int launch_bm(hipStream_t s, const BmLaunch& a);

@@ -59,32 +59,9 @@ static int slice_scratch(asw_ctx* ctx, int slices, size_t plane, double** E, flo
     return ASW_OK;
 }
 
-// the event pair around a method's aggregation kernels (asw_timing::aggregate_ms) and the launch count that goes with it
-static int agg_begin(asw_ctx* ctx)
-{
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
-    return ASW_OK;
-}
-
-static int agg_end(asw_ctx* ctx, int launches)
-{
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
-    ctx->timing.aggregate_launches = launches;
-    return ASW_OK;
-}
-
-int timed_finish(asw_ctx* ctx)
-{
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
-    ASW_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    float t = 0;
-    ASW_HIP_TRY(hipEventElapsedTime(&t, ctx->ev[0], ctx->ev[1]));
-    ctx->timing.total_ms = t;
-    ASW_HIP_TRY(hipEventElapsedTime(&t, ctx->ev[2], ctx->ev[3]));
-    ctx->timing.aggregate_ms = t;
-    ctx->timing.cost_ms = ctx->timing.total_ms - ctx->timing.aggregate_ms;
-    return ASW_OK;
-}
+// the clock's marks around a method's aggregation kernels (asw_timing::aggregate_ms) and the launch count that goes with them
+static int agg_begin(asw_ctx* ctx) { return ctx->clock.begin_aggregate(); }
+static int agg_end(asw_ctx* ctx, int launches) { return ctx->clock.end_aggregate(launches); }
 
 // ------------------------------------------------------------------------------------------
 // classic bilateral ASW: host-side tables (tap list with the reference's two index conventions,
@@ -243,20 +220,18 @@ static int run_bilateral(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool kee
         ASW_TRY(agg_begin(ctx));
         // fork: border tiles and the tail are independent of the interior launch (they write other pixels / another slice of the
         // per-slice winners); on side streams they overlap it instead of adding two latency-bound 0.5 ms launches to the frame
-        ASW_HIP_TRY(hipEventRecord(ctx->aux_ev[0], ctx->stream));
-        ASW_HIP_TRY(hipStreamWaitEvent(ctx->aux[0], ctx->aux_ev[0], 0));
-        ASW_TRY(launch_bilateral_xq(ctx->stream, ctx->aux[0], xq_waves, a.gL, a.gR, H, W, mp.minD, ctx->bil.cells.as<int4>(), ctx->bil.lut_xq.as<float>(), a.vol,
+        SideStreams side(ctx->stream, ctx->side);
+        hipStream_t s_border = nullptr, s_tail = nullptr;
+        ASW_TRY(side.use(0, &s_border));
+        ASW_TRY(launch_bilateral_xq(ctx->stream, s_border, xq_waves, a.gL, a.gR, H, W, mp.minD, ctx->bil.cells.as<int4>(), ctx->bil.lut_xq.as<float>(), a.vol,
                                     a.partE, a.partD, tail && !last ? nullptr : a.disp, flip != 0, last));
-        ASW_HIP_TRY(hipEventRecord(ctx->aux_ev[1], ctx->aux[0]));
         if (tail) {
-            ASW_HIP_TRY(hipStreamWaitEvent(ctx->aux[1], ctx->aux_ev[0], 0));
+            ASW_TRY(side.use(1, &s_tail));
             a.out_slice = 1;  // candidates [128 | 64, nD) -> slice 1; the xq launches fill slice 0
             if (last) { a.col_lo = bc_lo; a.col_hi = bc_hi; }
-            ASW_TRY(launch_bilateral(ctx->aux[1], a));
-            ASW_HIP_TRY(hipEventRecord(ctx->aux_ev[2], ctx->aux[1]));
-            ASW_HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->aux_ev[2], 0));
+            ASW_TRY(launch_bilateral(s_tail, a));
         }
-        ASW_HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->aux_ev[1], 0));  // join
+        ASW_TRY(side.join());
         // strict '<', ascending d
         if (tail && last) ASW_TRY(launch_merge_slices_cols(ctx->stream, a.partE, a.partD, 2, H, W, bc_lo, bc_hi, a.disp));
         else if (tail) ASW_TRY(launch_merge_slices(ctx->stream, a.partE, a.partD, 2, plane, a.disp));
@@ -400,13 +375,13 @@ static int run_ncc(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep_volu
     if (mp.win < 1 || mp.win > std::min(ncc_max_window(), walk_max_kernel())) return ASW_ERR_BAD_ARGUMENT;  // run_ncc_cost's limit, before agg_begin
     const int H = f->rows, W = f->cols;
     const bool right = mp.disparity_type == ASW_DISPARITY_RIGHT;
+    if (right && keep_volume) return ASW_ERR_UNSUPPORTED_LAYOUT;  // the RIGHT view has no selector volume: before any work
     // LEFT, kept: the raw (un-normalised) costs of all numD offsets, for inspection
-    ASW_TRY(ensure_outputs(f, mp.numD, keep_volume && !right));
+    ASW_TRY(ensure_outputs(f, mp.numD, keep_volume));
     ASW_TRY(agg_begin(ctx));
-    if (right) {
+    if (right)
         ASW_HIP_TRY(hipMemsetAsync(f->disp.p, 0, (size_t)H * W * 4, ctx->stream));
-        if (keep_volume) return ASW_ERR_UNSUPPORTED_LAYOUT;
-    } else
+    else
         ASW_TRY(run_ncc_cost(ctx, f->L.as<uint8_t>(), f->R.as<uint8_t>(), H, W, mp.disparity_type, mp.win, mp.minD, mp.numD,
                              keep_volume ? f->vol.as<float>() : nullptr, f->disp.as<float>(), mp.numD - 1));
     return agg_end(ctx, 1);
@@ -554,30 +529,28 @@ static int run_geodesic(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool keep
         double* sE;
         float* sD;
         ASW_TRY(slice_scratch(ctx, nD / 64 + 2, plane, &sE, &sD));
-        ASW_HIP_TRY(hipEventRecord(ctx->aux_ev[0], ctx->stream));  // fork: border tiles and the tail run beside the passes
-        ASW_HIP_TRY(hipStreamWaitEvent(ctx->aux[0], ctx->aux_ev[0], 0));
-        ASW_HIP_TRY(hipStreamWaitEvent(ctx->aux[1], ctx->aux_ev[0], 0));
+        SideStreams side(ctx->stream, ctx->side);  // fork: border tiles and the leftover run beside the passes
+        hipStream_t s_border = nullptr, s_left = nullptr;
+        ASW_TRY(side.use(0, &s_border));
         int cb = 0, ns = 0;
         for (int nw = 8; nw >= 4; nw /= 2)
             while (nD - cb >= geodesic_xq_pass_candidates(nw)) {
-                ASW_TRY(launch_geodesic_xq(ctx->stream, ctx->aux[0], nw, pf, po, wf, wo, H, W, mp.minD, cb, vol,
+                ASW_TRY(launch_geodesic_xq(ctx->stream, s_border, nw, pf, po, wf, wo, H, W, mp.minD, cb, vol,
                                            sE + (size_t)ns * plane, sD + (size_t)ns * plane, flip != 0));
                 cb += geodesic_xq_pass_candidates(nw);
                 ns++;
             }
+        if (cb < nD) ASW_TRY(side.use(1, &s_left));
         if (cb < nD && nD - cb <= 4) {  // the reference's inclusive range: one candidate behind the passes at numDisparity = 192
-            ASW_TRY(launch_asw_geodesic_few(ctx->aux[1], pf, po, wf, wo, H, W, mp.minD, cb, nD, flip != 0, vol, sE + (size_t)ns * plane,
+            ASW_TRY(launch_asw_geodesic_few(s_left, pf, po, wf, wo, H, W, mp.minD, cb, nD, flip != 0, vol, sE + (size_t)ns * plane,
                                             sD + (size_t)ns * plane));
             ns++;
         } else if (cb < nD) {
-            ASW_TRY(launch_asw_geodesic(ctx->aux[1], pf, po, wf, wo, H, W, mp.win, mp.minD, nD, flip, vol, f->disp.as<float>(), sE, sD,
+            ASW_TRY(launch_asw_geodesic(s_left, pf, po, wf, wo, H, W, mp.win, mp.minD, nD, flip, vol, f->disp.as<float>(), sE, sD,
                                         cb, ns));
             ns++;
         }
-        ASW_HIP_TRY(hipEventRecord(ctx->aux_ev[1], ctx->aux[0]));
-        ASW_HIP_TRY(hipEventRecord(ctx->aux_ev[2], ctx->aux[1]));
-        ASW_HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->aux_ev[1], 0));  // join
-        ASW_HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->aux_ev[2], 0));
+        ASW_TRY(side.join());
         ASW_TRY(launch_merge_slices(ctx->stream, sE, sD, ns, plane, f->disp.as<float>()));
     } else
         ASW_TRY(launch_asw_geodesic(ctx->stream, pf, po, wf, wo, H, W, mp.win, mp.minD, nD, flip, vol, f->disp.as<float>(), partE, partD));
@@ -789,12 +762,10 @@ static int run_sgbm(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool /* keep_
     ASW_TRY(sgbm_prepare(ctx, p, f->rows, f->cols, cn, false, &a));
     a.L = f->L.as<uint8_t>(); a.R = f->R.as<uint8_t>();
     a.vol = nullptr;
-    a.ev_agg0 = ctx->ev[2]; a.ev_agg1 = ctx->ev[3];
+    a.agg = {&ctx->clock, 2};
     ASW_TRY(ensure_outputs(f, 0, false));
     ASW_TRY(launch_sgbm(ctx->stream, a));
-    ASW_TRY(launch_disp16_to_u8f(ctx->stream, a.disp16, (size_t)f->rows * f->cols, f->disp.as<float>()));
-    ctx->timing.aggregate_launches = 2;
-    return ASW_OK;
+    return launch_disp16_to_u8f(ctx->stream, a.disp16, (size_t)f->rows * f->cols, f->disp.as<float>());
 }
 
 // ------------------------------------------------------------------------------------------
@@ -936,16 +907,16 @@ static int run_permeability(asw_ctx* ctx, Frame* f, const MatchParams& mp, bool 
     PermLaunch nl = a;
     nl.cost = ones.as<uint8_t>(); nl.nc = 1; nl.cbeg = 0; nl.first = 1; nl.ck = nck.as<double>(); nl.hs = nhs.as<double>();
     nl.N = nullptr; nl.Nout = nrm.as<double>(); nl.vol = nullptr;
-    ASW_HIP_TRY(hipEventRecord(ctx->aux_ev[0], ctx->stream));  // fork: behind the permeability planes
-    ASW_HIP_TRY(hipStreamWaitEvent(ctx->aux[0], ctx->aux_ev[0], 0));
-    ASW_TRY(launch_perm_scan_h(ctx->aux[0], nl));
-    ASW_TRY(launch_perm_scan_v(ctx->aux[0], nl));
-    ASW_HIP_TRY(hipEventRecord(ctx->aux_ev[1], ctx->aux[0]));
+    SideStreams side(ctx->stream, ctx->side);
+    hipStream_t s_n = nullptr;
+    ASW_TRY(side.use(0, &s_n));  // fork: behind the permeability planes
+    ASW_TRY(launch_perm_scan_h(s_n, nl));
+    ASW_TRY(launch_perm_scan_v(s_n, nl));
     a.N = nrm.as<double>(); a.Nout = nullptr; a.vol = keep_volume ? f->vol.as<float>() : nullptr;
     for (int c0 = 0; c0 < n; c0 += chunk) {  // ascending: the vertical pass merges a chunk's winners into the running minimum
         a.cost = raw.as<uint8_t>() + (size_t)c0 * plane; a.nc = std::min(chunk, n - c0); a.cbeg = c0; a.first = c0 == 0;
         ASW_TRY(launch_perm_scan_h(ctx->stream, a));
-        if (c0 == 0) ASW_HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->aux_ev[1], 0));  // join: the vertical pass divides by N
+        if (c0 == 0) ASW_TRY(side.join());  // the vertical pass divides by N
         ASW_TRY(launch_perm_scan_v(ctx->stream, a));
     }
     return agg_end(ctx, 4 + 2 * chunks);  // two permeability planes, N's two passes, two passes per chunk
@@ -1033,7 +1004,7 @@ static int run_scanline(asw_ctx* ctx, Frame* f, const MethodInfo* m, const Match
 
 // The method on every level of the pair's 2x2-mean pyramid, coarsest first, then the combination of the levels' volumes and its
 // winner (k_cross_scale.hip).  Everything goes on the context's stream; the coarse pairs and volumes live in ctx->coarse, the
-// runners' named scratch is reused level after level.  The finest level runs last: ev[2] / ev[3] stay on it.
+// runners' named scratch is reused level after level.  The finest level runs last: the clock's aggregate marks stay on it.
 static int run_cross_scale(asw_ctx* ctx, Frame* f, const MethodInfo* m, const MatchParams& mp, bool store)
 {
     static_assert(DT_CROSS_SCALES.hi == CROSS_SCALE_MAX, "the levels decode_disparity_type accepts are those ctx->coarse holds");
@@ -1081,7 +1052,7 @@ int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp_in, 
     // BLO1, the bilateral grid) are asked for it; what the CALLER keeps is decided below
     const bool want_volume = keep_volume || mp.subpixel != 0 || mp.scan_p1 != 0 || confidence;
     ASW_HIP_TRY(hipSetDevice(ctx->device));
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
+    ASW_TRY(ctx->clock.begin_total());
     int rc;
     if (mp.cross_scales)  // every level's volume is wanted; the combined one is stored over the finest only for a reader
         rc = run_cross_scale(ctx, f, m, mp, want_volume);
@@ -1104,10 +1075,7 @@ int run_method(asw_ctx* ctx, Frame* f, int algorithm, const MatchParams& mp_in, 
     }
     const size_t kept_floats = keep_volume ? f->vol_floats : 0;  // a volume asked for by the sub-pixel step alone is not the caller's
     f->vol_floats = 0;  // restored together with has_disp once nothing can fail any more
-    if (sync)
-        ASW_TRY(timed_finish(ctx));
-    else  // pipelined callers (batch scheduler) order and wait on the stream themselves
-        ASW_HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
+    ASW_TRY(ctx->clock.finish(sync));  // !sync: pipelined callers (batch scheduler) order and wait on the stream themselves
     f->has_disp = true; f->disp_rows = f->rows; f->disp_cols = f->cols; f->vol_floats = kept_floats; f->has_conf = confidence;
     return ASW_OK;
 }
@@ -1240,19 +1208,12 @@ static int match_smoothed(asw_ctx* ctx, Frame* f, int algorithm, int win_size, i
     int T = 0;
     ASW_TRY(check_smooth_params(f->rows, f->cols, f->channels, word, sigma_c, lambda, false, &T));
     ASW_TRY(run_method(ctx, f, algorithm, match_params(ASW_DISPARITY_LEFT, win_size, min_disparity, num_disparity), false, true, true));
-    asw_timing sum = ctx->timing;  // the match and its confidence
     f->invalidate_results();  // whatever fails from here on, the slot holds no result
     const float* pairs = f->dconf.as<float>();
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
-    ASW_TRY(run_smooth(ctx, f->L.as<uint8_t>(), f->channels, pairs, pairs + 1, 2, f->rows, f->cols, T, sigma_c, lambda,
-                       f->disp.as<float>()));
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
-    ASW_HIP_TRY(hipEventSynchronize(ctx->ev[1]));
-    float t = 0;
-    ASW_HIP_TRY(hipEventElapsedTime(&t, ctx->ev[0], ctx->ev[1]));
-    sum.total_ms += t;
-    sum.cost_ms = sum.total_ms - sum.aggregate_ms;
-    ctx->timing = sum;
+    ASW_TRY(ctx->clock.timed_step(ctx->clock.timing /* the match and its confidence */, [&] {
+        return run_smooth(ctx, f->L.as<uint8_t>(), f->channels, pairs, pairs + 1, 2, f->rows, f->cols, T, sigma_c, lambda,
+                          f->disp.as<float>());
+    }));
     f->has_disp = true; f->disp_rows = f->rows; f->disp_cols = f->cols;
     return ASW_OK;
 }
@@ -1283,20 +1244,14 @@ int match_refined(asw_ctx* ctx, Frame* f, int algorithm, int win_size, int min_d
         ASW_TRY(run_method(ctx, f, algorithm, mp, false));
         std::swap(f->disp, *side[dt]);
         f->invalidate_results();
-        sum.total_ms += ctx->timing.total_ms; sum.aggregate_ms += ctx->timing.aggregate_ms;
-        sum.aggregate_launches += ctx->timing.aggregate_launches;
+        sum.total_ms += ctx->clock.timing.total_ms; sum.aggregate_ms += ctx->clock.timing.aggregate_ms;
+        sum.aggregate_launches += ctx->clock.timing.aggregate_launches;
     }
     ASW_TRY(f->disp.ensure((size_t)f->rows * f->cols * sizeof(float)));
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
-    ASW_TRY(run_refine(ctx, f->L.as<uint8_t>(), f->channels, side[0]->as<float>(), side[1]->as<float>(), f->rows, f->cols, rp,
-                       f->disp.as<float>(), n_rejected, n_unfillable));
-    ASW_HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
-    ASW_HIP_TRY(hipEventSynchronize(ctx->ev[1]));
-    float t = 0;
-    ASW_HIP_TRY(hipEventElapsedTime(&t, ctx->ev[0], ctx->ev[1]));
-    sum.total_ms += t;
-    sum.cost_ms = sum.total_ms - sum.aggregate_ms;
-    ctx->timing = sum;
+    ASW_TRY(ctx->clock.timed_step(sum, [&] {
+        return run_refine(ctx, f->L.as<uint8_t>(), f->channels, side[0]->as<float>(), side[1]->as<float>(), f->rows, f->cols, rp,
+                          f->disp.as<float>(), n_rejected, n_unfillable);
+    }));
     f->has_disp = true; f->disp_rows = f->rows; f->disp_cols = f->cols;
     return ASW_OK;
 }

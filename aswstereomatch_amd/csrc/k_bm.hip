@@ -266,8 +266,8 @@ int launch_bm(hipStream_t s, const BmLaunch& a)
     if (a.vol) ASW_HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)a.vol, 0x7fc00000, plane * D, s));  // NaN where nothing is computed
     if (y1 <= y0 || x1 <= x0) {  // empty valid region: the whole map is FILTERED (this library's definition)
         ASW_TRY(launch_fill_s16(s, a.disp16, plane, (short)FILTERED));
-        if (a.ev_agg0) ASW_HIP_TRY(hipEventRecord(a.ev_agg0, s));
-        if (a.ev_agg1) ASW_HIP_TRY(hipEventRecord(a.ev_agg1, s));
+        ASW_TRY(a.agg.begin());
+        ASW_TRY(a.agg.end());
         return ASW_OK;
     }
     // carve the scratch in bm_scratch_bytes' order
@@ -278,9 +278,9 @@ int launch_bm(hipStream_t s, const BmLaunch& a)
     int* cost = (int*)p; p += plane * 4;
     short* raw = (short*)p;
     ASW_TRY(ASW_LAUNCH(k_bm_prefilter, dim3(blocks(plane, 256), 2), dim3(256), 0, s, a.L, a.R, H, W, a.cap, pf));
-    if (a.ev_agg0) ASW_HIP_TRY(hipEventRecord(a.ev_agg0, s));
+    ASW_TRY(a.agg.begin());
     ASW_TRY(dispatch_npl(D, [&](auto npl) { return launch_match<decltype(npl)::value>(s, a, pf, raw, cost); }));
-    if (a.ev_agg1) ASW_HIP_TRY(hipEventRecord(a.ev_agg1, s));
+    ASW_TRY(a.agg.end());
     const int minX1 = minD + D;
     if (a.M >= 0 && minX1 < W) {
         ASW_HIP_TRY(hipMemsetAsync(key, 0xff, plane * 8, s));

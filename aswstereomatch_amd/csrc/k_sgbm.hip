@@ -593,8 +593,8 @@ int launch_sgbm(hipStream_t s, const SgbmLaunch& a)
     if (W <= minD + D) {  // no valid column: every pixel INVALID, nothing to filter
         ASW_TRY(launch_fill_s16(s, a.disp16, plane, (short)INVALID));
         if (a.vol) ASW_HIP_TRY(hipMemsetAsync(a.vol, 0, plane * D * sizeof(float), s));
-        if (a.ev_agg0) ASW_HIP_TRY(hipEventRecord(a.ev_agg0, s));
-        if (a.ev_agg1) ASW_HIP_TRY(hipEventRecord(a.ev_agg1, s));
+        ASW_TRY(a.agg.begin());
+        ASW_TRY(a.agg.end());
         return ASW_OK;
     }
     const int Wv = W - (minD + D);
@@ -616,9 +616,9 @@ int launch_sgbm(hipStream_t s, const SgbmLaunch& a)
         ASW_TRY(ASW_LAUNCH(k_sgbm_hcost, dim3(blocks((size_t)H * D, 256)), dim3(256), 0, s, pf, H, W, a.cn, minD, D, a.w / 2, hb));
     }
     ASW_HIP_TRY(hipMemsetAsync(key, 0xff, plane * 8, s));
-    if (a.ev_agg0) ASW_HIP_TRY(hipEventRecord(a.ev_agg0, s));
+    ASW_TRY(a.agg.begin());
     ASW_TRY(dispatch_npl(D, [&](auto npl) { return launch_paths<decltype(npl)::value>(s, a, hb, C, T, disp_raw, key); }));
-    if (a.ev_agg1) ASW_HIP_TRY(hipEventRecord(a.ev_agg1, s));
+    ASW_TRY(a.agg.end());
     if (a.vol) {
         ASW_TRY(ASW_LAUNCH(k_sgbm_volume, dim3(blocks(plane * D, 256)), dim3(256), 0, s, T, H, W, minD, D, a.vol));
     }

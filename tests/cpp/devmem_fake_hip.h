@@ -1,7 +1,10 @@
-// The few HIP runtime calls csrc/asw_devmem.h and asw_ctx's destructor make, defined here so that a host program runs them without
-// libamdhip64 and without a GPU (tests/test_devmem_cpu.py).  "Device" memory is host memory, which puts it under the sanitizers:
+// The few HIP runtime calls csrc/asw_devmem.h, csrc/asw_streams.h and asw_ctx's destructor make, defined here so that a host program
+// runs them without libamdhip64 and without a GPU (tests/test_devmem_cpu.py, tests/test_streams_cpu.py).  "Device" memory is host
+// memory, which puts it under the sanitizers:
 //   - allocations, streams and events are counted, and freeing / destroying / copying into one that was never handed out aborts;
-//   - the n-th hipMalloc, hipMemcpyAsync or hipStreamSynchronize from now can be told to fail;
+//   - the n-th hipMalloc, hipMemcpyAsync, hipStreamSynchronize or event call from now can be told to fail;
+//   - event records, waits and synchronisations are logged in order with their stream and event, which must be the fake's own;
+//     hipEventElapsedTime gives what the program set for the pair;
 //   - hipMemcpyAsync only records the copy: it is carried out at the next hipStreamSynchronize of its stream, so host data that
 //     died in between is read after its lifetime -- which AddressSanitizer reports.
 #pragma once
@@ -29,6 +32,15 @@ struct FakeHip {
     int fail_malloc = 0, fail_copy = 0, fail_sync = 0;  // n > 0: the n-th call from now fails, once
     struct Copy { void* dst; const void* src; size_t bytes; hipStream_t stream; };
     std::vector<Copy> pending;
+    // the event calls of csrc/asw_streams.h ("record", "wait", "sync") and every hipStreamSynchronize ("stream-sync"), in the order
+    // they were made; a failed event call is not logged
+    struct EventCall {
+        const char* call; hipStream_t stream; hipEvent_t event;
+        bool operator==(const EventCall& o) const { return !strcmp(call, o.call) && stream == o.stream && event == o.event; }
+    };
+    std::vector<EventCall> log;
+    int fail_event = 0;  // counts hipEventRecord, hipStreamWaitEvent and hipEventSynchronize together
+    std::map<std::pair<hipEvent_t, hipEvent_t>, float> elapsed;  // what hipEventElapsedTime gives for (start, stop): set by the program
     bool due(int& n) { return n > 0 && --n == 0; }
     hipStream_t new_stream() { void* s = malloc(1); streams.insert(s); return (hipStream_t)s; }
     hipEvent_t new_event() { void* e = malloc(1); events.insert(e); return (hipEvent_t)e; }
@@ -71,6 +83,7 @@ hipError_t hipStreamSynchronize(hipStream_t stream)
 {
     CHECK(fake.streams.count(stream) == 1);
     fake.syncs++;
+    fake.log.push_back({"stream-sync", stream, nullptr});
     std::vector<FakeHip::Copy> rest;
     for (auto& c : fake.pending) {
         if (c.stream != stream) { rest.push_back(c); continue; }
@@ -97,6 +110,33 @@ hipError_t hipEventDestroy(hipEvent_t e)
 {
     CHECK(fake.events.erase(e) == 1);
     free(e);
+    return hipSuccess;
+}
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t stream)
+{
+    CHECK(fake.events.count(e) == 1 && fake.streams.count(stream) == 1);
+    if (fake.due(fake.fail_event)) return hipErrorUnknown;
+    fake.log.push_back({"record", stream, e});
+    return hipSuccess;
+}
+hipError_t hipStreamWaitEvent(hipStream_t stream, hipEvent_t e, unsigned flags)
+{
+    CHECK(fake.events.count(e) == 1 && fake.streams.count(stream) == 1 && flags == 0);
+    if (fake.due(fake.fail_event)) return hipErrorUnknown;
+    fake.log.push_back({"wait", stream, e});
+    return hipSuccess;
+}
+hipError_t hipEventSynchronize(hipEvent_t e)
+{
+    CHECK(fake.events.count(e) == 1);
+    if (fake.due(fake.fail_event)) return hipErrorUnknown;
+    fake.log.push_back({"sync", nullptr, e});
+    return hipSuccess;
+}
+hipError_t hipEventElapsedTime(float* ms, hipEvent_t start, hipEvent_t stop)
+{
+    CHECK(fake.events.count(start) == 1 && fake.events.count(stop) == 1 && fake.elapsed.count({start, stop}) == 1);
+    *ms = fake.elapsed[{start, stop}];
     return hipSuccess;
 }
 }

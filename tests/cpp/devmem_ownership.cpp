@@ -16,9 +16,11 @@ static void exercise()
 {
     asw_ctx ctx;
     ctx.stream = fake.new_stream();
-    for (auto& s : ctx.aux) s = fake.new_stream();
-    for (auto& e : ctx.ev) e = fake.new_event();
-    for (auto& e : ctx.aux_ev) e = fake.new_event();
+    ctx.clock.stream = ctx.stream;
+    for (auto& s : ctx.side.stream) s = fake.new_stream();
+    for (hipEvent_t* e : {&ctx.clock.total_start, &ctx.clock.total_stop, &ctx.clock.agg_start, &ctx.clock.agg_stop, &ctx.side.fork,
+                          &ctx.side.joined[0], &ctx.side.joined[1]})
+        *e = fake.new_event();
     // every member that bears a buffer
     fill(ctx.host_frame, 1000);
     for (Frame& f : ctx.coarse) fill(f, 500);
